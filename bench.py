@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X hot path (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-extras]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full [--no-extras]] [--dump-outputs DIR]
+
+A plain run does only what the headline needs: it sets up, runs the W warm-up steps, times the K
+steps and prints one JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` = milliseconds per timed step, and the roofline fraction of the timed region).
+--full adds everything else the line used to carry (see below): the per-launch spread and the
+clock ramp, the parity checks, the CPU baseline, the other BASELINE configurations (`extras`,
+which --no-extras leaves out again) and the figures of the committed counter passes.
+--dump-outputs DIR writes what the timed path computed in its last step: a fixed, seeded sample of
+DUMP_ROWS rows of every product C_i of the batch, as DIR/matmul_C<i>_rows.npy (float32).  The inputs
+depend only on the arguments (numpower_amd/synth.py), so two builds can be compared output for output.
 
 A "step" is one pass of the hot path over one batch of synthetic input: a batch of 16 independent
 nd::matmul products of two 4096 x 4096 fp32 matrices each (BASELINE config 2, the configuration the
@@ -9,7 +19,7 @@ metric is quoted on), one np_sgemm launch per product, 4 distinct operand sets. 
 of round 6 a step was ONE product: W = 5 such steps are 5 ms of matrix work, the device needs ~50 ms
 to raise the matrix cores' clock, and a timed region right behind them reported that ramp —
 0.82-0.85 of the MFMA peak for a kernel that runs at 0.91.  bench_matmul's docstring; the figure of
-the old step definition is still in the line: roofline.frac_launches_5_24; NP_BENCH_STEP_PRODUCTS=1
+the old step definition is in the --full line: roofline.frac_launches_5_24; NP_BENCH_STEP_PRODUCTS=1
 runs the old step.)
 Inputs are resident in HBM before the timed region.  K steps are launched back to back between
 a barrier + device sync on both sides; `value` = all ranks' FLOPs / max-over-ranks wall time.
@@ -27,9 +37,10 @@ gather through np_comm_*).  NP_BENCH_SHARE_DEVICE=1 puts every spawned rank on d
 a collective library that allows ranks to share a device (the tests' stand-in does, RCCL does not): the line then
 says "valid": false; it is how the N > 1 path runs on a one-GPU box, not a measurement.
 
-The JSON line also carries
+Every line carries
   roofline      achieved vs peak for the dominant kernel (fp32 MFMA GEMM), from HIP events
                 recorded on the kernel's own stream around the timed launches
+With --full it also carries the launch spread and ramp inside `roofline`, `parity`, and
   cpu_baseline  the oracle (CPU restatement of the reference: cblas_sgemm from the OpenBLAS found
                 on this host) timed on a bounded sample of the same workload
   extras        the second half of the metric (elementwise add on 1e8 floats, GB/s) and the other
@@ -320,9 +331,23 @@ def cpu_time(fn, budget_s=8.0, max_iters=5):
 
 STEP_PRODUCTS = max(1, int(os.environ.get("NP_BENCH_STEP_PRODUCTS", "16")))
 PRODUCT_SETS = 4
+DUMP_ROWS = 256          # --dump-outputs: rows per product, 4 MiB each
+DUMP_SEED = 20240611
 
 
-def bench_matmul(dist: Dist, steps, warmup, do_cpu):
+def dump_outputs(path, sets, n, products):
+    """--dump-outputs: the same DUMP_ROWS rows (a fixed, seeded choice) of every C_i the last step wrote."""
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_ROWS, replace=False))
+    D.sync()
+    for i in range(min(products, PRODUCT_SETS)):
+        Ci = sets[i][2].to_host()
+        np.save(out / ("matmul_C%d_rows.npy" % i), np.ascontiguousarray(Ci[rows], dtype=np.float32))
+        del Ci
+
+
+def bench_matmul(dist: Dist, steps, warmup, full=False, do_cpu=False, dump=None):
     """The headline.  A STEP is one batch of STEP_PRODUCTS independent 4096^3 products, one np_sgemm launch each, cycling
     over PRODUCT_SETS distinct (A_i, B_i, C_i): A_i = A * 2^-i (exact), B_i a copy of B — so every C_i must equal
     C_0 * 2^-i BIT FOR BIT, which is checked over all elements next to the fp64 check of C_0.
@@ -331,7 +356,9 @@ def bench_matmul(dist: Dist, steps, warmup, do_cpu):
     W warm-up steps of ONE 1 ms product each (the steps of rounds 1-6's earlier lines) end long before that; a timed region
     behind them reported the ramp, 0.82-0.85, for a kernel that runs at 0.91.  The W warm-up steps are launched with an event
     pair around every product (they are untimed anyway): `ramp` in the result is what those launches took, and
-    `frac_launches_5_24` the figure the one-product steps of the earlier lines would have given in this very run."""
+    `frac_launches_5_24` the figure the one-product steps of the earlier lines would have given in this very run.
+    Only with full=True: the ramp, the launch spread, the parity checks and the CPU baseline (do_cpu); a plain run warms up,
+    times and, if asked (dump = a directory), writes the last step's outputs."""
     n = 4096
     seed = 3 + 100 * dist.rank
     A = synth.uniform((n, n), seed, -1.0, 1.0)
@@ -367,8 +394,19 @@ def bench_matmul(dist: Dist, steps, warmup, do_cpu):
             product(j)
 
     for _ in range(warmup):      # the W untimed warm-up steps (timed()'s own warm-up count is 0 below)
-        warm_step()
+        if full:
+            warm_step()
+        else:
+            step()
     wall, ev_ms = timed(dist, step, steps, 0)
+    if dump is not None and dist.rank == 0:
+        dump_outputs(dump, sets, n, P)
+    out = {"wall_s": wall, "event_ms": ev_ms, "flop_per_step": flop * P, "flop_per_launch": flop, "products_per_step": P}
+    if not full:
+        for trio in sets:
+            for d in trio:
+                d.free()
+        return out
     ramp_ms = [t.elapsed_ms() for t in ramp_timers]
     ramp = None
     if ramp_ms:
@@ -402,11 +440,10 @@ def bench_matmul(dist: Dist, steps, warmup, do_cpu):
         batch_ok = batch_ok and bool((Ci.view(np.uint32) == (C0 * np.float32(2.0 ** -i)).view(np.uint32)).all())
         del Ci
     del C0
-    out = {
-        "wall_s": wall, "event_ms": ev_ms, "flop_per_step": flop * P, "flop_per_launch": flop, "products_per_step": P,
+    out.update({
         "launch_ms": launch_ms, "ramp": ramp,
         "parity_max_norm_err_vs_fp64": err, "parity_ok": bool(err <= 1e-6) and batch_ok, "batch_linearity_bit_exact": batch_ok,
-    }
+    })
     if do_cpu:
         from oracle import oracle
         info = oracle.use_openblas()
@@ -1224,7 +1261,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-extras", action="store_true", help="headline only")
+    ap.add_argument("--full", action="store_true",
+                    help="also the launch spread, parity checks, CPU baseline, the other BASELINE configs and counter figures")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out the other BASELINE configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the last timed step's outputs to DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -1242,7 +1283,7 @@ def main():
         line = {"metric": METRIC, "value": 0.0, "unit": "GFLOP/s", "n_gpus": args.gpus,
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": wall / args.steps * 1e3,
                 "dry_run": True, **who}
-        if dist.use_torch and args.gpus > 1 and not args.no_extras:
+        if args.full and dist.use_torch and args.gpus > 1 and not args.no_extras:
             # config 5's N > 1 report on gloo: every leg timed and checked, whatever one leg's parity says
             try:
                 line["extras"] = {"config5_batched_matmul_allgather": _compact(bench_config5(dist, max(2, args.steps // 2), 2))}
@@ -1253,13 +1294,13 @@ def main():
         dist.close()
         return
     _diag_add(dist, "before anything")
-    mm = bench_matmul(dist, args.steps, args.warmup, do_cpu=rank0 and args.gpus == 1 and os.environ.get("NP_BENCH_DIAG_NOCPU") != "1")
+    do_cpu = args.full and rank0 and args.gpus == 1 and os.environ.get("NP_BENCH_DIAG_NOCPU") != "1"
+    mm = bench_matmul(dist, args.steps, args.warmup, full=args.full, do_cpu=do_cpu, dump=args.dump_outputs)
     _diag_add(dist, "after matmul + cpu baseline")
     flop = mm["flop_per_launch"]                                            # one 4096^3 product = one launch
     P = mm["products_per_step"]
     value = mm["flop_per_step"] * args.steps * args.gpus / mm["wall_s"] / 1e9   # GFLOP/s, whole job
     kernel_tflops = flop / (mm["event_ms"] / (args.steps * P)) / 1e9        # this rank's kernel: average launch of the timed region
-    ramp = mm.get("ramp") or {}
     result = {
         "metric": METRIC, "value": value, "unit": "GFLOP/s", "n_gpus": args.gpus, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": mm["wall_s"] / args.steps * 1e3, "higher_is_better": True,
@@ -1271,14 +1312,21 @@ def main():
         "roofline": {"bound": "mfma", "achieved": kernel_tflops, "peak": PEAK_FP32_MFMA_TFLOPS,
                      "unit": "TFLOP/s", "frac": kernel_tflops / PEAK_FP32_MFMA_TFLOPS, "traffic": None,
                      "kernel": "sgemm_dma_kernel 256x128x16 (v_mfma_f32_32x32x2_f32, LDS-DMA staging)",
-                     "algorithmic_flop_per_launch": flop, "launches_per_step": P, "launch_ms": mm["launch_ms"],
-                     "frac_best_launch": flop / mm["launch_ms"]["min"] / 1e9 / PEAK_FP32_MFMA_TFLOPS,
-                     # what the one-product steps of the lines before this one reported, measured in THIS run on the warm-up launches
-                     "frac_launches_5_24": (ramp["TFLOPs_launches_5_24"] / PEAK_FP32_MFMA_TFLOPS) if ramp.get("TFLOPs_launches_5_24") else None,
-                     "ramp": ramp or None},
-        "parity": {"matmul_max_norm_err_vs_fp64": mm["parity_max_norm_err_vs_fp64"], "ok": mm["parity_ok"],
-                   "batch_linearity_bit_exact": mm["batch_linearity_bit_exact"]},
+                     "algorithmic_flop_per_launch": flop, "launches_per_step": P},
     }
+    if not args.full:
+        if args.gpus > 1:
+            result.update(dist.describe())      # ranks_seen: one collective, every rank calls it
+        _finish(result, args, dist, rank0)
+        return
+    ramp = mm.get("ramp") or {}
+    result["roofline"].update({
+        "launch_ms": mm["launch_ms"], "frac_best_launch": flop / mm["launch_ms"]["min"] / 1e9 / PEAK_FP32_MFMA_TFLOPS,
+        # what the one-product steps of the lines before this one reported, measured in THIS run on the warm-up launches
+        "frac_launches_5_24": (ramp["TFLOPs_launches_5_24"] / PEAK_FP32_MFMA_TFLOPS) if ramp.get("TFLOPs_launches_5_24") else None,
+        "ramp": ramp or None})
+    result["parity"] = {"matmul_max_norm_err_vs_fp64": mm["parity_max_norm_err_vs_fp64"], "ok": mm["parity_ok"],
+                        "batch_linearity_bit_exact": mm["batch_linearity_bit_exact"]}
     result.update(dist.describe())      # ranks_seen + the collective library and its version (a collective: every rank calls it)
     if "cpu" in mm:
         result["cpu_baseline"] = mm["cpu"]
@@ -1406,6 +1454,11 @@ def main():
     if extras:
         result["extras"] = _compact(extras)
         result["summary"] = _summary(result, extras)       # LAST key: the tail of the line shows every BASELINE config
+    _finish(result, args, dist, rank0)
+
+
+def _finish(result, args, dist, rank0):
+    """The one exit of a measured run: mark a shared-device run, print the line on rank 0, close the communicator."""
     if os.environ.get("NP_BENCH_SHARE_DEVICE") == "1" and args.gpus > 1:
         # N ranks on ONE device (possible only over a collective library that allows it — RCCL does not): every line of the
         # N > 1 path runs on hardware, the ranks take the GPU from each other, and the figures are not a measurement of anything

@@ -630,7 +630,9 @@ typedef void (*sgemm_fn)(int, int, int, int, int, int, float, const float *, int
 typedef void (*sgemv_fn)(int, int, int, int, float, const float *, int, const float *, int, float,
                          float *, int);
 typedef void (*setthreads_fn)(int);
+typedef int (*getthreads_fn)(void);
 static sgemm_fn g_sgemm = NULL;
+static getthreads_fn g_blas_threads = NULL;
 static sgemv_fn g_sgemv = NULL;
 static void *g_blas = NULL;
 
@@ -645,7 +647,13 @@ int oracle_set_blas(const char *path, const char *prefix, int threads) {
     snprintf(name, sizeof(name), "%scblas_sgemv", prefix);
     sgemv_fn v = (sgemv_fn) dlsym(h, name);
     if (!f || !v) return fail("cblas_sgemm/cblas_sgemv not found in BLAS library");
+    snprintf(name, sizeof(name), "%sopenblas_get_num_threads", prefix);
+    g_blas_threads = (getthreads_fn) dlsym(h, name);
     if (threads > 0) {
+        /* OpenBLAS sizes its per-thread buffers for the thread count it starts with
+         * (OPENBLAS_NUM_THREADS / OMP_NUM_THREADS, capped at the CPUs it sees); asking for more
+         * later makes sgemm crash.  So the count is only ever lowered. */
+        if (g_blas_threads && threads > g_blas_threads()) threads = g_blas_threads();
         snprintf(name, sizeof(name), "%sopenblas_set_num_threads", prefix);
         setthreads_fn st = (setthreads_fn) dlsym(h, name);
         if (st) st(threads);
@@ -658,6 +666,12 @@ int oracle_set_blas(const char *path, const char *prefix, int threads) {
 
 /* 1 = external CBLAS (the reference's own back end), 0 = built-in plain sgemm */
 int oracle_blas_kind(void) { return g_sgemm != NULL; }
+
+/* the thread count the external CBLAS runs with (1 without one, 0 if it does not say) */
+int oracle_blas_threads(void) {
+    if (!g_sgemm) return 1;
+    return g_blas_threads ? g_blas_threads() : 0;
+}
 
 static void plain_sgemm(int M, int N, int K, const float *A, const float *B, float *C) {
     /* i-k-j loop, row-major, fp32 accumulation; only used when no CBLAS could be found */

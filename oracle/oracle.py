@@ -71,6 +71,7 @@ def load():
     lib.oracle_set_blas.restype = C.c_int
     lib.oracle_set_blas.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
     lib.oracle_blas_kind.restype = C.c_int
+    lib.oracle_blas_threads.restype = C.c_int
     lib.oracle_matmul.argtypes = [C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]
     lib.oracle_matvec.argtypes = [C.c_int, C.c_int, _fp, _fp, _fp]
     lib.oracle_matmul_check.restype = C.c_int
@@ -437,7 +438,7 @@ def use_openblas(threads: int | None = None):
     if load().oracle_set_blas(path.encode(), prefix.encode(), t) != 0:
         _blas_info = {"kind": "builtin-plain-sgemm", "threads": 1, "error": _err().args[0]}
         return _blas_info
-    _blas_info = {"kind": "openblas", "path": path, "threads": t}
+    _blas_info = {"kind": "openblas", "path": path, "threads": load().oracle_blas_threads() or t}
     return _blas_info
 
 

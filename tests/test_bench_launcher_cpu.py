@@ -24,7 +24,7 @@ def run_bench(args, extra_env=None, timeout=240):
 
 @pytest.mark.parametrize("n", [2, 3])
 def test_self_launch_prints_one_json_line(n):
-    p = run_bench(["--gpus", str(n), "--steps", "4", "--warmup", "1"])
+    p = run_bench(["--gpus", str(n), "--steps", "4", "--warmup", "1", "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout
@@ -40,10 +40,19 @@ def test_self_launch_prints_one_json_line(n):
     assert c5["parity_ok"] is True and c5["scaling"] == "strong" and "%d slab(s) of 8" % n in c5["workload"]
 
 
+def test_a_plain_run_carries_only_the_headline():
+    """Without --full the line holds the timed steps alone: no config-5 legs, no other configurations."""
+    p = run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    j = json.loads(p.stdout.strip())
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["ranks_seen"] == 2
+    assert "extras" not in j
+
+
 def test_a_leg_that_fails_parity_does_not_cost_the_other_legs_their_numbers():
-    """VERDICT r05 next #6a: `bench.py --gpus N` prints ranks_seen, the collective library and per-leg medians EVEN IF one leg's
+    """VERDICT r05 next #6a: `bench.py --gpus N --full` prints ranks_seen, the collective library and per-leg medians EVEN IF one leg's
     result is wrong — the line says parity_ok false with that leg's error, and every leg keeps its timing."""
-    p = run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1"], {"NP_BENCH_DRYRUN_BAD_LEG": "overlapped_2"})
+    p = run_bench(["--gpus", "2", "--steps", "4", "--warmup", "1", "--full"], {"NP_BENCH_DRYRUN_BAD_LEG": "overlapped_2"})
     assert p.returncode == 0, p.stderr[-2000:]
     j = json.loads(p.stdout.strip())
     c5 = j["extras"]["config5_batched_matmul_allgather"]

@@ -125,10 +125,11 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def test_sharded_matmul_across_real_ranks(tmp_path, oracle):
+def test_sharded_matmul_across_real_ranks(tmp_path, request):
     devices = _device_count()
     if devices < 2:
         pytest.skip("needs two GPUs in one box (RCCL refuses two ranks on one device)")
+    oracle = request.getfixturevalue("oracle")      # after the check: a one-GPU box does no work for this test
     world = 4 if devices >= 4 else 2
     _run_workers(WORKER, world, tmp_path, "rank")
     check_abi_worker_results(world, tmp_path, oracle)

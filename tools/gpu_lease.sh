@@ -3,7 +3,7 @@
 #   gpurun --timeout 1500 -- 'bash tools/gpu_lease.sh <recipe> [tag]'
 # Recipes (outputs under gpurun_out/<tag>/, tag defaults to the recipe name; copy what should be judged to profiles/rNN/):
 #   tests      the -m gpu suite (the gate)
-#   bench      bench.py twice: default flags and the driver's (--steps 20 --warmup 5)
+#   bench      bench.py --full twice: default flags and the driver's (--steps 20 --warmup 5)
 #   world1     bench.py's N > 1 code paths on one GPU (torch.distributed plumbing, then the C-ABI communicator)
 #   peers      bench.py --gpus 2 with both ranks on this GPU over tests/loopback_rccl (NP_COMM=abi): the N > 1 path with a peer
 #   profile    rocprofv3 --kernel-trace --stats of bench.py -> bench_kernel_stats.csv
@@ -30,8 +30,12 @@ r_tests() {
     tail -4 "$O/pytest_gpu.log"
 }
 r_bench() {
-    python bench.py > "$O/bench.json" 2> "$O/bench.err"; echo "bench rc=$?"
-    python bench.py --steps 20 --warmup 5 > "$O/bench_driver_args.json" 2> "$O/bench_driver_args.err"; echo "bench (driver args) rc=$?"
+    # each GPU run under its own time limit; after a failed one nothing more is started on the GPU
+    timeout -k 10 900 python bench.py --full > "$O/bench.json" 2> "$O/bench.err"; rc=$?; echo "bench rc=$rc"
+    [ $rc -eq 0 ] || return $rc
+    timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 > "$O/bench_driver_args.json" 2> "$O/bench_driver_args.err"; rc=$?
+    echo "bench (driver args) rc=$rc"
+    [ $rc -eq 0 ] || return $rc
     python - "$O" <<'PY'
 import json, sys
 for name in ("bench.json", "bench_driver_args.json"):
@@ -44,17 +48,26 @@ for name in ("bench.json", "bench_driver_args.json"):
 PY
 }
 r_world1() {
-    NP_BENCH_FORCE_DIST=1 timeout 600 python bench.py --steps 20 --warmup 5 > "$O/bench_world1_torch.json" 2> "$O/w1t.err"; echo "world1 torch rc=$?"
-    NP_BENCH_FORCE_DIST=1 NP_COMM=abi timeout 600 python bench.py --steps 20 --warmup 5 > "$O/bench_world1_abi.json" 2> "$O/w1a.err"; echo "world1 abi rc=$?"
+    NP_BENCH_FORCE_DIST=1 timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > "$O/bench_world1_torch.json" 2> "$O/w1t.err"; rc=$?
+    echo "world1 torch rc=$rc"
+    [ $rc -eq 0 ] || return $rc
+    NP_BENCH_FORCE_DIST=1 NP_COMM=abi timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > "$O/bench_world1_abi.json" 2> "$O/w1a.err"; rc=$?
+    echo "world1 abi rc=$rc"
+    return $rc
 }
 r_peers() {
     # the N > 1 bench with two ranks that SHARE this GPU, over the tests' stand-in for librccl.so.1 (tests/loopback_rccl): every
     # leg of config 5 through np_comm_* with a real peer process; "valid": false in the line - a code-path run, not a measurement
-    LD_LIBRARY_PATH="$R/tests/loopback_rccl/lib:$LD_LIBRARY_PATH" NP_COMM=abi NP_BENCH_SHARE_DEVICE=1 timeout 700 python bench.py --gpus 2 --steps 10 --warmup 3 \
-        > "$O/bench_two_ranks_one_gpu_abi.json" 2> "$O/peers.err"; echo "peers (2 ranks, one GPU, loopback) rc=$?"
+    LD_LIBRARY_PATH="$R/tests/loopback_rccl/lib:$LD_LIBRARY_PATH" NP_COMM=abi NP_BENCH_SHARE_DEVICE=1 timeout -k 10 700 python bench.py --full --gpus 2 --steps 10 --warmup 3 \
+        > "$O/bench_two_ranks_one_gpu_abi.json" 2> "$O/peers.err"; rc=$?
+    echo "peers (2 ranks, one GPU, loopback) rc=$rc"
+    return $rc
 }
 r_profile() {
-    (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats -d "$O/kt" -o bench --output-format csv -- python "$R/bench.py" > "$O/bench_under_rocprof.json" 2> "$O/bench_under_rocprof.err")
+    # run from a scratch directory of its own (rocprofv3 writes beside the working directory)
+    (d=$(mktemp -d) && cd "$d" && export TMPDIR="$d" &&
+     timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/kt" -o bench --output-format csv -- python "$R/bench.py" --full \
+        > "$O/bench_under_rocprof.json" 2> "$O/bench_under_rocprof.err") || return $?
     cp "$O"/kt/*kernel_stats.csv "$O/bench_kernel_stats.csv" 2>/dev/null
     head -16 "$O/bench_kernel_stats.csv" | cut -c1-200
     # the same kernels launched at the BASELINE sizes ONLY (bench.py also runs add / sum at 1000 x 1000 for config 1, which share
@@ -153,7 +166,7 @@ case "$RECIPE" in
     profile) r_profile ;;
     counters) r_counters ;;
     sweeps) r_sweeps ;;
-    evidence) r_tests; r_bench; r_world1; r_peers; r_profile; r_counters; r_sweeps ;;
+    evidence) r_tests && r_bench && r_world1 && r_peers && r_profile && r_counters && r_sweeps ;;
     cleanbuild) r_cleanbuild ;;
     fuzz) r_fuzz ;;
     binding) r_binding ;;
