@@ -1,0 +1,45 @@
+/*
+ * hip_linalg.h — det / inv / lu / solve of GPU arrays on the device LU (np_getrf / np_getrs of include/np_hip.h).
+ *
+ * The reference computes these with LAPACK on the CPU and, under --with-cuda, through cuSOLVER / its own kernel
+ * (cuda_math.cu); its NDArray_Solve refuses GPU arrays.  tools/apply_with_hip.py inserts an early-out into each of the
+ * four functions of src/ndmath/linalg.c:
+ *
+ *     NDArray_Det      at the top                                   return NPH_Det(a);
+ *     NDArray_Inverse  at the top                                   return NPH_Inverse(target);
+ *     NDArray_LU       behind its shape checks and result arrays   NPH_LU(target, p, l, u), then its own rtns[]
+ *     NDArray_Solve    behind its device check, before its GPU throw  return NPH_Solve(a, b);
+ *
+ * each guarded by `#ifdef HAVE_NP_HIP` and NPH_LINALG_TAKES: CPU operands fall through to the reference's LAPACK code.
+ * The cuda_det_float / cuda_matrix_float_inverse stubs of hip_math.c are never reached in such a tree.
+ *
+ * Plain C over the reference's headers in a PHP build (results are the reference's own arrays and die in its
+ * NDArray_FREE), over include/numpower_host.h in libnumpower_host.so, whose NDArray_Det / Inverse / LU / Solve call
+ * these functions after making their operands contiguous.  Operands must be contiguous (the reference's arrays are).
+ * Errors: the reference's messages (linalg.c:123-125, 488-490, 577-588, 981-995); NULL / 0 after a raised error.
+ */
+#ifndef NUMPOWER_AMD_EXT_HIP_LINALG_H
+#define NUMPOWER_AMD_EXT_HIP_LINALG_H
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+struct NDArray;
+
+/* true when the early-out takes the call: the (first) operand lives on the GPU */
+#define NPH_LINALG_TAKES(a) (NDArray_DEVICE(a) == NDARRAY_DEVICE_GPU)
+
+/* a 0-d GPU array: the product of U's diagonal in index order, the pivot parity's sign, 0 when singular */
+struct NDArray *NPH_Det(struct NDArray *a);
+/* a^-1; a singular a raises "LU factorization failed. Unable to compute the matrix inverse.\n" */
+struct NDArray *NPH_Inverse(struct NDArray *a);
+/* p, l, u (n x n GPU arrays the caller allocated) := P, L, U with P a = L U; 1 on success, 0 after a raised error */
+int NPH_LU(struct NDArray *a, struct NDArray *p, struct NDArray *l, struct NDArray *u);
+/* x with a x = b, b n x k (any k); singular: the same throw as NPH_Inverse */
+struct NDArray *NPH_Solve(struct NDArray *a, struct NDArray *b);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -78,9 +78,11 @@ void cuda_float_multiply_matrix_vector(int nblocks, float *a_array, float *b_arr
 void cuda_calculate_outer_product(int m, int n, float *a_array, float *b_array, float *r_array);
 void cuda_float_transpose(int tiledim, int blockrows, const float *d_in, float *d_out, int width, int height);
 
-/* ---- dense factorizations: OUT OF SCOPE (linalg.c beyond matmul/dot/outer).  Present so
- * that an extension built --with-hip links and loads; each raises "... is not available on the HIP
- * back end" through np_ext_throw and returns failure / leaves its outputs untouched. ---- */
+/* ---- dense factorizations: stubs.  Present so that an extension built --with-hip links and loads; each
+ * raises "... is not available on the HIP back end" through np_ext_throw and returns failure / leaves its
+ * outputs untouched.  A tree patched by tools/apply_with_hip.py never calls the det / inverse / lu ones: the
+ * early-outs it inserts into NDArray_Det / Inverse / LU / Solve (linalg.c) send GPU operands to the device LU
+ * first (hip_linalg.h).  svd and lstsq have no device version: those two stay stubs. ---- */
 int cuda_svd_float(float *d_A, float *d_U, float *d_V, float *d_S, int m, int n);
 int cuda_det_float(float *a, float *result, int n);
 void cuda_matrix_float_inverse(float *matrix, int n);

@@ -377,6 +377,29 @@ int np_strided_copy(const float *in, float *out, int ndim, const int *host_shape
  * where NDArray_AssignArray copies element by element through the sliding view). */
 int np_copy2d(float *dst, size_t dst_pitch, const float *src, size_t src_pitch, size_t width, size_t rows);
 
+/* ---- dense LU factorization (np_linalg.hip; DESIGN.md "LU") ------------------------------------
+ * All matrices are n x n fp32 on the device; every call runs on the library stream and takes its
+ * scratch from the caching pool.  Results are bit-identical from run to run.
+ * np_getrf:   LAPACK sgetrf on the COLUMN-MAJOR a, in place: a = P^T L U, ipiv[n] = 0-based pivot rows
+ *             (device int32), *info (device int) = 1 + the first exactly-zero pivot, else 0.  A row-major
+ *             buffer is factored as its transpose, which is how the reference's LAPACK calls see it.
+ * np_getrs:   solves A X = B with np_getrf's factors; b is column-major n x nrhs, overwritten by X.
+ * np_det:     det of the buffer as LAPACK sees it (= det(a)): the diagonal of U multiplied in index order
+ *             in fp32, the pivot parity's sign; exactly 0.0f when info > 0.  *out_dev is device memory.
+ * np_inverse: out = a^-1 (row-major; getrf on the buffer as-is, getrs against I).  *info_host (host)
+ *             > 0: a is singular and out is left undefined.  Blocks until info is known.
+ * np_solve:   x (n x nrhs, row-major) with a x = b (b row-major n x nrhs).  *info_host as np_inverse.
+ * np_lu:      row-major p, l, u with p a = l u: partial pivoting by |value| on the rows of a, l unit-lower
+ *             with |l| <= 1, u upper, p a permutation matrix.
+ * n == 0 does nothing (np_det writes 1); null pointers are NP_ERR_INVALID; the blocked path takes
+ * n <= 65536. */
+int np_getrf(float *a, size_t n, int *ipiv, int *info);
+int np_getrs(const float *lu, const int *ipiv, size_t n, size_t nrhs, float *b);
+int np_det(const float *a, size_t n, float *out_dev);
+int np_inverse(const float *a, size_t n, float *out, int *info_host);
+int np_solve(const float *a, const float *b, size_t n, size_t nrhs, float *x, int *info_host);
+int np_lu(const float *a, size_t n, float *p, float *l, float *u);
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

@@ -156,6 +156,9 @@ NDArray *NDArray_ArangeOn(double start, double stop, double step, int device);
 int NDArray_ArrayEqual(NDArray *a, NDArray *b);
 int NDArray_AllClose(NDArray *a, NDArray *b, float rtol, float atol);
 NDArray *NDArray_ToContiguous(NDArray *a);
+/* `a` itself when it is C-contiguous, else a contiguous copy that is also stored in *owned (the caller frees it; *owned is
+ * NULL otherwise); NULL after a raised error.  The one contiguity rule of the host layer (host/numpower_linalg.cpp). */
+NDArray *numpower_host_contiguous(NDArray *a, NDArray **owned);
 NDArray *NDArray_Diagonal(NDArray *target, int offset);
 NDArray *NDArray_Trace(NDArray *a);
 NDArray *NDArray_Reshape(NDArray *target, int *new_shape, int ndim);
@@ -298,6 +301,20 @@ int NDArray_CommDestroy(void);
 int NDArray_CommRank(void);
 int NDArray_CommWorld(void);
 NDArray *NDArray_ShardedBatchedMatmul(NDArray *a_slab, NDArray *b_slab, int batch, int gather_mode);
+
+/* ---- dense linear algebra on the LU (host/numpower_linalg.cpp; linalg.c:253, 584, 620, 981) ----
+ * GPU operands only (the CPU path is the reference's own LAPACK calls).  Strided views are made contiguous
+ * (numpower_host_contiguous), then ext/hip_linalg.c does the work — the same code a --with-hip tree runs.
+ * NDArray_Det     0-d GPU array: the product of U's diagonal in index order, the pivot parity's sign, 0 when singular
+ * NDArray_Inverse a^-1; singular -> "LU factorization failed. Unable to compute the matrix inverse.\n"
+ * NDArray_LU      malloc'd vector {P, L, U} with P a = L U (the caller free()s the vector, the reference efree()s it)
+ * NDArray_Solve   x with a x = b, b n x k (any k); singular -> the same throw as NDArray_Inverse
+ * Shape errors: "Array must be at least two-dimensional", "Array must be square", "Incompatible shapes",
+ * "Both NDArray must be in the same device." (the reference's messages). */
+NDArray *NDArray_Det(NDArray *a);
+NDArray *NDArray_Inverse(NDArray *target);
+NDArray **NDArray_LU(NDArray *target);
+NDArray *NDArray_Solve(NDArray *a, NDArray *b);
 
 #ifdef __cplusplus
 }

@@ -128,6 +128,12 @@ PROTOTYPES = {
     "np_sgemv": (C.c_int, [C.c_size_t, C.c_size_t, _f32p, _f32p, _f32p]),
     "np_outer": (C.c_int, [_f32p, C.c_size_t, _f32p, C.c_size_t, _f32p]),
     "np_transpose2d": (C.c_int, [_f32p, _f32p, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "np_getrf": (C.c_int, [_f32p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "np_getrs": (C.c_int, [_f32p, C.c_void_p, C.c_size_t, C.c_size_t, _f32p]),
+    "np_det": (C.c_int, [_f32p, C.c_size_t, _f32p]),
+    "np_inverse": (C.c_int, [_f32p, C.c_size_t, _f32p, C.POINTER(C.c_int)]),
+    "np_solve": (C.c_int, [_f32p, _f32p, C.c_size_t, C.c_size_t, _f32p, C.POINTER(C.c_int)]),
+    "np_lu": (C.c_int, [_f32p, C.c_size_t, _f32p, _f32p, _f32p]),
     "np_permute": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "np_strided_copy": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "np_identity": (C.c_int, [_f32p, C.c_size_t]),

@@ -121,7 +121,8 @@ __device__ __forceinline__ void tile_coords(const GemmArgs &g, unsigned bid, uns
 
 // VEC : K % 4 == 0, N % 4 == 0, lda/ldb multiples of 4 and 16-byte aligned bases -> float4 loads
 // EDGE: tile may stick out of the matrix -> bounds-checked loads (zero fill) and stores
-template <int BM, int BN, int BK, int MINW, bool VEC, bool EDGE>
+// SUB : C = C - A.B (the LU's trailing updates, np::sgemm_sub_ld) instead of C = A.B
+template <int BM, int BN, int BK, int MINW, bool VEC, bool EDGE, bool SUB = false>
 __global__ __launch_bounds__(256, MINW) void sgemm_kernel(GemmArgs g) {
     if (g.K_last && blockIdx.z + 1 == gridDim.z) g.K = g.K_last;   // uniform: split-K remainder chunk
     constexpr int LDA_S = BK + 4;               // padded A row (floats)
@@ -265,7 +266,12 @@ __global__ __launch_bounds__(256, MINW) void sgemm_kernel(GemmArgs g) {
             for (int r = 0; r < 16; ++r) {
                 const unsigned row = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 const unsigned col = n0 + wn0 + j * 32 + li;
-                if (!EDGE || (row < g.M && col < g.N)) C[(size_t)row * g.ldc + col] = acc[i][j][r];
+                if (!EDGE || (row < g.M && col < g.N)) {
+                    if constexpr (SUB)
+                        C[(size_t)row * g.ldc + col] -= acc[i][j][r];
+                    else
+                        C[(size_t)row * g.ldc + col] = acc[i][j][r];
+                }
             }
     probe_end(g, probe_c0, probe_w0);
 }
@@ -3347,6 +3353,33 @@ int sgemm_batched_piece(size_t count, size_t whole, size_t M, size_t N, size_t K
     const int rc = np_sgemm_strided_batched(count, M, N, K, A, stride_a, B, stride_b, C, stride_c);
     g_plan_batch = 0;
     return rc;
+}
+
+// C (M x N, row stride ldc) -= A (M x K, row stride lda) . B (K x N, row stride ldb): one launch of the 128 x 128 tile kernel
+// with the subtracting epilogue, on the library stream.  Only the LU (np_linalg.hip) calls it; no np_sgemm* plan reaches it.
+int sgemm_sub_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, const float *B, size_t ldb, float *C, size_t ldc) {
+    if (M == 0 || N == 0 || K == 0) return NP_OK;
+    if (M > 0x7fffffffu || N > 0x7fffffffu || K > 0x7fffffffu || lda > 0x7fffffffu || ldb > 0x7fffffffu || ldc > 0x7fffffffu)
+        return np::fail(NP_ERR_INVALID, "sgemm_sub: dimension too large");
+    GemmArgs g = {};
+    g.A = A; g.B = B; g.C = C;
+    g.M = (unsigned)M; g.N = (unsigned)N; g.K = (unsigned)K;
+    g.lda = (unsigned)lda; g.ldb = (unsigned)ldb; g.ldc = (unsigned)ldc;
+    constexpr int BM = 128, BN = 128, BK = 16;
+    g.tiles_m = (g.M + BM - 1) / BM;
+    g.tiles_n = (g.N + BN - 1) / BN;
+    const bool vec = (K % 4 == 0) && (lda % 4 == 0) && (N % 4 == 0) && (ldb % 4 == 0) && aligned16(A) && aligned16(B);
+    const bool edge = (g.M % BM) || (g.N % BN) || (g.K % BK);
+    const dim3 grid(g.tiles_m * g.tiles_n, 1, 1);
+    hipStream_t s = np::stream();
+    if (vec && !edge)
+        sgemm_kernel<BM, BN, BK, 2, true, false, true><<<grid, 256, 0, s>>>(g);
+    else if (vec)
+        sgemm_kernel<BM, BN, BK, 2, true, true, true><<<grid, 256, 0, s>>>(g);
+    else
+        sgemm_kernel<BM, BN, BK, 2, false, true, true><<<grid, 256, 0, s>>>(g);
+    NP_LAUNCH_CHECK("sgemm_kernel (subtracting)");
+    return NP_OK;
 }
 
 }  // namespace np

@@ -540,6 +540,13 @@ NDArray *gather_to_new(const NDArray *like, const char *data, const int *shape, 
 
 }  // namespace
 
+NDArray *numpower_host_contiguous(NDArray *a, NDArray **owned) {
+    *owned = nullptr;
+    if (is_c_contiguous(a)) return a;
+    *owned = NDArray_ToContiguous(a);
+    return *owned;
+}
+
 int NDArray_ArrayEqual(NDArray *a, NDArray *b) {   // logic.c:703-716
     if (!a || !b) return 0;
     if (!same_shape(a, b)) return 0;

@@ -37,6 +37,11 @@ _LAZY_BINDING = _os.environ.get("NP_LAZY_BINDING") == "1"
 _LAZY_ARITH = ("add", "subtract", "multiply", "divide", "mod", "pow")
 
 
+_libc_free = C.CDLL(None).free
+_libc_free.argtypes = [C.c_void_p]
+_libc_free.restype = None
+
+
 class Error(RuntimeError):
     """PHP `Error` thrown by zend_throw_error in the reference."""
 
@@ -142,6 +147,10 @@ def _load_host():
     sig["NDArray_ToContiguous"] = (_P, [_P])
     sig["NDArray_Diagonal"] = (_P, [_P, C.c_int])
     sig["NDArray_Trace"] = (_P, [_P])
+    sig["NDArray_Det"] = (_P, [_P])
+    sig["NDArray_Inverse"] = (_P, [_P])
+    sig["NDArray_LU"] = (C.POINTER(_P), [_P])
+    sig["NDArray_Solve"] = (_P, [_P, _P])
     sig["NDArray_Reshape"] = (_P, [_P, ip, C.c_int])
     sig["NDArray_Flatten"] = (_P, [_P])
     sig["NDArray_ExpandDim"] = (_P, [_P, _P])
@@ -709,6 +718,36 @@ class NDArray:
         x, _ = NDArray._coerce(a)
         y, _ = NDArray._coerce(b)
         return NDArray._wrap(h.NDArray_Inner(x._p, y._p))
+
+    @staticmethod
+    def det(a):              # numpower.c:4598: a 0-d GPU array, RETURN_NDARRAY turns it into a float
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        return NDArray._wrap(h.NDArray_Det(x._p))
+
+    @staticmethod
+    def inv(a):              # numpower.c:4548
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        return NDArray._wrap(h.NDArray_Inverse(x._p))
+
+    @staticmethod
+    def solve(a, b):         # numpower.c:4145
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        y, _ = NDArray._coerce(b)
+        return NDArray._wrap(h.NDArray_Solve(x._p, y._p))
+
+    @staticmethod
+    def lu(a):               # numpower.c:4231-4253: RETURN_3NDARRAY -> (P, L, U)
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        rtns = h.NDArray_LU(x._p)
+        if not rtns:
+            _raise_pending(h)
+        out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(3))
+        _libc_free(C.cast(rtns, C.c_void_p))   # the vector itself (the reference efree()s it)
+        return out
 
     def copy(self):          # PHP_METHOD copy: NDArray_Copy on the array's own device
         return NDArray._wrap(_load_host().NDArray_Copy(self._p, C.cast(self._p, _P).contents.device))

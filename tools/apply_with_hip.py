@@ -454,6 +454,57 @@ EDITS = [
 ]
 
 # What each compiled snippet needs from the reference function around it (names and types as in the reference).
+# ---- section 2b, linear algebra: det / inv / lu / solve of GPU arrays on the device LU (ext/hip_linalg.h) ----
+_LINALG_NOTE = ("/* numpower_amd 2b: a GPU operand is factored on the device (np_det / np_inverse / np_lu / np_solve, ext/hip_linalg.c);\n"
+                " * CPU operands fall through to the reference's LAPACK code below, untouched */\n")
+LINALG_EDITS = [
+    Edit("src/ndmath/linalg.c", "linalg.c:12: <hip_linalg.h>",
+         r"^(?P<old>#include \"\.\./indexing\.h\")$",
+         "#include <hip_linalg.h>", after=True),
+    Edit("src/ndmath/linalg.c", "linalg.c:254 NDArray_Det: GPU early-out",
+         r"^(?P<old>NDArray_Det\(NDArray \*a\) \{)$",
+         "    " + _LINALG_NOTE.replace("\n *", "\n     *") +
+         "    if (NPH_LINALG_TAKES(a)) {\n"
+         "        return NPH_Det(a);\n"
+         "    }", after=True),   # behind the function's opening line: indented by hand
+    Edit("src/ndmath/linalg.c", "linalg.c:575 NDArray_Inverse: GPU early-out",
+         r"^(?P<old>NDArray_Inverse\(NDArray\* target\) \{)$",
+         "    " + _LINALG_NOTE.replace("\n *", "\n     *") +
+         "    if (NPH_LINALG_TAKES(target)) {\n"
+         "        return NPH_Inverse(target);\n"
+         "    }", after=True),   # behind the function's opening line: indented by hand
+    # behind the reference's shape checks and its three result arrays (NDArray_Empty on the operand's device), so that the
+    # vector and the arrays are the reference's own; the copy it made for LAPACK is not needed on the device
+    Edit("src/ndmath/linalg.c", "linalg.c:634 NDArray_LU: GPU early-out",
+         r"^(?P<old>[ \t]*NDArray \*u = NDArray_Empty\(new_shape_u, NDArray_NDIM\(target\), NDARRAY_TYPE_FLOAT32, NDArray_DEVICE\(target\)\);)$",
+         _LINALG_NOTE +
+         "if (NPH_LINALG_TAKES(target)) {\n"
+         "    NDArray_FREE(copied);\n"
+         "    if (!NPH_LU(target, p, l, u)) {\n"
+         "        NDArray_FREE(p);\n"
+         "        NDArray_FREE(l);\n"
+         "        NDArray_FREE(u);\n"
+         "        return NULL;\n"
+         "    }\n"
+         "    rtns[0] = p;\n"
+         "    rtns[1] = l;\n"
+         "    rtns[2] = u;\n"
+         "    return rtns;\n"
+         "}", after=True),
+    # behind the reference's device check, before its "ndarray::solve not implemented for GPU" throw
+    Edit("src/ndmath/linalg.c", "linalg.c:982-985 NDArray_Solve: GPU early-out",
+         r"^(?P<old>[ \t]*if \(NDArray_DEVICE\(a\) != NDArray_DEVICE\(b\)\) \{\n"
+         r"[ \t]*zend_throw_error\(NULL, \"Both NDArray must be in the same device\.\"\);\n"
+         r"[ \t]*return NULL;\n"
+         r"[ \t]*\})(?=\n[ \t]*if \(NDArray_DEVICE\(a\) == NDARRAY_DEVICE_GPU\) \{\n"
+         r"[ \t]*zend_throw_error\(NULL, \"ndarray::solve not implemented for GPU\"\);)",
+         _LINALG_NOTE +
+         "if (NPH_LINALG_TAKES(a)) {\n"
+         "    return NPH_Solve(a, b);\n"
+         "}", after=True),
+]
+EDITS += LINALG_EDITS
+
 CONTEXTS = {
     "ndarray.c:1055-1060 NDArray_ToGPU: H2D copy": "float *tmp_gpu = 0; NDArray *target = 0;",
     "ndarray.c:1090 NDArray_ToCPU: D2H copy": "NDArray *rtn = 0, *target = 0;",
@@ -501,8 +552,14 @@ for _e in EDITS:
     if "`rtn = NDArray_" in _e.what:
         CONTEXTS[_e.what] = "NDArray *rtn = 0, *nda = 0, *ndb = 0;"
 for _e in EDITS:
-    if _e.what.endswith("GPU early-out"):
+    if _e.what.endswith("GPU early-out") and _e not in LINALG_EDITS:
         CONTEXTS[_e.what] = "NDArray *nda = 0, *ndb = 0;" if _e.file == "src/logic.c" else "NDArray *a = 0, *b = 0;"
+CONTEXTS.update({
+    "linalg.c:254 NDArray_Det: GPU early-out": "NDArray *a = 0;",
+    "linalg.c:575 NDArray_Inverse: GPU early-out": "NDArray *target = 0;",
+    "linalg.c:634 NDArray_LU: GPU early-out": "NDArray *target = 0, *copied = 0, *p = 0, *l = 0, *u = 0; NDArray **rtns = 0;",
+    "linalg.c:982-985 NDArray_Solve: GPU early-out": "NDArray *a = 0, *b = 0;",
+})
 
 HIP_M4_BLOCK = '''dnl ---- MI355X (gfx950) through numpower_amd: added by numpower_amd/tools/apply_with_hip.py ----
 dnl No device compiler step: the kernels live in a prebuilt libnp_hip.so, everything compiled here is plain C
@@ -533,11 +590,11 @@ if test "$PHP_HIP" != "no"; then
   AC_DEFINE([HAVE_CUBLAS], [1], [a device back end is present (the C files gate every GPU branch on this name)])
   AC_DEFINE([HAVE_NP_HIP], [1], [the device back end is numpower_amd / MI355X])
   CFLAGS+=" -DNUMPOWER_NDARRAY_HEADER='\\"src/initializers.h\\"' -DNP_GPU_ALLOC_WIDE=1 "
-  NP_GPU_ALLOC_SOURCES="src/hip/gpu_alloc_hip.c src/hip/hip_math.c src/hip/hip_math_drivers.c src/hip/hip_fast.c src/hip/hip_lazy.c src/hip/zend_hooks.c"
+  NP_GPU_ALLOC_SOURCES="src/hip/gpu_alloc_hip.c src/hip/hip_math.c src/hip/hip_math_drivers.c src/hip/hip_fast.c src/hip/hip_lazy.c src/hip/hip_linalg.c src/hip/zend_hooks.c"
 fi'''
 
 GLUE_FILES = ["ext/gpu_alloc_hip.c", "ext/hip_math.c", "ext/hip_math.h", "ext/hip_math_drivers.c", "ext/hip_fast.c",
-              "ext/hip_fast.h", "ext/hip_lazy.c", "ext/hip_lazy.h", "ext/zend_hooks.c", "ext/np_ext_hooks.h", "include/np_hip.h"]
+              "ext/hip_fast.h", "ext/hip_lazy.c", "ext/hip_lazy.h", "ext/hip_linalg.c", "ext/hip_linalg.h", "ext/zend_hooks.c", "ext/np_ext_hooks.h", "include/np_hip.h"]
 # not compiled in a --with-hip build: replaced wholesale by the glue
 REPLACED_BY_GLUE = ("src/gpu_alloc.c", "src/ndmath/cuda/")
 
@@ -555,7 +612,7 @@ def snippet_check_source() -> str:
     PHP build.  The only foreign declarations are the three reference symbols the new text itself calls."""
     out = ["/* generated by tools/apply_with_hip.py: snippet_check_source() */",
            "#include <stdio.h>", "#include <stddef.h>",
-           '#include "np_hip.h"', '#include "numpower_host.h"', '#include "hip_math.h"', '#include "hip_fast.h"', '#include "hip_lazy.h"',
+           '#include "np_hip.h"', '#include "numpower_host.h"', '#include "hip_math.h"', '#include "hip_fast.h"', '#include "hip_lazy.h"', '#include "hip_linalg.h"',
            "void zend_throw_error(void *exception_ce, const char *format, ...);   /* Zend/zend_exceptions.h */",
            "typedef struct _zval_struct zval;                                        /* Zend/zend_types.h */",
            "NDArray *ZVAL_TO_NDARRAY(zval *obj);                                     /* numpower.c:89 */",
@@ -584,7 +641,7 @@ def snippet_check_source() -> str:
     return "\n".join(out)
 
 
-FAST_BINARY = [(e.what.split(" ")[1].rstrip(":"), e) for e in EDITS if e.what.endswith("GPU early-out")]   # ("NDArray_Add_Float", edit)
+FAST_BINARY = [(e.what.split(" ")[1].rstrip(":"), e) for e in EDITS if e.what.endswith("GPU early-out") and e not in LINALG_EDITS]   # ("NDArray_Add_Float", edit)
 
 
 def fast_path_program_source() -> str:
@@ -635,6 +692,114 @@ def fast_path_program_source() -> str:
     table = ",\n".join('    {"%s", patched_%s}' % (name[len("NDArray_"):], name) for name, _ in FAST_BINARY)
     o.append(_FAST_PROGRAM_MAIN.replace("@TABLE@", table))
     return "\n".join(o)
+
+
+def linalg_program_source() -> str:
+    """A C99 PROGRAM around the text section 2b inserts into linalg.c (LINALG_EDITS): each of NDArray_Det / Inverse / LU /
+    Solve with the reference's signature, the inserted text VERBATIM, then a stand-in for the reference's LAPACK code that
+    only counts how often it is reached (for LU: the reference's own preamble first — the copy, the three result arrays and
+    the vector).  Built against include/numpower_host.h + ext/hip_linalg.h, linked with libnumpower_host.so (which carries
+    ext/hip_linalg.c), -Wall -Wextra -Werror.  Its own program, not fast_path_bodies.
+
+        linalg_bodies cpu    CPU operands: all four calls fall through to the stand-in, no device is touched
+        linalg_bodies gpu    GPU operands: none falls through; the results are checked against known answers, a singular
+                             matrix raises the reference's message, and no device allocation leaks
+    """
+    e = {x.what.split(" ")[1].rstrip(":"): x for x in LINALG_EDITS if x.what.endswith("GPU early-out")}
+    o = ["/* generated by tools/apply_with_hip.py: linalg_program_source() — do not edit */",
+         "#include <stdio.h>", "#include <stdlib.h>", "#include <string.h>", "",
+         "#define HAVE_NP_HIP 1", '#include "numpower_host.h"', '#include "hip_linalg.h"', "",
+         "static int g_fell_through;   /* calls that reached the reference's own code (the stand-ins below) */",
+         "static NDArray *reference_body(void) { g_fell_through++; return NULL; }", "",
+         "static NDArray *patched_NDArray_Det(NDArray *a) {", "#ifdef HAVE_NP_HIP", _indent(e["NDArray_Det"].new, ""), "#endif",
+         "    return reference_body();", "}", "",
+         "static NDArray *patched_NDArray_Inverse(NDArray *target) {", "#ifdef HAVE_NP_HIP", _indent(e["NDArray_Inverse"].new, ""),
+         "#endif", "    return reference_body();", "}", "",
+         "static NDArray **patched_NDArray_LU(NDArray *target) {",
+         "    /* the reference's preamble (linalg.c:615-634): shape checks, the vector, a copy, three arrays on the device */",
+         "    if (NDArray_NDIM(target) != 2 || NDArray_SHAPE(target)[0] != NDArray_SHAPE(target)[1]) return NULL;",
+         "    NDArray **rtns = malloc(sizeof(NDArray *) * 3);",
+         "    NDArray *copied = NDArray_Copy(target, NDArray_DEVICE(target));",
+         "    NDArray *p = NDArray_EmptyLike(target);", "    NDArray *l = NDArray_EmptyLike(target);",
+         "    NDArray *u = NDArray_EmptyLike(target);",
+         "#ifdef HAVE_NP_HIP", _indent(e["NDArray_LU"].new, "    "), "#endif",
+         "    NDArray_FREE(copied);", "    NDArray_FREE(p);", "    NDArray_FREE(l);", "    NDArray_FREE(u);", "    free(rtns);",
+         "    reference_body();", "    return NULL;", "}", "",
+         "static NDArray *patched_NDArray_Solve(NDArray *a, NDArray *b) {",
+         "    if (NDArray_DEVICE(a) != NDArray_DEVICE(b)) return NULL;   /* the reference's device check (linalg.c:982-985) */",
+         "#ifdef HAVE_NP_HIP", _indent(e["NDArray_Solve"].new, "    "), "#endif", "    return reference_body();", "}", ""]
+    o.append(_LINALG_PROGRAM_MAIN)
+    return "\n".join(o)
+
+
+_LINALG_PROGRAM_MAIN = r"""static int g_failures;
+#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "linalg_bodies: " __VA_ARGS__); fprintf(stderr, "\n"); g_failures++; } } while (0)
+
+static NDArray *make(const float *v, int rows, int cols, int gpu) {
+    int shape[2] = {rows, cols};
+    NDArray *h = NDArray_FromHostBuffer(v, shape, 2);
+    if (!gpu) return h;
+    NDArray *d = NDArray_ToGPU(h);
+    NDArray_FREE(h);
+    return d;
+}
+
+static int values(NDArray *a, float *out) {
+    NDArray *h = NDArray_ToCPU(a);
+    const int rc = h ? NDArray_CopyToHostBuffer(h, out) : -1;
+    if (h) NDArray_FREE(h);
+    return rc;
+}
+
+int main(int argc, char **argv) {
+    if (argc < 2 || (strcmp(argv[1], "cpu") && strcmp(argv[1], "gpu"))) {
+        fprintf(stderr, "usage: linalg_bodies cpu|gpu\n");
+        return 2;
+    }
+    const int gpu = strcmp(argv[1], "gpu") == 0;
+    const float a2[4] = {1, 2, 3, 4}, b2[2] = {5, 6};
+    const float a3[9] = {1, 1, 1, 2, 3, 5, 4, 6, 8};
+    const float sing[4] = {1, 0, 2, 0};
+    const long live0 = gpu ? NDArray_LiveDeviceAllocations() : 0;
+    NDArray *a = make(a2, 2, 2, gpu), *b = make(b2, 2, 1, gpu), *m3 = make(a3, 3, 3, gpu), *s = make(sing, 2, 2, gpu);
+    NDArray *det = patched_NDArray_Det(a);
+    NDArray *inv = patched_NDArray_Inverse(a);
+    NDArray **lu = patched_NDArray_LU(m3);
+    NDArray *x = patched_NDArray_Solve(a, b);
+    if (!gpu) {
+        CHECK(!det && !inv && !lu && !x, "a CPU operand was computed on the device");
+        CHECK(g_fell_through == 4, "%d of 4 calls reached the reference's code", g_fell_through);
+    } else {
+        CHECK(g_fell_through == 0, "%d GPU calls fell through to the reference's code", g_fell_through);
+        float v[9];
+        CHECK(det && NDArray_GetFloatScalar(det) == -2.0f, "det([[1,2],[3,4]]) != -2");
+        CHECK(inv && values(inv, v) == 0 && v[0] == -2.0f && v[1] == 1.0f && v[2] == 1.5f && v[3] == -0.5f,
+              "inv([[1,2],[3,4]]) != [[-2,1],[1.5,-0.5]]");
+        CHECK(x && values(x, v) == 0 && v[0] > -4.00001f && v[0] < -3.99999f && v[1] > 4.49999f && v[1] < 4.50001f,
+              "solve([[1,2],[3,4]], [5,6]) != [-4, 4.5]");
+        const float P[9] = {0, 0, 1, 1, 0, 0, 0, 1, 0}, L[9] = {1, 0, 0, 0.25f, 1, 0, 0.5f, 0, 1}, U[9] = {4, 6, 8, 0, -0.5f, -1, 0, 0, 1};
+        const float *want[3] = {P, L, U};
+        for (int k = 0; k < 3; ++k) {
+            int ok = lu && values(lu[k], v) == 0;
+            for (int i = 0; ok && i < 9; ++i) ok = v[i] == want[k][i];
+            CHECK(ok, "lu factor %d differs from the known answer", k);
+        }
+        CHECK(patched_NDArray_Inverse(s) == NULL &&
+              strcmp(numpower_host_last_error(), "LU factorization failed. Unable to compute the matrix inverse.\n") == 0,
+              "a singular inverse did not raise the reference's message");
+        NDArray *ds = patched_NDArray_Det(s);
+        CHECK(ds && NDArray_GetFloatScalar(ds) == 0.0f, "det of a singular matrix is not 0");
+        if (ds) NDArray_FREE(ds);
+    }
+    NDArray *all[] = {det, inv, x, a, b, m3, s, lu ? lu[0] : NULL, lu ? lu[1] : NULL, lu ? lu[2] : NULL};
+    for (size_t i = 0; i < sizeof(all) / sizeof(all[0]); ++i)
+        if (all[i]) NDArray_FREE(all[i]);
+    free(lu);
+    if (gpu) CHECK(NDArray_LiveDeviceAllocations() == live0, "%ld device allocations leaked", NDArray_LiveDeviceAllocations() - live0);
+    printf("linalg_bodies %s: %d calls reached the reference's own code, %d failures\n", argv[1], g_fell_through, g_failures);
+    return g_failures ? 1 : 0;
+}
+"""
 
 
 _FAST_PROGRAM_MAIN = r'''typedef NDArray *(*Binary)(NDArray *, NDArray *);

@@ -1,0 +1,97 @@
+"""Timing of the device LU (np_linalg.hip): getrf, inverse and solve (one right-hand side) over n, after a GEMM warm-up
+that covers the clock ramp.  getrf is timed together with the copy that restores its input (2 n^2 floats, included).
+Prints ms per call, TFLOP/s (2/3 n^3 for getrf, 2 n^3 for the inverse, 2/3 n^3 + 2 n^2 for solve), kernel launches per
+call, and numpy's fp32 solve on the host for comparison (the median of a few calls after a warm-up call).  The share of the trailing GEMMs comes from a run under
+`rocprofv3 --kernel-trace --stats` (profiles/linalg/).  Usage: python tools/linalg_sweep.py [--sizes 64,256,...] [--reps N]"""
+import argparse
+import ctypes as C
+import sys
+import time
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+import numpy as np
+from numpower_amd import device as D
+from numpower_amd._lib import Timer, check, load
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--sizes", default="64,256,1024,4096,8192,16384")
+ap.add_argument("--reps", type=int, default=0, help="0: as many as fit ~0.5 s per size (at least 3)")
+ap.add_argument("--no-host", action="store_true", help="skip numpy's solve on the host")
+args = ap.parse_args()
+
+D.init(0)
+lib = load()
+t = Timer()
+
+
+def launches():
+    c = C.c_ulonglong()
+    check(lib.np_debug_launch_count(C.byref(c)))
+    return c.value
+
+
+def timed(fn, reps):
+    fn()
+    D.sync()
+    l0 = launches()
+    fn()
+    D.sync()
+    per_call = launches() - l0
+    t.start()
+    for _ in range(reps):
+        fn()
+    t.stop()
+    return t.elapsed_ms() / reps, per_call
+
+
+# clock ramp: ~1 s of 4096^3 GEMMs
+ga = D.DeviceArray.from_host(np.random.default_rng(0).standard_normal((4096, 4096)).astype(np.float32))
+gc = D.DeviceArray((4096, 4096))
+t0 = time.time()
+while time.time() - t0 < 1.0:
+    for _ in range(10):
+        check(lib.np_sgemm(4096, 4096, 4096, ga.ptr, ga.ptr, gc.ptr))
+    D.sync()
+ga.free()
+gc.free()
+
+print("%6s %-8s %10s %9s %9s   %s" % ("n", "op", "ms", "TFLOP/s", "launches", "host numpy fp32 solve"), flush=True)
+for n in [int(s) for s in args.sizes.split(",")]:
+    rng = np.random.default_rng(n)
+    a = rng.standard_normal((n, n)).astype(np.float32)
+    b = rng.standard_normal((n, 1)).astype(np.float32)
+    da, db = D.DeviceArray.from_host(a), D.DeviceArray.from_host(b)
+    work, out = D.DeviceArray((n, n)), D.DeviceArray((n, n))
+    piv, info = D.DeviceArray((n,)), D.DeviceArray((1,))
+    ih = C.c_int()
+
+    def getrf():
+        check(lib.np_memcpy_d2d(work.ptr, da.ptr, 4 * n * n))
+        check(lib.np_getrf(work.ptr, n, piv.ptr, info.ptr))
+
+    def inverse():
+        check(lib.np_inverse(da.ptr, n, out.ptr, C.byref(ih)))
+
+    def solve():
+        check(lib.np_solve(da.ptr, db.ptr, n, 1, out.ptr, C.byref(ih)))
+
+    for name, fn, flops in (("getrf", getrf, 2 / 3 * n ** 3), ("inv", inverse, 2 * n ** 3),
+                            ("solve", solve, 2 / 3 * n ** 3 + 2 * n * n)):
+        t0 = time.time()
+        fn()
+        D.sync()
+        one = max(time.time() - t0, 1e-5)
+        reps = args.reps or max(3, min(200, int(0.5 / one)))
+        ms, per_call = timed(fn, reps)
+        host = ""
+        if name == "solve" and not args.no_host and n <= 8192:
+            np.linalg.solve(a, b)                  # warm-up: the first call pays for thread start-up
+            ts = []
+            for _ in range(5 if n <= 4096 else 3):
+                h0 = time.perf_counter()
+                np.linalg.solve(a, b)
+                ts.append((time.perf_counter() - h0) * 1e3)
+            host = "%.3f ms (median of %d after a warm-up)" % (float(np.median(ts)), len(ts))
+        print("%6d %-8s %10.3f %9.2f %9d   %s" % (n, name, ms, flops / ms / 1e9, per_call, host), flush=True)
+    for x in (da, db, work, out, piv, info):
+        x.free()
