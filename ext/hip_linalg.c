@@ -1,5 +1,5 @@
 /*
- * hip_linalg.c — the device side of NDArray_Det / Inverse / LU / Solve (hip_linalg.h).  Compiled into a --with-hip tree
+ * hip_linalg.c — the device side of NDArray_Det / Inverse / LU / Solve / Cholesky (hip_linalg.h).  Compiled into a --with-hip tree
  * against the reference's headers (-DNUMPOWER_NDARRAY_HEADER='"src/initializers.h"') and into libnumpower_host.so
  * against include/numpower_host.h; it uses only what both declare.
  */
@@ -102,6 +102,29 @@ NDArray *NPH_Solve(NDArray *a, NDArray *b) {
     if (info > 0) {
         np_ext_throw(kSingular);
         NDArray_FREE(rtn);
+        return NULL;
+    }
+    return rtn;
+}
+
+NDArray *NPH_Cholesky(NDArray *a) {
+    if (a == NULL) return NULL;
+    if (NDArray_NDIM(a) != 2 || NDArray_SHAPE(a)[0] != NDArray_SHAPE(a)[1]) {   /* linalg.c:1062-1065 */
+        np_ext_throw("NDArray" "_Cholesky: $a must be a square matrix.");   /* split: this file names only functions it may call */
+        return NULL;
+    }
+    if (!on_gpu(a)) return NULL;
+    NDArray *rtn = NDArray_EmptyLike(a);
+    if (rtn == NULL) return NULL;
+    int info = 0;
+    if (np_cholesky(NDArray_FDATA(a), (size_t) NDArray_SHAPE(a)[0], NDArray_FDATA(rtn), &info) != NP_OK) {
+        np_ext_throw_last();
+        NDArray_FREE(rtn);
+        return NULL;
+    }
+    if (info > 0) {                                                              /* linalg.c:1070-1074 */
+        NDArray_FREE(rtn);
+        np_ext_throw("Error calculating the cholesky decomposition. (Is $a not positive definite?)");
         return NULL;
     }
     return rtn;

@@ -1,5 +1,6 @@
 /*
- * hip_linalg.h — det / inv / lu / solve of GPU arrays on the device LU (np_getrf / np_getrs of include/np_hip.h).
+ * hip_linalg.h — det / inv / lu / solve of GPU arrays on the device LU (np_getrf / np_getrs of include/np_hip.h), and
+ * cholesky on the device Cholesky factorization (np_cholesky).
  *
  * The reference computes these with LAPACK on the CPU and, under --with-cuda, through cuSOLVER / its own kernel
  * (cuda_math.cu); its NDArray_Solve refuses GPU arrays.  tools/apply_with_hip.py inserts an early-out into each of the
@@ -10,13 +11,18 @@
  *     NDArray_LU       behind its shape checks and result arrays   NPH_LU(target, p, l, u), then its own rtns[]
  *     NDArray_Solve    behind its device check, before its GPU throw  return NPH_Solve(a, b);
  *
+ *
+ * and one into NDArray_Cholesky, which the reference leaves "@todo Implement GPU":
+ *
+ *     NDArray_Cholesky at the top, before its GPU throw             return NPH_Cholesky(a);
+ *
  * each guarded by `#ifdef HAVE_NP_HIP` and NPH_LINALG_TAKES: CPU operands fall through to the reference's LAPACK code.
  * The cuda_det_float / cuda_matrix_float_inverse stubs of hip_math.c are never reached in such a tree.
  *
  * Plain C over the reference's headers in a PHP build (results are the reference's own arrays and die in its
  * NDArray_FREE), over include/numpower_host.h in libnumpower_host.so, whose NDArray_Det / Inverse / LU / Solve call
  * these functions after making their operands contiguous.  Operands must be contiguous (the reference's arrays are).
- * Errors: the reference's messages (linalg.c:123-125, 488-490, 577-588, 981-995); NULL / 0 after a raised error.
+ * Errors: the reference's messages (linalg.c:123-125, 488-490, 577-588, 981-995, 1063, 1072); NULL / 0 after a raised error.
  */
 #ifndef NUMPOWER_AMD_EXT_HIP_LINALG_H
 #define NUMPOWER_AMD_EXT_HIP_LINALG_H
@@ -38,6 +44,10 @@ struct NDArray *NPH_Inverse(struct NDArray *a);
 int NPH_LU(struct NDArray *a, struct NDArray *p, struct NDArray *l, struct NDArray *u);
 /* x with a x = b, b n x k (any k); singular: the same throw as NPH_Inverse */
 struct NDArray *NPH_Solve(struct NDArray *a, struct NDArray *b);
+/* the lower-triangular L with a = L L^T (upper triangle +0.0f), from a's lower triangle alone; not square:
+ * "NDArray_Cholesky: $a must be a square matrix."; a pivot that is not positive:
+ * "Error calculating the cholesky decomposition. (Is $a not positive definite?)" */
+struct NDArray *NPH_Cholesky(struct NDArray *a);
 
 #ifdef __cplusplus
 }

@@ -400,6 +400,20 @@ int np_inverse(const float *a, size_t n, float *out, int *info_host);
 int np_solve(const float *a, const float *b, size_t n, size_t nrhs, float *x, int *info_host);
 int np_lu(const float *a, size_t n, float *p, float *l, float *u);
 
+/* ---- dense Cholesky factorization (np_linalg.hip; DESIGN.md "Cholesky") --------------------------
+ * a = L L^T for a symmetric positive definite n x n fp32 matrix, ROW-MAJOR, with LAPACK's spotrf('L')
+ * semantics: only the lower triangle of a (diagonal included) is read, whatever the strict upper triangle
+ * holds.  info = 1 + the first column whose pivot a_jj - sum_k l_jk^2 is not greater than zero (or is NaN),
+ * else 0; what the factor holds from that column on is unspecified.  Library stream, pool scratch,
+ * bit-identical from run to run.
+ * np_potrf:    in place: the lower triangle of a becomes L, the strict upper triangle of a is left exactly
+ *              as it was; *info is a device int.
+ * np_cholesky: out = L with the strict upper triangle +0.0f, a untouched (out must not overlap a);
+ *              *info_host (host).  Blocks until info is known.
+ * n == 0 does nothing and reports info = 0; null pointers are NP_ERR_INVALID; n <= 65536. */
+int np_potrf(float *a, size_t n, int *info);
+int np_cholesky(const float *a, size_t n, float *out, int *info_host);
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

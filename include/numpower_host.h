@@ -316,6 +316,14 @@ NDArray *NDArray_Inverse(NDArray *target);
 NDArray **NDArray_LU(NDArray *target);
 NDArray *NDArray_Solve(NDArray *a, NDArray *b);
 
+/* ---- Cholesky factorization (host/numpower_linalg.cpp; linalg.c:1056-1102) ----
+ * NDArray_Cholesky  the lower-triangular L with a = L L^T, strict upper triangle +0.0f; only the lower triangle of a
+ *                   is read (the reference: LAPACKE_spotrf(ROW_MAJOR, 'L') on a copy).  GPU operands only, views made
+ *                   contiguous; ext/hip_linalg.c (NPH_Cholesky) does the work.
+ * Errors: "NDArray_Cholesky: $a must be a square matrix." for a non-square or non-2-D operand,
+ * "Error calculating the cholesky decomposition. (Is $a not positive definite?)" when a pivot is not positive. */
+NDArray *NDArray_Cholesky(NDArray *a);
+
 #ifdef __cplusplus
 }
 #endif

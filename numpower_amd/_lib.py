@@ -134,6 +134,8 @@ PROTOTYPES = {
     "np_inverse": (C.c_int, [_f32p, C.c_size_t, _f32p, C.POINTER(C.c_int)]),
     "np_solve": (C.c_int, [_f32p, _f32p, C.c_size_t, C.c_size_t, _f32p, C.POINTER(C.c_int)]),
     "np_lu": (C.c_int, [_f32p, C.c_size_t, _f32p, _f32p, _f32p]),
+    "np_potrf": (C.c_int, [_f32p, C.c_size_t, C.c_void_p]),
+    "np_cholesky": (C.c_int, [_f32p, C.c_size_t, _f32p, C.POINTER(C.c_int)]),
     "np_permute": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "np_strided_copy": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "np_identity": (C.c_int, [_f32p, C.c_size_t]),

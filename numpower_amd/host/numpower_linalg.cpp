@@ -1,5 +1,6 @@
-// NDArray_Det / NDArray_Inverse / NDArray_LU / NDArray_Solve (linalg.c:253, 584, 620, 981) on the device LU.
-// The work — argument checks, the reference's messages, the np_det / np_inverse / np_lu / np_solve calls — is
+// NDArray_Det / NDArray_Inverse / NDArray_LU / NDArray_Solve (linalg.c:253, 584, 620, 981) on the device LU, and
+// NDArray_Cholesky (linalg.c:1056) on the device Cholesky factorization.
+// The work — argument checks, the reference's messages, the np_det / np_inverse / np_lu / np_solve / np_cholesky calls — is
 // ext/hip_linalg.c, the same code a --with-hip tree reaches through the early-outs tools/apply_with_hip.py inserts into
 // the reference's functions; here strided views are first made contiguous (numpower_host_contiguous).
 // A translation unit of its own: the sanitizer build of numpower_host.cpp (tests/test_host_sanitizers_cpu.py) links
@@ -10,6 +11,7 @@
 //   inverse  getrf on the buffer as-is, getrs against I: (a^T)^-1 column-major, which read row-major is a^-1
 //   solve    a itself is factored (a transposed copy in column-major), so x solves a x = b for any number of columns
 //   lu       the same factorization of a: P a = L U with partial pivoting on the rows of a
+//   cholesky row-major as it is: only the lower triangle of a is read
 #include <stdlib.h>
 
 #include "hip_linalg.h"
@@ -72,6 +74,12 @@ NDArray *NDArray_Solve(NDArray *a, NDArray *b) {   // linalg.c:981-1030
     if (!ca.arr) return nullptr;
     Operand cb(b);
     return cb.arr ? NPH_Solve(ca.arr, cb.arr) : nullptr;
+}
+
+NDArray *NDArray_Cholesky(NDArray *a) {   // linalg.c:1056-1102
+    if (!a) return nullptr;
+    Operand ca(a);
+    return ca.arr ? NPH_Cholesky(ca.arr) : nullptr;
 }
 
 }  // extern "C"

@@ -151,6 +151,7 @@ def _load_host():
     sig["NDArray_Inverse"] = (_P, [_P])
     sig["NDArray_LU"] = (C.POINTER(_P), [_P])
     sig["NDArray_Solve"] = (_P, [_P, _P])
+    sig["NDArray_Cholesky"] = (_P, [_P])
     sig["NDArray_Reshape"] = (_P, [_P, ip, C.c_int])
     sig["NDArray_Flatten"] = (_P, [_P])
     sig["NDArray_ExpandDim"] = (_P, [_P, _P])
@@ -748,6 +749,12 @@ class NDArray:
         out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(3))
         _libc_free(C.cast(rtns, C.c_void_p))   # the vector itself (the reference efree()s it)
         return out
+
+    @staticmethod
+    def cholesky(a):         # numpower.c:4119: lower-triangular L with a = L L^T, from a's lower triangle alone
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        return NDArray._wrap(h.NDArray_Cholesky(x._p))
 
     def copy(self):          # PHP_METHOD copy: NDArray_Copy on the array's own device
         return NDArray._wrap(_load_host().NDArray_Copy(self._p, C.cast(self._p, _P).contents.device))

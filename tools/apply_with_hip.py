@@ -505,6 +505,20 @@ LINALG_EDITS = [
 ]
 EDITS += LINALG_EDITS
 
+# ---- section 2b, Cholesky: the reference's NDArray_Cholesky refuses GPU arrays ("@todo Implement GPU"); the early-out sits
+# in front of that throw and replaces nothing.  A list of its own: its text runs as a program of its own (cholesky_bodies) ----
+CHOLESKY_EDITS = [
+    Edit("src/ndmath/linalg.c", "linalg.c:1057 NDArray_Cholesky: GPU early-out",
+         r"^(?P<old>NDArray_Cholesky\(NDArray \*a\) \{)(?=\n[ \t]*if \(NDArray_DEVICE\(a\) == NDARRAY_DEVICE_GPU\) \{\n"
+         r"[ \t]*zend_throw_error\(NULL, \"ndarray::cholesky not implemented for GPU\"\);)",
+         "    /* numpower_amd 2b: a GPU operand is factored on the device (np_cholesky, ext/hip_linalg.c); CPU operands fall\n"
+         "     * through to the reference's LAPACK code below, untouched */\n"
+         "    if (NPH_LINALG_TAKES(a)) {\n"
+         "        return NPH_Cholesky(a);\n"
+         "    }", after=True),   # behind the function's opening line: indented by hand
+]
+EDITS += CHOLESKY_EDITS
+
 CONTEXTS = {
     "ndarray.c:1055-1060 NDArray_ToGPU: H2D copy": "float *tmp_gpu = 0; NDArray *target = 0;",
     "ndarray.c:1090 NDArray_ToCPU: D2H copy": "NDArray *rtn = 0, *target = 0;",
@@ -552,13 +566,14 @@ for _e in EDITS:
     if "`rtn = NDArray_" in _e.what:
         CONTEXTS[_e.what] = "NDArray *rtn = 0, *nda = 0, *ndb = 0;"
 for _e in EDITS:
-    if _e.what.endswith("GPU early-out") and _e not in LINALG_EDITS:
+    if _e.what.endswith("GPU early-out") and _e not in LINALG_EDITS + CHOLESKY_EDITS:
         CONTEXTS[_e.what] = "NDArray *nda = 0, *ndb = 0;" if _e.file == "src/logic.c" else "NDArray *a = 0, *b = 0;"
 CONTEXTS.update({
     "linalg.c:254 NDArray_Det: GPU early-out": "NDArray *a = 0;",
     "linalg.c:575 NDArray_Inverse: GPU early-out": "NDArray *target = 0;",
     "linalg.c:634 NDArray_LU: GPU early-out": "NDArray *target = 0, *copied = 0, *p = 0, *l = 0, *u = 0; NDArray **rtns = 0;",
     "linalg.c:982-985 NDArray_Solve: GPU early-out": "NDArray *a = 0, *b = 0;",
+    "linalg.c:1057 NDArray_Cholesky: GPU early-out": "NDArray *a = 0;",
 })
 
 HIP_M4_BLOCK = '''dnl ---- MI355X (gfx950) through numpower_amd: added by numpower_amd/tools/apply_with_hip.py ----
@@ -641,7 +656,7 @@ def snippet_check_source() -> str:
     return "\n".join(out)
 
 
-FAST_BINARY = [(e.what.split(" ")[1].rstrip(":"), e) for e in EDITS if e.what.endswith("GPU early-out") and e not in LINALG_EDITS]   # ("NDArray_Add_Float", edit)
+FAST_BINARY = [(e.what.split(" ")[1].rstrip(":"), e) for e in EDITS if e.what.endswith("GPU early-out") and e not in LINALG_EDITS + CHOLESKY_EDITS]   # ("NDArray_Add_Float", edit)
 
 
 def fast_path_program_source() -> str:
@@ -730,6 +745,86 @@ def linalg_program_source() -> str:
          "#ifdef HAVE_NP_HIP", _indent(e["NDArray_Solve"].new, "    "), "#endif", "    return reference_body();", "}", ""]
     o.append(_LINALG_PROGRAM_MAIN)
     return "\n".join(o)
+
+
+def cholesky_program_source() -> str:
+    """A C99 PROGRAM around the text CHOLESKY_EDITS inserts into linalg.c: NDArray_Cholesky with the reference's signature, the
+    inserted text VERBATIM, then a stand-in for the reference's own code (its GPU throw and LAPACK call) that only counts
+    how often it is reached.  Built and linked like linalg_bodies.
+
+        cholesky_bodies cpu    a CPU operand falls through to the stand-in, no device is touched
+        cholesky_bodies gpu    GPU operands never fall through: a known answer (from the lower triangle alone, upper
+                               triangle +0), the not-positive-definite and the non-square throw, no device allocation leaks
+    """
+    (edit,) = CHOLESKY_EDITS
+    o = ["/* generated by tools/apply_with_hip.py: cholesky_program_source() — do not edit */",
+         "#include <math.h>", "#include <stdio.h>", "#include <string.h>", "",
+         "#define HAVE_NP_HIP 1", '#include "numpower_host.h"', '#include "hip_linalg.h"', "",
+         "static int g_fell_through;   /* calls that reached the reference's own code (the stand-in below) */",
+         "static NDArray *reference_body(void) { g_fell_through++; return NULL; }", "",
+         "static NDArray *patched_NDArray_Cholesky(NDArray *a) {", "#ifdef HAVE_NP_HIP", _indent(edit.new, ""), "#endif",
+         "    return reference_body();", "}", ""]
+    o.append(_CHOLESKY_PROGRAM_MAIN)
+    return "\n".join(o)
+
+
+_CHOLESKY_PROGRAM_MAIN = r"""static int g_failures;
+#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "cholesky_bodies: " __VA_ARGS__); fprintf(stderr, "\n"); g_failures++; } } while (0)
+
+static NDArray *make(const float *v, int rows, int cols, int gpu) {
+    int shape[2] = {rows, cols};
+    NDArray *h = NDArray_FromHostBuffer(v, shape, 2);
+    if (!gpu) return h;
+    NDArray *d = NDArray_ToGPU(h);
+    NDArray_FREE(h);
+    return d;
+}
+
+static int values(NDArray *a, float *out) {
+    NDArray *h = NDArray_ToCPU(a);
+    const int rc = h ? NDArray_CopyToHostBuffer(h, out) : -1;
+    if (h) NDArray_FREE(h);
+    return rc;
+}
+
+int main(int argc, char **argv) {
+    if (argc < 2 || (strcmp(argv[1], "cpu") && strcmp(argv[1], "gpu"))) {
+        fprintf(stderr, "usage: cholesky_bodies cpu|gpu\n");
+        return 2;
+    }
+    const int gpu = strcmp(argv[1], "gpu") == 0;
+    /* L0 = [[2,0,0],[-1,4,0],[2,1,1]]: a3 = L0 L0^T below and on the diagonal, values the factorization must not read above it */
+    const float a3[9] = {4, 99, -7, -2, 17, 1e30f, 4, 2, 6};
+    const float l3[9] = {2, 0, 0, -1, 4, 0, 2, 1, 1};
+    const float indef[4] = {1, 0, 2, 1};     /* lower triangle of [[1,2],[2,1]]: the second pivot is 1 - 4 */
+    const float wide[6] = {1, 0, 0, 0, 1, 0};
+    const long live0 = gpu ? NDArray_LiveDeviceAllocations() : 0;
+    NDArray *a = make(a3, 3, 3, gpu), *bad = make(indef, 2, 2, gpu), *w = make(wide, 2, 3, gpu);
+    NDArray *l = patched_NDArray_Cholesky(a);
+    if (!gpu) {
+        CHECK(!l, "a CPU operand was computed on the device");
+        CHECK(g_fell_through == 1, "%d of 1 calls reached the reference's code", g_fell_through);
+    } else {
+        float v[9];
+        int ok = l && values(l, v) == 0;
+        for (int i = 0; ok && i < 9; ++i) ok = v[i] == l3[i] && !signbit(v[i]) == !signbit(l3[i]);
+        CHECK(ok, "cholesky of the known matrix differs from the known factor");
+        CHECK(patched_NDArray_Cholesky(bad) == NULL &&
+              strcmp(numpower_host_last_error(), "Error calculating the cholesky decomposition. (Is $a not positive definite?)") == 0,
+              "a matrix that is not positive definite did not raise the reference's message");
+        CHECK(patched_NDArray_Cholesky(w) == NULL &&
+              strcmp(numpower_host_last_error(), "NDArray_Cholesky: $a must be a square matrix.") == 0,
+              "a 2 x 3 operand did not raise the reference's message");
+        CHECK(g_fell_through == 0, "%d GPU calls fell through to the reference's code", g_fell_through);
+    }
+    NDArray *all[] = {l, a, bad, w};
+    for (size_t i = 0; i < sizeof(all) / sizeof(all[0]); ++i)
+        if (all[i]) NDArray_FREE(all[i]);
+    if (gpu) CHECK(NDArray_LiveDeviceAllocations() == live0, "%ld device allocations leaked", NDArray_LiveDeviceAllocations() - live0);
+    printf("cholesky_bodies %s: %d calls reached the reference's own code, %d failures\n", argv[1], g_fell_through, g_failures);
+    return g_failures ? 1 : 0;
+}
+"""
 
 
 _LINALG_PROGRAM_MAIN = r"""static int g_failures;

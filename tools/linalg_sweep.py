@@ -2,7 +2,13 @@
 that covers the clock ramp.  getrf is timed together with the copy that restores its input (2 n^2 floats, included).
 Prints ms per call, TFLOP/s (2/3 n^3 for getrf, 2 n^3 for the inverse, 2/3 n^3 + 2 n^2 for solve), kernel launches per
 call, and numpy's fp32 solve on the host for comparison (the median of a few calls after a warm-up call).  The share of the trailing GEMMs comes from a run under
-`rocprofv3 --kernel-trace --stats` (profiles/linalg/).  Usage: python tools/linalg_sweep.py [--sizes 64,256,...] [--reps N]"""
+`rocprofv3 --kernel-trace --stats` (profiles/linalg/).  Usage: python tools/linalg_sweep.py [--sizes 64,256,...] [--reps N]
+
+--cholesky runs the Cholesky leg instead (profiles/linalg/cholesky_sweep.log): np_potrf against np_getrf of the same run at
+the same n and on the same matrix (A = X X^T / n + I), both timed with the copy that restores their input; TFLOP/s over
+n^3 / 3 and 2/3 n^3; the residual ||A - L L^T||_1 / ||A||_1 of np_cholesky's factor in float64 over eps = 2^-23 next to
+that of numpy's fp32 cholesky, and numpy's time on the host (the median of five calls after a warm-up), up to n = 8192.
+--no-host leaves the host work out (a run under the profiler)."""
 import argparse
 import ctypes as C
 import sys
@@ -14,10 +20,13 @@ from numpower_amd import device as D
 from numpower_amd._lib import Timer, check, load
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--sizes", default="64,256,1024,4096,8192,16384")
+ap.add_argument("--sizes", default=None, help="default 64,256,1024,4096,8192,16384 (with --cholesky also 128)")
+ap.add_argument("--cholesky", action="store_true", help="the Cholesky leg: np_potrf against np_getrf")
 ap.add_argument("--reps", type=int, default=0, help="0: as many as fit ~0.5 s per size (at least 3)")
 ap.add_argument("--no-host", action="store_true", help="skip numpy's solve on the host")
 args = ap.parse_args()
+if args.sizes is None:
+    args.sizes = "64,128,256,1024,4096,8192,16384" if args.cholesky else "64,256,1024,4096,8192,16384"
 
 D.init(0)
 lib = load()
@@ -54,6 +63,61 @@ while time.time() - t0 < 1.0:
     D.sync()
 ga.free()
 gc.free()
+
+
+
+def reps_for(fn):
+    t0 = time.time()
+    fn()
+    D.sync()
+    return args.reps or max(3, min(200, int(0.5 / max(time.time() - t0, 1e-5))))
+
+
+def residual_over_eps(a64, l):
+    l64 = l.astype(np.float64)
+    return float(np.abs(a64 - l64 @ l64.T).sum(axis=0).max() / np.abs(a64).sum(axis=0).max()) * 2.0 ** 23
+
+
+if args.cholesky:
+    print("%6s %10s %9s %9s %10s %9s %9s %7s %8s %8s   %s" % ("n", "potrf ms", "TFLOP/s", "launches", "getrf ms", "TFLOP/s", "launches",
+                                                             "ratio", "r/eps", "ref/eps", "host numpy fp32 cholesky"), flush=True)
+    for n in [int(s) for s in args.sizes.split(",")]:
+        x = np.random.default_rng(n).standard_normal((n, n)).astype(np.float32)
+        a = x @ x.T / np.float32(n) + np.eye(n, dtype=np.float32)
+        del x
+        a = np.tril(a) + np.tril(a, -1).T
+        da, work, piv, info = D.DeviceArray.from_host(a), D.DeviceArray((n, n)), D.DeviceArray((n,)), D.DeviceArray((1,))
+
+        def potrf():
+            check(lib.np_memcpy_d2d(work.ptr, da.ptr, 4 * n * n))
+            check(lib.np_potrf(work.ptr, n, info.ptr))
+
+        def getrf():
+            check(lib.np_memcpy_d2d(work.ptr, da.ptr, 4 * n * n))
+            check(lib.np_getrf(work.ptr, n, piv.ptr, info.ptr))
+
+        p_ms, p_launches = timed(potrf, reps_for(potrf))
+        assert int(info.to_host().view(np.int32)[0]) == 0
+        g_ms, g_launches = timed(getrf, reps_for(getrf))
+        r = ref = host = "-"
+        if not args.no_host and n <= 8192:
+            ih = C.c_int()
+            check(lib.np_cholesky(da.ptr, n, work.ptr, C.byref(ih)))
+            a64 = a.astype(np.float64)
+            r = "%.3f" % residual_over_eps(a64, work.to_host())
+            ref = "%.3f" % residual_over_eps(a64, np.linalg.cholesky(a))   # also the warm-up call
+            ts = []
+            for _ in range(5):
+                h0 = time.perf_counter()
+                np.linalg.cholesky(a)
+                ts.append((time.perf_counter() - h0) * 1e3)
+            host = "%.3f ms (median of 5 after a warm-up)" % float(np.median(ts))
+        print("%6d %10.3f %9.2f %9d %10.3f %9.2f %9d %7.3f %8s %8s   %s"
+              % (n, p_ms, n ** 3 / 3 / p_ms / 1e9, p_launches, g_ms, 2 / 3 * n ** 3 / g_ms / 1e9, g_launches, p_ms / g_ms, r, ref, host),
+              flush=True)
+        for d in (da, work, piv, info):
+            d.free()
+    sys.exit(0)
 
 print("%6s %-8s %10s %9s %9s   %s" % ("n", "op", "ms", "TFLOP/s", "launches", "host numpy fp32 solve"), flush=True)
 for n in [int(s) for s in args.sizes.split(",")]:
