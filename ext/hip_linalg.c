@@ -1,7 +1,8 @@
 /*
- * hip_linalg.c — the device side of NDArray_Det / Inverse / LU / Solve / Cholesky (hip_linalg.h).  Compiled into a --with-hip tree
+ * hip_linalg.c — the device side of NDArray_Det / Inverse / LU / Solve / Cholesky / SVD (hip_linalg.h).  Compiled into a --with-hip tree
  * against the reference's headers (-DNUMPOWER_NDARRAY_HEADER='"src/initializers.h"') and into libnumpower_host.so
- * against include/numpower_host.h; it uses only what both declare.
+ * against include/numpower_host.h; it uses only what both declare, with one switch: the reference's arrays take ownership of
+ * an emalloc'd shape and its result vectors are emalloc'd, the host library copies shapes and hands out malloc'd vectors.
  */
 #ifndef NUMPOWER_NDARRAY_HEADER
 #define NUMPOWER_NDARRAY_HEADER "numpower_host.h"
@@ -13,6 +14,17 @@
 #include "hip_linalg.h"
 #include "np_ext_hooks.h"
 #include "np_hip.h"
+
+#ifdef NUMPOWER_AMD_HOST_H
+#include <stdlib.h>
+#define NPH_ALLOC(bytes) malloc(bytes)
+#define NPH_RELEASE(ptr) free(ptr)
+#define NPH_SHAPE_IS_COPIED 1
+#else
+#define NPH_ALLOC(bytes) emalloc(bytes)
+#define NPH_RELEASE(ptr) efree(ptr)
+#define NPH_SHAPE_IS_COPIED 0
+#endif
 
 static const char kSingular[] = "LU factorization failed. Unable to compute the matrix inverse.\n";   /* linalg.c:488-490 */
 
@@ -128,4 +140,58 @@ NDArray *NPH_Cholesky(NDArray *a) {
         return NULL;
     }
     return rtn;
+}
+
+/* a zero-filled fp32 GPU array of ndim (1 or 2) dimensions */
+static NDArray *zeros_on_gpu(int ndim, int d0, int d1) {
+    int *shape = (int *) NPH_ALLOC(sizeof(int) * 2);
+    if (shape == NULL) return NULL;
+    shape[0] = d0;
+    shape[1] = d1;
+    NDArray *rtn = NDArray_Zeros(shape, ndim, "float32", NDARRAY_DEVICE_GPU);
+    if (NPH_SHAPE_IS_COPIED) NPH_RELEASE(shape);
+    return rtn;
+}
+
+NDArray **NPH_SVD(NDArray *a) {
+    if (a == NULL) return NULL;
+    if (NDArray_NDIM(a) == 1) {                                                  /* linalg.c:122-125 */
+        np_ext_throw("Array must be at least two-dimensional");
+        return NULL;
+    }
+    if (NDArray_NDIM(a) != 2) {   /* the reference reads the first two extents of whatever it is given */
+        np_ext_throw("svd: only two-dimensional GPU arrays are supported (batches of matrices are not)");
+        return NULL;
+    }
+    if (!on_gpu(a)) return NULL;
+    const int m = NDArray_SHAPE(a)[0], n = NDArray_SHAPE(a)[1], k = m < n ? m : n;
+    /* the reference's shapes (linalg.c:171-184): U (m, m), S (k), V (n, n); the thin factors fill the leading k columns of U
+     * and the leading k rows of V, the rest is +0.0f */
+    NDArray *u = zeros_on_gpu(2, m, m), *s = zeros_on_gpu(1, k, 0), *v = zeros_on_gpu(2, n, n);
+    NDArray *thin = (m > n) ? zeros_on_gpu(2, m, k) : NULL;                      /* m x k does not sit in m x m as it is */
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 3);
+    int ok = u != NULL && s != NULL && v != NULL && rtns != NULL && (m <= n || thin != NULL);
+    int info = 0;
+    if (ok && np_svd(NDArray_FDATA(a), (size_t) m, (size_t) n, NDArray_FDATA(thin != NULL ? thin : u), NDArray_FDATA(s),
+                     NDArray_FDATA(v), &info) != NP_OK) {
+        np_ext_throw_last();
+        ok = 0;
+    }
+    if (ok && thin != NULL &&
+        np_copy2d(NDArray_FDATA(u), (size_t) m, NDArray_FDATA(thin), (size_t) k, (size_t) k, (size_t) m) != NP_OK) {
+        np_ext_throw_last();
+        ok = 0;
+    }
+    if (thin != NULL) NDArray_FREE(thin);
+    if (!ok) {   /* info > 0 (the sweep cap) is no error: the factors still reconstruct a, as cuSOLVER's gesvdj reports it */
+        if (u != NULL) NDArray_FREE(u);
+        if (s != NULL) NDArray_FREE(s);
+        if (v != NULL) NDArray_FREE(v);
+        if (rtns != NULL) NPH_RELEASE(rtns);
+        return NULL;
+    }
+    rtns[0] = u;
+    rtns[1] = s;
+    rtns[2] = v;
+    return rtns;
 }

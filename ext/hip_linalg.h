@@ -16,6 +16,12 @@
  *
  *     NDArray_Cholesky at the top, before its GPU throw             return NPH_Cholesky(a);
  *
+ * and one into NDArray_SVD, whose GPU branch calls cuSOLVER under --with-cuda and returns NULL without it:
+ *
+ *     NDArray_SVD      at the top                                   return NPH_SVD(target);
+ *
+ * (NDArray_MatrixRank, NDArray_L2Norm and NDArray_Cond are host code over NDArray_SVD and work for GPU arrays with it.)
+ *
  * each guarded by `#ifdef HAVE_NP_HIP` and NPH_LINALG_TAKES: CPU operands fall through to the reference's LAPACK code.
  * The cuda_det_float / cuda_matrix_float_inverse stubs of hip_math.c are never reached in such a tree.
  *
@@ -48,6 +54,11 @@ struct NDArray *NPH_Solve(struct NDArray *a, struct NDArray *b);
  * "NDArray_Cholesky: $a must be a square matrix."; a pivot that is not positive:
  * "Error calculating the cholesky decomposition. (Is $a not positive definite?)" */
 struct NDArray *NPH_Cholesky(struct NDArray *a);
+/* the vector {U (m, m), S (k), V (n, n)}, k = min(m, n), allocated the way the host allocates result vectors: the thin
+ * factors of np_svd in the leading k columns of U and the leading k rows of V (V holds the right singular vectors as ROWS,
+ * as on the reference's CPU path), +0.0f elsewhere, so U diag(S, 0) V = a.  1-d: "Array must be at least two-dimensional";
+ * other ranks are refused (the reference reads the first two extents). */
+struct NDArray **NPH_SVD(struct NDArray *a);
 
 #ifdef __cplusplus
 }

@@ -414,6 +414,35 @@ int np_lu(const float *a, size_t n, float *p, float *l, float *u);
 int np_potrf(float *a, size_t n, int *info);
 int np_cholesky(const float *a, size_t n, float *out, int *info_host);
 
+/* ---- singular value decomposition (np_linalg.hip; DESIGN.md "SVD") --------------------------------
+ * One-sided (Hestenes) Jacobi, blocked: replaces cuda_svd_float (cuda_math.cu:947, cuSOLVER's gesvdj) behind NDArray_SVD.
+ * a: m x n fp32, ROW-MAJOR, untouched.  k = min(m, n).
+ * u: m x k row-major, s: k, vt: k x n row-major, with  a = u . diag(s) . vt,  s >= 0 and non-increasing.
+ * *info_host (host int): 0 = converged, > 0 = the sweep cap (60) was reached — the value: how many column pairs were still
+ * above the tolerance (|g_pq| <= 4 eps sqrt(g_pp g_qq)) in the last sweep, clipped to INT_MAX; the factors are returned
+ * either way and still reconstruct a.  Blocks until info is known.
+ * np_svdvals: singular values only — no V accumulation, no U normalisation; the same s bit for bit as np_svd.
+ * Library stream, scratch from the caching pool, no float atomics, one fixed rotation order: bit-identical from run to run.
+ * Scratch: with r = min(m, n) rounded up to 64 and c = max(m, n) rounded up to 32, the work matrix r x c, for np_svd the
+ * accumulated r x r rotations and one k x max(m, n) staging matrix (np_svdvals: that one only for m >= n), and per pair of
+ * 32-row blocks (r / 64 of them) up to 17 matrices of 64 x 64 floats.
+ * Fine print:
+ *   - signs are not normalised (an SVD is unique only up to the sign of each pair u_i, v_i); they are deterministic.
+ *   - for m >= n the columns of a are rotated: vt is a product of rotations and always orthonormal; column i of u is the
+ *     rotated column divided by s_i.  If s_i is exactly 0 that column of u is written as +0.0f; for a negligible s_i
+ *     (<= max(m, n) eps s_0) it is normalised noise and need not be orthogonal to the others.  For m < n the transposed
+ *     problem is solved and the roles of u and vt swap.  (cuSOLVER's gesvdj has the same property; LAPACK completes the
+ *     basis.  This library does not.)
+ *   - non-finite input: the call returns (the sweep loop is bounded by the cap, nothing spins on a NaN compare), s contains
+ *     at least one NaN, nothing else is promised.
+ *   - min(m, n) <= 64 with a row length that fits LDS (64 x 557, 5 x 7000 ...) is ONE launch of one workgroup (unblocked, rotations
+ *     applied in fp32); everything else is the blocked form.  np_svd and np_svdvals of one shape always take the same path.
+ *   - tested up to 4097 x 4097.  The sweep count grows with min(m, n) (26 at 4096 x 4096 on a well-conditioned dense matrix), so
+ *     for much larger matrices info > 0 at the cap may be the normal outcome; the factors still reconstruct a then.
+ * m == 0 || n == 0 does nothing and reports 0; null pointers are NP_ERR_INVALID; m, n <= 65536.  Outputs must not overlap a. */
+int np_svd(const float *a, size_t m, size_t n, float *u, float *s, float *vt, int *info_host);
+int np_svdvals(const float *a, size_t m, size_t n, float *s, int *info_host);
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

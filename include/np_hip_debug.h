@@ -101,6 +101,15 @@ int np_debug_raise_device_error(unsigned bits);
 /* testing: kernel launches the library has issued since it was loaded (all devices, all threads): the difference around an
  * expression is how many launches it cost — `nd::exp($a) * $b + 2` through the pending chains of INTEGRATION.md 2c: one. */
 int np_debug_launch_count(unsigned long long *host_count);
+/* testing: the sweep cap of np_svd / np_svdvals from now on (0 = the default, 60): with 1 a dense matrix cannot converge, which
+ * is how a test reaches info > 0 without a pathological matrix.  Process-global. */
+int np_debug_svd_max_sweeps(int sweeps);
+/* tools: sweeps the last np_svd / np_svdvals call of the process took (the converged one, which rotates nothing, included).
+ * A plain process global, like the two knobs around it: meaningful only while one thread calls the SVD. */
+int np_debug_svd_last_sweeps(int *host_sweeps);
+/* testing / A-B: on = 0 sends every shape through the blocked path, on != 0 (the default) lets min(m, n) <= 64 with a row
+ * length that fits LDS take the one-launch kernel.  Process-global. */
+int np_debug_svd_small_path(int on);
 
 #ifdef __cplusplus
 }

@@ -324,6 +324,20 @@ NDArray *NDArray_Solve(NDArray *a, NDArray *b);
  * "Error calculating the cholesky decomposition. (Is $a not positive definite?)" when a pivot is not positive. */
 NDArray *NDArray_Cholesky(NDArray *a);
 
+/* ---- singular value decomposition (host/numpower_linalg.cpp; linalg.c:111-209, 402-470, 668-715, 1038-1050) ----
+ * GPU operands only, views made contiguous; the device Jacobi SVD (np_svd / np_svdvals) does the work.
+ * NDArray_SVD         malloc'd vector {U (m, m), S (k), V (n, n)}, k = min(m, n): the thin factors in the leading k columns of U
+ *                     and the leading k rows of V (rows of V are right singular vectors, as on the reference's CPU path),
+ *                     +0.0f elsewhere, S descending.  1-d: "Array must be at least two-dimensional"; ndim > 2 is refused.
+ * NDArray_MatrixRank  a 0-d array: how many singular values are > tol (default s_max max(m, n) FLT_EPSILON when tol is NULL)
+ * NDArray_Norm        type 2: the largest singular value as a 0-d GPU array; type 1 is refused for GPU arrays; any other
+ *                     type: "NDArray_Norm: The provided norm `%d` is invalid"
+ * NDArray_Cond        norm2(a) norm2(inv(a)); a singular a raises NDArray_Inverse's message */
+NDArray **NDArray_SVD(NDArray *target);
+NDArray *NDArray_MatrixRank(NDArray *target, float *tol);
+NDArray *NDArray_Norm(NDArray *target, int type);
+NDArray *NDArray_Cond(NDArray *a);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,8 @@ PROTOTYPES = {
     "np_lu": (C.c_int, [_f32p, C.c_size_t, _f32p, _f32p, _f32p]),
     "np_potrf": (C.c_int, [_f32p, C.c_size_t, C.c_void_p]),
     "np_cholesky": (C.c_int, [_f32p, C.c_size_t, _f32p, C.POINTER(C.c_int)]),
+    "np_svd": (C.c_int, [_f32p, C.c_size_t, C.c_size_t, _f32p, _f32p, _f32p, C.POINTER(C.c_int)]),
+    "np_svdvals": (C.c_int, [_f32p, C.c_size_t, C.c_size_t, _f32p, C.POINTER(C.c_int)]),
     "np_permute": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "np_strided_copy": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "np_identity": (C.c_int, [_f32p, C.c_size_t]),
@@ -150,6 +152,9 @@ PROTOTYPES = {
     "np_select_last_path": (C.c_int, [C.POINTER(C.c_int)]),
     "np_debug_raise_device_error": (C.c_int, [C.c_uint]),
     "np_debug_launch_count": (C.c_int, [C.POINTER(C.c_ulonglong)]),
+    "np_debug_svd_max_sweeps": (C.c_int, [C.c_int]),
+    "np_debug_svd_last_sweeps": (C.c_int, [C.POINTER(C.c_int)]),
+    "np_debug_svd_small_path": (C.c_int, [C.c_int]),
     "np_clear_device_error": (C.c_int, [C.POINTER(C.c_uint)]),
     "np_debug_clock_mhz": (C.c_int, [C.POINTER(C.c_float)]),
 }

@@ -236,6 +236,31 @@ def build_cholesky_bodies(force: bool = False, verbose: bool = False) -> Path:
     return exe
 
 
+def build_svd_bodies(force: bool = False, verbose: bool = False) -> Path:
+    """The text tools/apply_with_hip.py inserts into the reference's NDArray_SVD (SVD), wrapped
+    into a C99 program by the tool itself (svd_program_source) -> build/gen/svd_bodies.c ->
+    numpower_amd/lib/svd_bodies; -Wall -Wextra -Werror against numpower_host.h + hip_linalg.h."""
+    exe = LIBDIR / "svd_bodies"
+    tool = ROOT / "tools" / "apply_with_hip.py"
+    gen = ROOT / "build" / "gen" / "svd_bodies.c"
+    deps = [tool, LIBDIR / "libnumpower_host.so"] + list(INCLUDE.glob("*.h")) + list(EXT.glob("*.h"))
+    if force or _newer(exe, deps):
+        if verbose:
+            print("[build] generating + compiling svd_bodies", flush=True)
+        import importlib.util
+        spec = importlib.util.spec_from_file_location("np_apply_with_hip", tool)
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules[spec.name] = mod
+        spec.loader.exec_module(mod)
+        gen.parent.mkdir(parents=True, exist_ok=True)
+        gen.write_text(mod.svd_program_source())
+        cc = shutil.which("gcc") or "gcc"
+        flags = [f for f in EXT_CFLAGS if f != "-fPIC"]
+        _run([cc, *flags, str(gen), "-o", str(exe), f"-L{LIBDIR}", "-lnumpower_host", "-lnp_hip",
+              "-Wl,-rpath,$ORIGIN"])
+    return exe
+
+
 def build_lazy_bodies(force: bool = False, verbose: bool = False) -> Path:
     """The text tools/apply_with_hip.py inserts for the pending chains (buffer_get's flush, the appenders of
     numpower.c's operator handler, static arithmetic methods and unary methods), wrapped by the tool itself into a C99 program
@@ -306,6 +331,7 @@ def build_all(force: bool = False, verbose: bool = False):
     build_lazy_bodies(force, verbose)
     build_linalg_bodies(force, verbose)
     build_cholesky_bodies(force, verbose)
+    build_svd_bodies(force, verbose)
     oracle = build_oracle(force, verbose)
     build_loopback_rccl(force, verbose)
     return hip, host, oracle

@@ -16,6 +16,7 @@
 // triangular solves — a kNB x kNB diagonal block per launch, the rest of the right-hand sides updated on the GEMM.
 //
 // Cholesky (potrf / cholesky; DESIGN.md "Cholesky") is further down: row-major, lower triangle, no pivoting, its own kernels.
+// So is the SVD (svd / svdvals; DESIGN.md "SVD"): blocked one-sided Jacobi, its own kernels, nothing shared with the LU.
 #include <limits.h>
 
 #include "np_internal.h"
@@ -614,6 +615,460 @@ __global__ __launch_bounds__(256) void chol_tri_kernel(const float *src, float *
     }
 }
 
+// ---- SVD: one-sided (Hestenes) Jacobi, blocked over pairs of 32-row blocks ----
+//
+// The work matrix W holds one "column of a" per row (W = a^T for m >= n, a itself for m < n: the transposed problem), padded
+// with zero rows to a multiple of 64 and zero columns to a multiple of 32; Vt starts as I.  A sweep is a round-robin tournament
+// over the 32-row blocks.  Per step and block pair (rows P, 64 x L):
+//   svd_gram_kernel   G = P P^T on v_mfma_f32_32x32x2_f32, a wave per 32 x 32 quadrant, the row length cut into up to 16
+//                     workgroups whose partial Grams are stored one by one
+//   svd_eig_kernel    folds the partials in index order, counts the row pairs above the tolerance and, if there are any,
+//                     diagonalises G by two-sided cyclic Jacobi in LDS — G, the rotations and their product M in fp64, M rounded
+//                     to fp32 once at the end
+//   svd_apply_kernel  P <- M P and the same for the 64 rows of Vt, on the MFMA, a wave per 32 columns, in place (a wave
+//                     reads all 64 rows of its columns before it stores one); pairs without a rotation are skipped
+// Up to 64 rows whose length fits LDS take svd_small_kernel instead: one launch, one workgroup (further down).
+// A zero row never rotates, so the padding stays what it is.  The only cross-workgroup sums are integer counters and an integer
+// max of float bit patterns: order-independent, so every call gives the same bits.
+constexpr int kSvdB = 32;                // rows of a block
+constexpr int kSvdP = 2 * kSvdB;         // rows of a block pair
+constexpr int kSvdStr = kSvdP + 1;       // row stride of a 64 x 64 matrix in LDS
+constexpr int kSvdMaxSplit = 16;         // partial Grams per pair at most
+constexpr int kSvdSweepCap = 60;         // 26 sweeps at 4096 x 4096: the count grows with n
+constexpr int kSvdInnerCap = 10;         // sweeps of the 64 x 64 eigenproblem at most (any orthogonal M is a valid step)
+constexpr double kSvdTol = 4.0 * 1.1920928955078125e-7;
+constexpr size_t kSvdMaxDim = 65536;
+int g_svd_max_sweeps = 0;                // np_debug_svd_max_sweeps
+int g_svd_last_sweeps = 0;               // np_debug_svd_last_sweeps
+int g_svd_small_off = 0;                 // np_debug_svd_small_path(0): every shape takes the blocked path (A/B, tests)
+
+typedef float svd_v16f __attribute__((ext_vector_type(16)));
+
+struct SvdCtl {
+    unsigned long long above;        // row pairs found above the tolerance by any workgroup of the sweep (0 = converged)
+    unsigned long long above_once;   // the same with every row pair counted once (k (k - 1) / 2 at most: 2^31 at k = 65536)
+    unsigned maxbits;                // bit pattern of the largest squared row norm at the start of the sweep
+    int pad;
+};
+
+// block pair j of tournament step `step` over nblk (even) blocks: position 0 stays, the others go round
+__device__ __forceinline__ void svd_pair(int nblk, int step, int j, int &p, int &q) {
+    const int r = nblk - 1;
+    const int a = j == 0 ? 0 : 1 + (j - 1 + step) % r;
+    const int b = 1 + (nblk - 2 - j + step) % r;
+    p = a < b ? a : b;
+    q = a < b ? b : a;
+}
+
+// global row of local row k (0 .. 63) of the block pair (p, q)
+__device__ __forceinline__ size_t svd_row(int p, int q, int k) {
+    return k < kSvdB ? (size_t)p * kSvdB + k : (size_t)q * kSvdB + (k - kSvdB);
+}
+
+// a, b squared norms, g the dot product; lim: both norms at or under it = a negligible pair
+__device__ __forceinline__ bool svd_active(double a, double b, double g, double lim) {
+    return a > 0.0 && b > 0.0 && !(a <= lim && b <= lim) && fabs(g) > kSvdTol * sqrt(a * b);
+}
+
+// squared norm of every row (a wave per row, one fixed order) and the largest of them into ctl->maxbits
+__global__ __launch_bounds__(256) void svd_rownorm_kernel(const float *W, size_t ld, size_t nrows, float *normsq, SvdCtl *ctl) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t row = (size_t)blockIdx.x * 4 + wave;
+    if (row >= nrows) return;
+    const float *w = W + row * ld;
+    float acc = 0.0f;
+    for (size_t c = lane; c < ld; c += 64) acc = fmaf(w[c], w[c], acc);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if (lane == 0) {
+        normsq[row] = acc;
+        atomicMax(&ctl->maxbits, __float_as_uint(acc));   // non-negative floats order as their bits (a NaN ends on top)
+    }
+}
+
+__global__ __launch_bounds__(256) void svd_gram_kernel(const float *W, size_t ld, int nblk, int step, int tiles_per_split,
+                                                       int ntiles, int nsplit, float *Gpart) {
+    __shared__ float T[kSvdP * 33];
+    int p, q;
+    svd_pair(nblk, step, blockIdx.x, p, q);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int bi = wave >> 1, bj = wave & 1, i = lane & 31, kq = lane >> 5;
+    svd_v16f acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    const int t0 = blockIdx.y * tiles_per_split;
+    const int t1 = t0 + tiles_per_split < ntiles ? t0 + tiles_per_split : ntiles;
+    const int col = tid & 31, r0 = tid >> 5;
+    for (int t = t0; t < t1; ++t) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int row = r0 + 8 * u;
+            T[row * 33 + col] = W[svd_row(p, q, row) * ld + (size_t)t * 32 + col];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < 32; kk += 2) {
+            const float a = T[(bi * 32 + i) * 33 + kk + kq];
+            const float b = T[(bj * 32 + i) * 33 + kk + kq];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    float *out = Gpart + ((size_t)blockIdx.x * nsplit + blockIdx.y) * (kSvdP * kSvdP);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = bi * 32 + (r & 3) + 8 * (r >> 2) + 4 * kq;
+        out[row * kSvdP + bj * 32 + i] = acc[r];
+    }
+}
+
+// dynamic LDS: G and M, kSvdP x kSvdStr doubles each
+__global__ __launch_bounds__(256) void svd_eig_kernel(const float *Gpart, int nsplit, int step, float thr, SvdCtl *ctl,
+                                                      float *Mbuf, int *flag) {
+    extern __shared__ double svd_sm[];
+    double *G = svd_sm, *M = svd_sm + kSvdP * kSvdStr;
+    __shared__ double cs_c[32], cs_s[32];
+    __shared__ int cs_p[32], cs_q[32];
+    __shared__ int s_cnt[2];
+    __shared__ int s_rot;
+    const int tid = threadIdx.x, pair = blockIdx.x;
+    const float *gp = Gpart + (size_t)pair * nsplit * (kSvdP * kSvdP);
+    for (int idx = tid; idx < kSvdP * kSvdP; idx += 256) {
+        float acc = gp[idx];   // (folding in fp64 instead was tried: no fewer sweeps)
+        for (int s = 1; s < nsplit; ++s) acc += gp[(size_t)s * (kSvdP * kSvdP) + idx];
+        const int r = idx >> 6, c = idx & 63;
+        G[r * kSvdStr + c] = (double)acc;
+        M[r * kSvdStr + c] = r == c ? 1.0 : 0.0;
+    }
+    if (tid < 2) s_cnt[tid] = 0;
+    if (tid == 0) s_rot = 0;
+    __syncthreads();
+    const double maxsq = (double)__uint_as_float(ctl->maxbits);
+    const double lim = (double)thr * (double)thr * maxsq;
+    int all = 0, once = 0;
+    for (int idx = tid; idx < kSvdP * kSvdP; idx += 256) {
+        const int i = idx >> 6, j = idx & 63;
+        if (i < j && svd_active(G[i * kSvdStr + i], G[j * kSvdStr + j], G[i * kSvdStr + j], lim)) {
+            ++all;
+            if (step == 0 || ((i < kSvdB) != (j < kSvdB))) ++once;   // rows of one block meet again in every step
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        all += __shfl_down(all, off, 64);
+        once += __shfl_down(once, off, 64);
+    }
+    if ((tid & 63) == 0) {
+        atomicAdd(&s_cnt[0], all);
+        atomicAdd(&s_cnt[1], once);
+    }
+    __syncthreads();
+    if (s_cnt[0] == 0) {   // uniform: nothing to rotate, M = I, the apply kernel skips the pair
+        if (tid == 0) flag[pair] = 0;
+        return;
+    }
+    if (tid == 0) {
+        atomicAdd(&ctl->above, (unsigned long long)s_cnt[0]);
+        atomicAdd(&ctl->above_once, (unsigned long long)s_cnt[1]);
+    }
+    int p = 0, q = 0;
+    bool mine = false;
+    for (int isw = 0; isw < kSvdInnerCap; ++isw) {
+        for (int st = 0; st < kSvdP - 1; ++st) {
+            if (tid < 32) {
+                svd_pair(kSvdP, st, tid, p, q);
+                const double gpp = G[p * kSvdStr + p], gqq = G[q * kSvdStr + q], gpq = G[p * kSvdStr + q];
+                double c = 1.0, s = 0.0;
+                mine = svd_active(gpp, gqq, gpq, lim);
+                if (mine) {
+                    const double z = (gqq - gpp) / (2.0 * gpq);
+                    const double t = (z >= 0.0 ? 1.0 : -1.0) / (fabs(z) + sqrt(1.0 + z * z));
+                    c = 1.0 / sqrt(1.0 + t * t);
+                    s = c * t;
+                    s_rot = 1;
+                }
+                cs_c[tid] = c;
+                cs_s[tid] = s;
+                cs_p[tid] = p;
+                cs_q[tid] = q;
+            }
+            __syncthreads();
+            {   // rows p, q of G and of M
+                const int col = tid & 63;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int pr = (tid >> 6) + 4 * u;
+                    const double c = cs_c[pr], s = cs_s[pr];
+                    if (s != 0.0) {
+                        const int rp = cs_p[pr] * kSvdStr + col, rq = cs_q[pr] * kSvdStr + col;
+                        const double gp_ = G[rp], gq_ = G[rq], mp_ = M[rp], mq_ = M[rq];
+                        G[rp] = c * gp_ - s * gq_;
+                        G[rq] = s * gp_ + c * gq_;
+                        M[rp] = c * mp_ - s * mq_;
+                        M[rq] = s * mp_ + c * mq_;
+                    }
+                }
+            }
+            __syncthreads();
+            {   // columns p, q of G
+                const int row = tid & 63;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int pr = (tid >> 6) + 4 * u;
+                    const double c = cs_c[pr], s = cs_s[pr];
+                    if (s != 0.0) {
+                        const int cp = row * kSvdStr + cs_p[pr], cq = row * kSvdStr + cs_q[pr];
+                        const double gp_ = G[cp], gq_ = G[cq];
+                        G[cp] = c * gp_ - s * gq_;
+                        G[cq] = s * gp_ + c * gq_;
+                    }
+                }
+            }
+            __syncthreads();
+            if (tid < 32 && mine) {
+                G[p * kSvdStr + q] = 0.0;
+                G[q * kSvdStr + p] = 0.0;
+            }
+        }
+        __syncthreads();
+        const int rot = s_rot;
+        __syncthreads();
+        if (tid == 0) s_rot = 0;
+        __syncthreads();
+        if (!rot) break;
+    }
+    float *out = Mbuf + (size_t)pair * (kSvdP * kSvdP);
+    for (int idx = tid; idx < kSvdP * kSvdP; idx += 256) out[idx] = (float)M[(idx >> 6) * kSvdStr + (idx & 63)];
+    if (tid == 0) flag[pair] = 1;
+}
+
+// X <- M X for the block pair's 64 rows of W (chunks 0 .. wchunks - 1 of 128 columns) and of V (the chunks after them)
+__global__ __launch_bounds__(256) void svd_apply_kernel(float *W, size_t ldw, int wchunks, float *V, size_t ldv, int nblk,
+                                                        int step, const float *Mbuf, const int *flag) {
+    __shared__ float Ms[kSvdP * kSvdStr];
+    const int pair = blockIdx.x;
+    if (!flag[pair]) return;
+    int p, q;
+    svd_pair(nblk, step, pair, p, q);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *Mg = Mbuf + (size_t)pair * (kSvdP * kSvdP);
+    for (int idx = tid; idx < kSvdP * kSvdP; idx += 256) Ms[(idx >> 6) * kSvdStr + (idx & 63)] = Mg[idx];
+    __syncthreads();
+    const bool onw = (int)blockIdx.y < wchunks;
+    float *X = onw ? W : V;
+    const size_t ld = onw ? ldw : ldv;
+    const size_t col0 = (size_t)(onw ? blockIdx.y : blockIdx.y - wchunks) * 128 + (size_t)wave * 32;
+    if (col0 >= ld) return;   // ld is a multiple of 32: a wave's 32 columns are all there or none is
+    const int i = lane & 31, kq = lane >> 5;
+    float b[32];
+#pragma unroll
+    for (int kk = 0; kk < 32; ++kk) b[kk] = X[svd_row(p, q, 2 * kk + kq) * ld + col0 + i];
+    svd_v16f acc0, acc1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        acc0[r] = 0.0f;
+        acc1[r] = 0.0f;
+    }
+#pragma unroll
+    for (int kk = 0; kk < 32; ++kk) {
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(Ms[i * kSvdStr + 2 * kk + kq], b[kk], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(Ms[(32 + i) * kSvdStr + 2 * kk + kq], b[kk], acc1, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int lr = (r & 3) + 8 * (r >> 2) + 4 * kq;
+        X[((size_t)p * kSvdB + lr) * ld + col0 + i] = acc0[r];
+        X[((size_t)q * kSvdB + lr) * ld + col0 + i] = acc1[r];
+    }
+}
+
+// ---- small path: k <= 64 rows whose length fits LDS — the whole decomposition in ONE launch of one workgroup ----
+// W (k rows of L floats, row stride Ls, odd) and Vt (k x k, row stride Vs, odd) live in LDS.  Unblocked one-sided Jacobi: a
+// round-robin tournament over the rows (padded to an even count; the dummy never plays), k / 2 disjoint pairs per step, a
+// half-wave per pair: three dot products in fp32 (lane-strided fmaf chains, then a butterfly: every lane holds the same bits), the
+// rotation in fp64 from them, rounded once, applied to both rows of W and of Vt by the half-wave's lanes.  One barrier per step.  The
+// tail — norms, stable descending ranks, __fsqrt_rn / __fdiv_rn, +0.0f for a zero norm — is the blocked path's, in the same launch.
+struct SvdSmallArgs {
+    const float *a;
+    int k, L, Ls, Vs;    // rows (min(m, n)), their length (max(m, n)), LDS row strides of W and Vt
+    int wide;            // m < n: the rows of a are the rows of W; else W = a^T
+    int vectors;
+    int cap;
+    float thr;           // max(m, n) eps
+    float *u, *s, *vt;
+    int *out2;           // out2[0] = info, out2[1] = sweeps taken
+};
+
+__device__ __forceinline__ float svd_wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// the same within each half of the wave (the offsets stay below 32: no lane reads the other half, whatever that half is doing)
+__device__ __forceinline__ float svd_half_sum(float v) {
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(1024) void svd_small_kernel(SvdSmallArgs p) {
+    extern __shared__ float svd_small_sm[];
+    const int k = p.k, L = p.L, Ls = p.Ls, Vs = p.Vs;
+    float *W = svd_small_sm, *V = W + (size_t)k * Ls, *nsq = V + (size_t)k * Vs;
+    int *rank = (int *)(nsq + k);
+    __shared__ int s_cnt;
+    __shared__ unsigned s_max;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+    const int hl = lane & 31, half = lane >> 5;
+    const int ke = k + (k & 1);
+    for (int idx = tid; idx < k * L; idx += blockDim.x) {
+        if (p.wide) {
+            W[(idx / L) * Ls + idx % L] = p.a[idx];
+        } else {   // a is L x k: element (r, i) goes to row i
+            W[(idx % k) * Ls + idx / k] = p.a[idx];
+        }
+    }
+    if (p.vectors)
+        for (int idx = tid; idx < k * k; idx += blockDim.x) V[(idx / k) * Vs + idx % k] = idx / k == idx % k ? 1.0f : 0.0f;
+    if (tid == 0) {
+        s_cnt = 0;
+        s_max = 0u;
+    }
+    __syncthreads();
+    int sweeps = 0, above = 0;
+    for (int sweep = 0; sweep < p.cap; ++sweep) {
+        for (int i = wave; i < k; i += nw) {   // the largest squared norm at the start of the sweep: the negligible-pair rule
+            const float *w = W + i * Ls;
+            float acc = 0.0f;
+            for (int c = lane; c < L; c += 64) acc = fmaf(w[c], w[c], acc);
+            acc = svd_wave_sum(acc);
+            if (lane == 0) atomicMax(&s_max, __float_as_uint(acc));
+        }
+        __syncthreads();
+        const double lim = (double)p.thr * (double)p.thr * (double)__uint_as_float(s_max);
+        for (int st = 0; st < ke - 1; ++st) {
+            for (int pj = 2 * wave + half; pj < ke / 2; pj += 2 * nw) {   // a half-wave per pair: 32 pairs at once
+                int rp, rq;
+                svd_pair(ke, st, pj, rp, rq);
+                if (rq >= k) continue;   // the dummy of an odd k
+                float *wp = W + rp * Ls, *wq = W + rq * Ls;
+                float sa = 0.0f, sb = 0.0f, sg = 0.0f;
+                for (int c = hl; c < L; c += 32) {
+                    const float x = wp[c], y = wq[c];
+                    sa = fmaf(x, x, sa);
+                    sb = fmaf(y, y, sb);
+                    sg = fmaf(x, y, sg);
+                }
+                sa = svd_half_sum(sa);
+                sb = svd_half_sum(sb);
+                sg = svd_half_sum(sg);
+                if (!svd_active((double)sa, (double)sb, (double)sg, lim)) continue;   // uniform in the half-wave
+                const double z = ((double)sb - (double)sa) / (2.0 * (double)sg);
+                const double t = (z >= 0.0 ? 1.0 : -1.0) / (fabs(z) + sqrt(1.0 + z * z));
+                const double cd = 1.0 / sqrt(1.0 + t * t);
+                const float cf = (float)cd, sf = (float)(cd * t);
+                if (hl == 0) atomicAdd(&s_cnt, 1);
+                for (int c = hl; c < L; c += 32) {
+                    const float x = wp[c], y = wq[c];
+                    wp[c] = cf * x - sf * y;
+                    wq[c] = sf * x + cf * y;
+                }
+                if (p.vectors) {
+                    float *vp = V + rp * Vs, *vq = V + rq * Vs;
+                    for (int c = hl; c < k; c += 32) {
+                        const float x = vp[c], y = vq[c];
+                        vp[c] = cf * x - sf * y;
+                        vq[c] = sf * x + cf * y;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        above = s_cnt;
+        sweeps = sweep + 1;
+        __syncthreads();
+        if (tid == 0) {
+            s_cnt = 0;
+            s_max = 0u;
+        }
+        __syncthreads();
+        if (above == 0) break;   // uniform: every thread read the same count
+    }
+    for (int i = wave; i < k; i += nw) {
+        const float *w = W + i * Ls;
+        float acc = 0.0f;
+        for (int c = lane; c < L; c += 64) acc = fmaf(w[c], w[c], acc);
+        acc = svd_wave_sum(acc);
+        if (lane == 0) nsq[i] = acc;
+    }
+    __syncthreads();
+    if (tid < k) {   // the order of svd_rank_kernel
+        const float vi = nsq[tid];
+        const bool ni = vi != vi;
+        int r = 0;
+        for (int j = 0; j < k; ++j) {
+            const float vj = nsq[j];
+            const bool nj = vj != vj;
+            const bool greater = (nj && !ni) || vj > vi, equal = (nj && ni) || vj == vi;
+            r += (greater || (equal && j < tid)) ? 1 : 0;
+        }
+        rank[tid] = r;
+        p.s[r] = __fsqrt_rn(vi);
+    }
+    if (tid == 0) {
+        p.out2[0] = above;   // 0 when converged; at the cap: the pairs rotated in the last sweep, each met once
+        p.out2[1] = sweeps;
+    }
+    if (!p.vectors) return;
+    __syncthreads();
+    for (int idx = tid; idx < k * L; idx += blockDim.x) {   // the normalised rows of W: vt (k x L) when wide, else u (L x k)
+        const int i = p.wide ? idx / L : idx % k, c = p.wide ? idx % L : idx / k;
+        const float sv = __fsqrt_rn(nsq[i]);
+        const float v = sv == 0.0f ? 0.0f : __fdiv_rn(W[i * Ls + c], sv);
+        if (p.wide) p.vt[(size_t)rank[i] * L + c] = v;
+        else p.u[(size_t)c * k + rank[i]] = v;
+    }
+    for (int idx = tid; idx < k * k; idx += blockDim.x) {   // the rows of Vt: u (k x k) transposed when wide, else vt
+        const int i = p.wide ? idx % k : idx / k, c = p.wide ? idx / k : idx % k;
+        const float v = V[i * Vs + c];
+        if (p.wide) p.u[(size_t)c * k + rank[i]] = v;
+        else p.vt[(size_t)rank[i] * k + c] = v;
+    }
+}
+
+// rank[i] = position of row i in descending order of its norm (stable: the lower row first among equals); s[rank[i]] = the norm
+__global__ __launch_bounds__(256) void svd_rank_kernel(const float *normsq, size_t n, float *s, int *rank) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float vi = normsq[i];
+    const bool ni = vi != vi;
+    int r = 0;
+    for (size_t j = 0; j < n; ++j) {   // a NaN counts as larger than every number and equal to a NaN: the ranks are a permutation
+        const float vj = normsq[j];
+        const bool nj = vj != vj;
+        const bool greater = (nj && !ni) || vj > vi, equal = (nj && ni) || vj == vi;
+        r += (greater || (equal && j < i)) ? 1 : 0;
+    }
+    rank[i] = r;
+    s[r] = __fsqrt_rn(vi);
+}
+
+// dst[rank[i]][c] = src[i][c] for c < ncols, divided by the row's norm when normsq is given (+0.0f when that norm is 0)
+__global__ __launch_bounds__(256) void svd_gather_kernel(const float *src, size_t ld, size_t ncols, size_t n, const int *rank,
+                                                         const float *normsq, float *dst) {
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncols) return;
+    for (size_t i = blockIdx.y; i < n; i += gridDim.y) {
+        float v = src[i * ld + c];
+        if (normsq) {
+            const float sv = __fsqrt_rn(normsq[i]);
+            v = sv == 0.0f ? 0.0f : __fdiv_rn(v, sv);
+        }
+        dst[(size_t)rank[i] * ncols + c] = v;
+    }
+}
+
 // ---- host side ----
 
 int launch_small(const SmallArgs &p0) {
@@ -771,6 +1226,138 @@ int potrf_blocked(float *W, size_t n, int *info) {
         }
     }
     return NP_OK;
+}
+
+int svd_gather(const float *src, size_t ld, size_t ncols, size_t n, const int *rank, const float *normsq, float *dst) {
+    const dim3 grid(blocks_for(ncols, 256), (unsigned)(n < 4096 ? n : 4096));
+    svd_gather_kernel<<<grid, 256, 0, np::stream()>>>(src, ld, ncols, n, rank, normsq, dst);
+    NP_LAUNCH_CHECK("svd_gather_kernel");
+    return NP_OK;
+}
+
+// LDS floats of the small path, or 0 when the shape does not take it.  The same answer for np_svd and np_svdvals (room for Vt is
+// counted either way): both must take the same path to give the same s.
+size_t svd_small_floats(size_t k, size_t L) {
+    if (k > (size_t)kSvdP || g_svd_small_off) return 0;
+    const size_t f = k * (L | 1) + k * (k | 1) + 2 * k;
+    return f <= (size_t)kSmallLdsFloats ? f : 0;
+}
+
+int svd_small(const float *a, size_t k, size_t L, bool wide, float *u, float *s, float *vt, int *info_host) {
+    np::Scratch out2;
+    if (int rc = out2.alloc(2 * sizeof(int))) return rc;
+    SvdSmallArgs p = {};
+    p.a = a;
+    p.k = (int)k;
+    p.L = (int)L;
+    p.Ls = (int)(L | 1);
+    p.Vs = (int)(k | 1);
+    p.wide = wide ? 1 : 0;
+    p.vectors = u != nullptr ? 1 : 0;
+    p.cap = g_svd_max_sweeps > 0 ? g_svd_max_sweeps : kSvdSweepCap;
+    p.thr = (float)L * 1.1920928955078125e-7f;
+    p.u = u;
+    p.s = s;
+    p.vt = vt;
+    p.out2 = (int *)out2.ptr;
+    const size_t lds = svd_small_floats(k, L) * sizeof(float);
+    NP_HIP_CHECK(hipFuncSetAttribute((const void *)svd_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes));
+    svd_small_kernel<<<1, 1024, lds, np::stream()>>>(p);
+    NP_LAUNCH_CHECK("svd_small_kernel");
+    int host2[2] = {0, 0};
+    if (int rc = np_memcpy_d2h(host2, out2.ptr, sizeof(host2))) return rc;
+    *info_host = host2[0];
+    g_svd_last_sweeps = host2[1];
+    return NP_OK;
+}
+
+// u, vt null: singular values only (no Vt, no normalisation; W goes through the same rotations, so s has the same bits)
+int svd_impl(const char *who, const float *a, size_t m, size_t n, float *u, float *s, float *vt, int *info_host) {
+    *info_host = 0;
+    if (m == 0 || n == 0) return NP_OK;
+    if (m > kSvdMaxDim || n > kSvdMaxDim) return np::fail(NP_ERR_INVALID, "%s: m, n = %zu, %zu: larger than %zu", who, m, n, kSvdMaxDim);
+    hipStream_t st = np::stream();
+    const bool vectors = u != nullptr;
+    const bool wide = m < n;                       // the transposed problem: the rows of a are the "columns"
+    const size_t k = wide ? m : n, L = wide ? n : m;
+    if (svd_small_floats(k, L) > 0) return svd_small(a, k, L, wide, u, s, vt, info_host);
+    const size_t npad = (k + kSvdP - 1) / kSvdP * kSvdP, ldw = (L + 31) & ~(size_t)31;
+    const int nblk = (int)(npad / kSvdB), pairs = nblk / 2, steps = nblk - 1;
+    const int ntiles = (int)(ldw / 32);
+    int nsplit = (512 + pairs - 1) / pairs;
+    if (nsplit > kSvdMaxSplit) nsplit = kSvdMaxSplit;
+    if (nsplit > ntiles) nsplit = ntiles;
+    const int tps = (ntiles + nsplit - 1) / nsplit;
+    nsplit = (ntiles + tps - 1) / tps;
+    np::Scratch w, v, tmp, gpart, mbuf, flag, ctl, normsq, rank;
+    if (int rc = w.alloc(npad * ldw * sizeof(float))) return rc;
+    if (vectors)
+        if (int rc = v.alloc(npad * npad * sizeof(float))) return rc;
+    if (!wide || vectors)   // a^T on its way into W and the factor that leaves through a transpose
+        if (int rc = tmp.alloc(k * (wide ? k : L) * sizeof(float))) return rc;
+    if (int rc = gpart.alloc((size_t)pairs * nsplit * kSvdP * kSvdP * sizeof(float))) return rc;
+    if (int rc = mbuf.alloc((size_t)pairs * kSvdP * kSvdP * sizeof(float))) return rc;
+    if (int rc = flag.alloc((size_t)pairs * sizeof(int))) return rc;
+    if (int rc = ctl.alloc(sizeof(SvdCtl))) return rc;
+    if (int rc = normsq.alloc(npad * sizeof(float))) return rc;
+    if (int rc = rank.alloc(npad * sizeof(int))) return rc;
+    float *W = (float *)w.ptr, *V = (float *)v.ptr, *T = (float *)tmp.ptr;
+    if (int rc = np_memset0(W, npad * ldw * sizeof(float))) return rc;
+    if (wide) {
+        if (int rc = np_copy2d(W, ldw, a, n, n, m)) return rc;
+    } else {
+        if (int rc = np_transpose2d(a, T, 1, m, n)) return rc;
+        if (int rc = np_copy2d(W, ldw, T, m, m, n)) return rc;
+    }
+    if (vectors)
+        if (int rc = np_identity(V, npad)) return rc;
+    constexpr size_t eig_lds = 2 * (size_t)kSvdP * kSvdStr * sizeof(double);
+    // every call: the attribute belongs to the current device's copy of the kernel, and setting it costs nothing next to a sweep
+    NP_HIP_CHECK(hipFuncSetAttribute((const void *)svd_eig_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)eig_lds));
+    const float thr = (float)L * 1.1920928955078125e-7f;   // max(m, n) eps
+    const int wchunks = (int)((ldw + 127) / 128), vchunks = vectors ? (int)((npad + 127) / 128) : 0;
+    g_svd_last_sweeps = 0;
+    const int cap = g_svd_max_sweeps > 0 ? g_svd_max_sweeps : kSvdSweepCap;
+    bool converged = false;
+    unsigned long long last[2] = {0, 0};
+    for (int sweep = 0; sweep < cap && !converged; ++sweep) {
+        NP_HIP_CHECK(hipMemsetAsync(ctl.ptr, 0, sizeof(SvdCtl), st));
+        svd_rownorm_kernel<<<blocks_for(k, 4), 256, 0, st>>>(W, ldw, k, (float *)normsq.ptr, (SvdCtl *)ctl.ptr);
+        NP_LAUNCH_CHECK("svd_rownorm_kernel");
+        for (int step = 0; step < steps; ++step) {
+            svd_gram_kernel<<<dim3(pairs, nsplit), 256, 0, st>>>(W, ldw, nblk, step, tps, ntiles, nsplit, (float *)gpart.ptr);
+            NP_LAUNCH_CHECK("svd_gram_kernel");
+            svd_eig_kernel<<<pairs, 256, eig_lds, st>>>((const float *)gpart.ptr, nsplit, step, thr, (SvdCtl *)ctl.ptr,
+                                                        (float *)mbuf.ptr, (int *)flag.ptr);
+            NP_LAUNCH_CHECK("svd_eig_kernel");
+            svd_apply_kernel<<<dim3(pairs, wchunks + vchunks), 256, 0, st>>>(W, ldw, wchunks, V, npad, nblk, step,
+                                                                             (const float *)mbuf.ptr, (const int *)flag.ptr);
+            NP_LAUNCH_CHECK("svd_apply_kernel");
+        }
+        if (int rc = np_memcpy_d2h(last, ctl.ptr, sizeof(last))) return rc;   // the one host read of the sweep
+        converged = last[0] == 0;
+        g_svd_last_sweeps = sweep + 1;
+    }
+    if (!converged) *info_host = last[1] > (unsigned long long)INT_MAX ? INT_MAX : (last[1] > 0 ? (int)last[1] : 1);
+    NP_HIP_CHECK(hipMemsetAsync(ctl.ptr, 0, sizeof(SvdCtl), st));
+    svd_rownorm_kernel<<<blocks_for(k, 4), 256, 0, st>>>(W, ldw, k, (float *)normsq.ptr, (SvdCtl *)ctl.ptr);
+    NP_LAUNCH_CHECK("svd_rownorm_kernel");
+    svd_rank_kernel<<<blocks_for(k, 256), 256, 0, st>>>((const float *)normsq.ptr, k, s, (int *)rank.ptr);
+    NP_LAUNCH_CHECK("svd_rank_kernel");
+    if (vectors) {
+        const int *rk = (const int *)rank.ptr;
+        const float *nq = (const float *)normsq.ptr;
+        if (wide) {   // a = V_B S U_B^T for B = a^T: vt = the normalised rows of W, u = the transposed rows of Vt
+            if (int rc = svd_gather(W, ldw, L, k, rk, nq, vt)) return rc;
+            if (int rc = svd_gather(V, npad, k, k, rk, nullptr, T)) return rc;
+            if (int rc = np_transpose2d(T, u, 1, k, k)) return rc;
+        } else {
+            if (int rc = svd_gather(V, npad, k, k, rk, nullptr, vt)) return rc;
+            if (int rc = svd_gather(W, ldw, L, k, rk, nq, T)) return rc;
+            if (int rc = np_transpose2d(T, u, 1, k, L)) return rc;
+        }
+    }
+    return np_sync();   // the scratch goes back to the pool; info is known
 }
 
 }  // namespace
@@ -971,6 +1558,35 @@ int np_cholesky(const float *a, size_t n, float *out, int *info_host) {
         if (int rc = chol_tri(out, out, n, 1)) return rc;
     }
     return read_info((const int *)info.ptr, info_host);
+}
+
+int np_svd(const float *a, size_t m, size_t n, float *u, float *s, float *vt, int *info_host) {
+    if (int rc = np::ensure_init()) return rc;
+    if (!a || !u || !s || !vt || !info_host) return np::fail(NP_ERR_INVALID, "np_svd: null pointer");
+    return svd_impl("np_svd", a, m, n, u, s, vt, info_host);
+}
+
+int np_svdvals(const float *a, size_t m, size_t n, float *s, int *info_host) {
+    if (int rc = np::ensure_init()) return rc;
+    if (!a || !s || !info_host) return np::fail(NP_ERR_INVALID, "np_svdvals: null pointer");
+    return svd_impl("np_svdvals", a, m, n, nullptr, s, nullptr, info_host);
+}
+
+int np_debug_svd_max_sweeps(int sweeps) {
+    if (sweeps < 0) return np::fail(NP_ERR_INVALID, "np_debug_svd_max_sweeps: %d", sweeps);
+    g_svd_max_sweeps = sweeps;
+    return NP_OK;
+}
+
+int np_debug_svd_small_path(int on) {
+    g_svd_small_off = on ? 0 : 1;
+    return NP_OK;
+}
+
+int np_debug_svd_last_sweeps(int *host_sweeps) {
+    if (!host_sweeps) return np::fail(NP_ERR_INVALID, "np_debug_svd_last_sweeps: null pointer");
+    *host_sweeps = g_svd_last_sweeps;
+    return NP_OK;
 }
 
 }  // extern "C"

@@ -152,6 +152,10 @@ def _load_host():
     sig["NDArray_LU"] = (C.POINTER(_P), [_P])
     sig["NDArray_Solve"] = (_P, [_P, _P])
     sig["NDArray_Cholesky"] = (_P, [_P])
+    sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
+    sig["NDArray_MatrixRank"] = (_P, [_P, fp])
+    sig["NDArray_Norm"] = (_P, [_P, C.c_int])
+    sig["NDArray_Cond"] = (_P, [_P])
     sig["NDArray_Reshape"] = (_P, [_P, ip, C.c_int])
     sig["NDArray_Flatten"] = (_P, [_P])
     sig["NDArray_ExpandDim"] = (_P, [_P, _P])
@@ -755,6 +759,36 @@ class NDArray:
         h = _load_host()
         x, _ = NDArray._coerce(a)
         return NDArray._wrap(h.NDArray_Cholesky(x._p))
+
+    @staticmethod
+    def svd(a):              # numpower.c PHP_METHOD(svd): RETURN_3NDARRAY -> (U (m, m), S (k), V (n, n)); rows of V are right singular vectors
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        rtns = h.NDArray_SVD(x._p)
+        if not rtns:
+            _raise_pending(h)
+        out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(3))
+        _libc_free(C.cast(rtns, C.c_void_p))
+        return out
+
+    @staticmethod
+    def matrix_rank(a, tol=None):   # PHP_METHOD(matrix_rank): singular values > tol (default s_max * max(m, n) * FLT_EPSILON)
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        t = None if tol is None else C.byref(C.c_float(tol))
+        return NDArray._wrap(h.NDArray_MatrixRank(x._p, t))
+
+    @staticmethod
+    def norm(a, order=2):    # PHP_METHOD(norm): order 2 = the largest singular value
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        return NDArray._wrap(h.NDArray_Norm(x._p, int(order)))
+
+    @staticmethod
+    def cond(a):             # PHP_METHOD(cond): norm2(a) * norm2(inv(a))
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        return NDArray._wrap(h.NDArray_Cond(x._p))
 
     def copy(self):          # PHP_METHOD copy: NDArray_Copy on the array's own device
         return NDArray._wrap(_load_host().NDArray_Copy(self._p, C.cast(self._p, _P).contents.device))

@@ -519,6 +519,21 @@ CHOLESKY_EDITS = [
 ]
 EDITS += CHOLESKY_EDITS
 
+# ---- section 2b, SVD: the reference's NDArray_SVD calls cuSOLVER's gesvdj for a GPU array under --with-cuda and returns NULL
+# without it; the early-out at the top hands GPU operands to the device Jacobi SVD (np_svd) and replaces nothing.  With it
+# NDArray_MatrixRank, NDArray_L2Norm and NDArray_Cond work for GPU arrays through the reference's own code.  A list of its own:
+# its text runs as a program of its own (svd_bodies) ----
+SVD_EDITS = [
+    Edit("src/ndmath/linalg.c", "linalg.c:112 NDArray_SVD: GPU early-out",
+         r"^(?P<old>NDArray_SVD\(NDArray \*target\) \{)$",
+         "    /* numpower_amd 2b: a GPU operand is decomposed on the device (np_svd, ext/hip_linalg.c); CPU operands fall\n"
+         "     * through to the reference's LAPACK code below, untouched */\n"
+         "    if (NPH_LINALG_TAKES(target)) {\n"
+         "        return NPH_SVD(target);\n"
+         "    }", after=True),   # behind the function's opening line: indented by hand
+]
+EDITS += SVD_EDITS
+
 CONTEXTS = {
     "ndarray.c:1055-1060 NDArray_ToGPU: H2D copy": "float *tmp_gpu = 0; NDArray *target = 0;",
     "ndarray.c:1090 NDArray_ToCPU: D2H copy": "NDArray *rtn = 0, *target = 0;",
@@ -566,7 +581,7 @@ for _e in EDITS:
     if "`rtn = NDArray_" in _e.what:
         CONTEXTS[_e.what] = "NDArray *rtn = 0, *nda = 0, *ndb = 0;"
 for _e in EDITS:
-    if _e.what.endswith("GPU early-out") and _e not in LINALG_EDITS + CHOLESKY_EDITS:
+    if _e.what.endswith("GPU early-out") and _e not in LINALG_EDITS + CHOLESKY_EDITS + SVD_EDITS:
         CONTEXTS[_e.what] = "NDArray *nda = 0, *ndb = 0;" if _e.file == "src/logic.c" else "NDArray *a = 0, *b = 0;"
 CONTEXTS.update({
     "linalg.c:254 NDArray_Det: GPU early-out": "NDArray *a = 0;",
@@ -574,6 +589,7 @@ CONTEXTS.update({
     "linalg.c:634 NDArray_LU: GPU early-out": "NDArray *target = 0, *copied = 0, *p = 0, *l = 0, *u = 0; NDArray **rtns = 0;",
     "linalg.c:982-985 NDArray_Solve: GPU early-out": "NDArray *a = 0, *b = 0;",
     "linalg.c:1057 NDArray_Cholesky: GPU early-out": "NDArray *a = 0;",
+    "linalg.c:112 NDArray_SVD: GPU early-out": "NDArray *target = 0;",
 })
 
 HIP_M4_BLOCK = '''dnl ---- MI355X (gfx950) through numpower_amd: added by numpower_amd/tools/apply_with_hip.py ----
@@ -656,7 +672,7 @@ def snippet_check_source() -> str:
     return "\n".join(out)
 
 
-FAST_BINARY = [(e.what.split(" ")[1].rstrip(":"), e) for e in EDITS if e.what.endswith("GPU early-out") and e not in LINALG_EDITS + CHOLESKY_EDITS]   # ("NDArray_Add_Float", edit)
+FAST_BINARY = [(e.what.split(" ")[1].rstrip(":"), e) for e in EDITS if e.what.endswith("GPU early-out") and e not in LINALG_EDITS + CHOLESKY_EDITS + SVD_EDITS]   # ("NDArray_Add_Float", edit)
 
 
 def fast_path_program_source() -> str:
@@ -766,6 +782,92 @@ def cholesky_program_source() -> str:
          "    return reference_body();", "}", ""]
     o.append(_CHOLESKY_PROGRAM_MAIN)
     return "\n".join(o)
+
+
+def svd_program_source() -> str:
+    """A C99 PROGRAM around the text SVD_EDITS inserts into linalg.c: NDArray_SVD with the reference's signature, the inserted
+    text VERBATIM, then a stand-in for the reference's own code (LAPACK / cuSOLVER) that only counts how often it is reached.
+    Built and linked like linalg_bodies.
+
+        svd_bodies cpu    a CPU operand falls through to the stand-in, no device is touched
+        svd_bodies gpu    GPU operands never fall through: a known answer with the reference's shapes (U (m, m), S (k), V (n, n),
+                          zero padding), the 1-d throw, no device allocation leaks
+    """
+    (edit,) = SVD_EDITS
+    o = ["/* generated by tools/apply_with_hip.py: svd_program_source() — do not edit */",
+         "#include <math.h>", "#include <stdio.h>", "#include <stdlib.h>", "#include <string.h>", "",
+         "#define HAVE_NP_HIP 1", '#include "numpower_host.h"', '#include "hip_linalg.h"', "",
+         "static int g_fell_through;   /* calls that reached the reference's own code (the stand-in below) */",
+         "static NDArray **reference_body(void) { g_fell_through++; return NULL; }", "",
+         "static NDArray **patched_NDArray_SVD(NDArray *target) {", "#ifdef HAVE_NP_HIP", _indent(edit.new, ""), "#endif",
+         "    return reference_body();", "}", ""]
+    o.append(_SVD_PROGRAM_MAIN)
+    return "\n".join(o)
+
+
+_SVD_PROGRAM_MAIN = r"""static int g_failures;
+#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "svd_bodies: " __VA_ARGS__); fprintf(stderr, "\n"); g_failures++; } } while (0)
+
+static NDArray *make(const float *v, int rows, int cols, int gpu) {
+    int shape[2] = {rows, cols};
+    NDArray *h = NDArray_FromHostBuffer(v, shape, cols ? 2 : 1);
+    if (!gpu) return h;
+    NDArray *d = NDArray_ToGPU(h);
+    NDArray_FREE(h);
+    return d;
+}
+
+static int values(NDArray *a, float *out) {
+    NDArray *h = NDArray_ToCPU(a);
+    const int rc = h ? NDArray_CopyToHostBuffer(h, out) : -1;
+    if (h) NDArray_FREE(h);
+    return rc;
+}
+
+int main(int argc, char **argv) {
+    if (argc < 2 || (strcmp(argv[1], "cpu") && strcmp(argv[1], "gpu"))) {
+        fprintf(stderr, "usage: svd_bodies cpu|gpu\n");
+        return 2;
+    }
+    const int gpu = strcmp(argv[1], "gpu") == 0;
+    /* a 3 x 2 matrix with orthogonal columns of norm 6 and 2: S = {6, 2}, U (3, 3) with a zero third column, V (2, 2) */
+    const float a32[6] = {0, 6, -2, 0, 0, 0};
+    const float vec[3] = {1, 2, 3};
+    const long live0 = gpu ? NDArray_LiveDeviceAllocations() : 0;
+    NDArray *a = make(a32, 3, 2, gpu), *v1 = make(vec, 3, 0, gpu);
+    NDArray **r = patched_NDArray_SVD(a);
+    if (!gpu) {
+        CHECK(!r, "a CPU operand was computed on the device");
+        CHECK(g_fell_through == 1, "%d of 1 calls reached the reference's code", g_fell_through);
+    } else {
+        float u[9], s[2], v[4];
+        int ok = r && NDArray_NDIM(r[0]) == 2 && NDArray_SHAPE(r[0])[0] == 3 && NDArray_SHAPE(r[0])[1] == 3 &&
+                 NDArray_NDIM(r[1]) == 1 && NDArray_SHAPE(r[1])[0] == 2 && NDArray_NDIM(r[2]) == 2 &&
+                 NDArray_SHAPE(r[2])[0] == 2 && NDArray_SHAPE(r[2])[1] == 2;
+        CHECK(ok, "the result shapes are not U (3, 3), S (2), V (2, 2)");
+        ok = ok && values(r[0], u) == 0 && values(r[1], s) == 0 && values(r[2], v) == 0;
+        ok = ok && s[0] == 6.0f && s[1] == 2.0f;
+        for (int i = 0; ok && i < 3; ++i) {
+            ok = u[3 * i + 2] == 0.0f && !signbit(u[3 * i + 2]);
+            for (int j = 0; ok && j < 2; ++j)
+                ok = u[3 * i] * s[0] * v[j] + u[3 * i + 1] * s[1] * v[2 + j] == a32[2 * i + j];
+        }
+        CHECK(ok, "svd of the known matrix differs from the known factors");
+        CHECK(patched_NDArray_SVD(v1) == NULL && strcmp(numpower_host_last_error(), "Array must be at least two-dimensional") == 0,
+              "a 1-d operand did not raise the reference's message");
+        CHECK(g_fell_through == 0, "%d GPU calls fell through to the reference's code", g_fell_through);
+    }
+    if (r) {
+        for (int i = 0; i < 3; ++i) NDArray_FREE(r[i]);
+        free(r);
+    }
+    NDArray_FREE(a);
+    NDArray_FREE(v1);
+    if (gpu) CHECK(NDArray_LiveDeviceAllocations() == live0, "%ld device allocations leaked", NDArray_LiveDeviceAllocations() - live0);
+    printf("svd_bodies %s: %d calls reached the reference's own code, %d failures\n", argv[1], g_fell_through, g_failures);
+    return g_failures ? 1 : 0;
+}
+"""
 
 
 _CHOLESKY_PROGRAM_MAIN = r"""static int g_failures;

@@ -8,7 +8,14 @@ call, and numpy's fp32 solve on the host for comparison (the median of a few cal
 the same n and on the same matrix (A = X X^T / n + I), both timed with the copy that restores their input; TFLOP/s over
 n^3 / 3 and 2/3 n^3; the residual ||A - L L^T||_1 / ||A||_1 of np_cholesky's factor in float64 over eps = 2^-23 next to
 that of numpy's fp32 cholesky, and numpy's time on the host (the median of five calls after a warm-up), up to n = 8192.
---no-host leaves the host work out (a run under the profiler)."""
+--no-host leaves the host work out (a run under the profiler).
+
+--svd runs the SVD leg (profiles/linalg/svd_sweep.log): np_svd and np_svdvals on G + 2 sqrt(n) I (and a plain Gaussian
+4096 x 512), ms per call, sweeps taken, launches per call, numpy's fp32 svd on the host in the same run (median after a
+warm-up); it ends with the gate "the device call at n = 2048 is faster than numpy's".  --svd --accuracy prints instead the four
+metrics of tests/svd_family.py for every input of the bound tests next to their limits (profiles/linalg/svd_accuracy.log).
+The SVD leg imports tests/svd_family.py: the inputs, the metrics and the CPU emulator have that one definition, which the tests
+use too.  Sizes of up to 64 are timed twice, on the one-launch path and with it switched off (np_debug_svd_small_path)."""
 import argparse
 import ctypes as C
 import sys
@@ -22,9 +29,13 @@ from numpower_amd._lib import Timer, check, load
 ap = argparse.ArgumentParser()
 ap.add_argument("--sizes", default=None, help="default 64,256,1024,4096,8192,16384 (with --cholesky also 128)")
 ap.add_argument("--cholesky", action="store_true", help="the Cholesky leg: np_potrf against np_getrf")
+ap.add_argument("--svd", action="store_true", help="the SVD leg: np_svd / np_svdvals against numpy's svd on the host")
+ap.add_argument("--accuracy", action="store_true", help="with --svd: the accuracy table of the bound tests' inputs")
 ap.add_argument("--reps", type=int, default=0, help="0: as many as fit ~0.5 s per size (at least 3)")
 ap.add_argument("--no-host", action="store_true", help="skip numpy's solve on the host")
 args = ap.parse_args()
+if args.sizes is None and args.svd:
+    args.sizes = "8,32,64,256,1024,2048,4096"
 if args.sizes is None:
     args.sizes = "64,128,256,1024,4096,8192,16384" if args.cholesky else "64,256,1024,4096,8192,16384"
 
@@ -77,6 +88,90 @@ def residual_over_eps(a64, l):
     l64 = l.astype(np.float64)
     return float(np.abs(a64 - l64 @ l64.T).sum(axis=0).max() / np.abs(a64).sum(axis=0).max()) * 2.0 ** 23
 
+
+if args.svd:
+    from tests import svd_family as F
+
+    def svd_call(a, vals=False):
+        m, n = a.shape
+        k = min(m, n)
+        da, du, ds, dv = D.DeviceArray.from_host(a), D.DeviceArray((m, k)), D.DeviceArray((k,)), D.DeviceArray((k, n))
+        ih, sw = C.c_int(), C.c_int()
+
+        def run():
+            if vals:
+                check(lib.np_svdvals(da.ptr, m, n, ds.ptr, C.byref(ih)))
+            else:
+                check(lib.np_svd(da.ptr, m, n, du.ptr, ds.ptr, dv.ptr, C.byref(ih)))
+
+        return run, (da, du, ds, dv), ih, sw
+
+    if args.accuracy:
+        cases = [("shifted", F.shifted_square(n), None, 0) for n in F.SQUARE_SIZES]
+        cases += [("gaussian", F.gaussian(*s), None, 0) for s in F.RECT_SHAPES]
+        cases += [("scaled", F.scaled_case(*s), None, 0) for s in F.SCALED_SHAPES]
+        cases += [("rank%d" % r, F.rank_case(m, n, r), None, min(m, n) - r) for m, n, r in F.RANK_CASES]
+        cases += [("hadamard",) + F.hadamard_case(*s) + (0,) for s in F.HADAMARD_SHAPES]
+        print("figures in eps = 2^-23: rec / orthA / orthN / serr of the device, then of the limit (4 x the CPU emulator, floored at 2, up to "
+              "max(m, n) = 512; max(m, n) / 2 above)", flush=True)
+        for name, a, sigma, excluded in cases:
+            m, n = a.shape
+            run, bufs, ih, sw = svd_call(a)
+            run()
+            check(lib.np_debug_svd_last_sweeps(C.byref(sw)))
+            got = F.metrics(a, bufs[1].to_host().reshape(m, -1), bufs[2].to_host().reshape(-1), bufs[3].to_host().reshape(-1, n), sigma)
+            if max(m, n) <= 512:
+                ref = F.metrics(a, *F.jacobi_svd_emulated(a)[:3], sigma)
+                lim = {k: max(2.0, 4 * ref[k] / F.EPS) for k in ("rec", "orthA", "orthN", "serr")}
+            else:
+                lim = {k: max(m, n) / 2 for k in ("rec", "orthA", "orthN", "serr")}
+            keys = ("rec", "orthA", "orthN", "serr")
+            worst = max(got[k] / F.EPS / lim[k] for k in keys)
+            print("%-9s %5d x %-5d info %d sweeps %2d live %4d/%-4d  device %s  limit %s  worst ratio %.2f" %
+                  (name, m, n, ih.value, sw.value, got["live"], min(m, n) - excluded, " / ".join("%.1f" % (got[k] / F.EPS) for k in keys),
+                   " / ".join("%.1f" % lim[k] for k in keys), worst), flush=True)
+            for d in bufs:
+                d.free()
+        sys.exit(0)
+
+    print("%13s %10s %12s %7s %9s   %s" % ("m x n", "np_svd ms", "np_svdvals ms", "sweeps", "launches", "host numpy fp32 svd"), flush=True)
+    shapes = [(int(s), int(s)) for s in args.sizes.split(",")] + ([(500, 64), (4096, 512)] if len(args.sizes.split(",")) > 1 else [])
+    gate = None
+    for m, n in shapes:
+        a = F.shifted_square(n) if m == n else F.gaussian(m, n)
+        run, bufs, ih, sw = svd_call(a)
+        ms, per_call = timed(run, reps_for(run))
+        check(lib.np_debug_svd_last_sweeps(C.byref(sw)))
+        assert ih.value == 0
+        runv, bufsv, ihv, _ = svd_call(a, vals=True)
+        msv, _ = timed(runv, reps_for(runv))
+        host, med = "-", None
+        if not args.no_host:
+            np.linalg.svd(a, full_matrices=False)      # warm-up
+            ts = []
+            for _ in range(5 if n <= 1024 else 3):
+                h0 = time.perf_counter()
+                np.linalg.svd(a, full_matrices=False)
+                ts.append((time.perf_counter() - h0) * 1e3)
+            med = float(np.median(ts))
+            host = "%.3f ms (median of %d after a warm-up)" % (med, len(ts))
+        if (m, n) == (2048, 2048) and med is not None:
+            gate = (ms, med)
+        print("%6d x %-5d %10.3f %12.3f %7d %9d   %s" % (m, n, ms, msv, sw.value, per_call, host), flush=True)
+        if min(m, n) <= 64:   # the same shape on the blocked path
+            check(lib.np_debug_svd_small_path(0))
+            msb, per_b = timed(run, reps_for(run))
+            check(lib.np_debug_svd_last_sweeps(C.byref(sw)))
+            msvb, _ = timed(runv, reps_for(runv))
+            check(lib.np_debug_svd_small_path(1))
+            print("%6d x %-5d %10.3f %12.3f %7d %9d   (the one-launch path switched off)" % (m, n, msb, msvb, sw.value, per_b), flush=True)
+        for d in bufs + bufsv:
+            d.free()
+    if gate:
+        print("gate: np_svd at 2048 takes %.1f ms, numpy's fp32 svd on the host %.1f ms: %s" %
+              (gate[0], gate[1], "faster" if gate[0] < gate[1] else "NOT faster"), flush=True)
+        sys.exit(0 if gate[0] < gate[1] else 1)
+    sys.exit(0)
 
 if args.cholesky:
     print("%6s %10s %9s %9s %10s %9s %9s %7s %8s %8s   %s" % ("n", "potrf ms", "TFLOP/s", "launches", "getrf ms", "TFLOP/s", "launches",
