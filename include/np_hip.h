@@ -443,6 +443,36 @@ int np_cholesky(const float *a, size_t n, float *out, int *info_host);
 int np_svd(const float *a, size_t m, size_t n, float *u, float *s, float *vt, int *info_host);
 int np_svdvals(const float *a, size_t m, size_t n, float *s, int *info_host);
 
+/* ---- 2-D correlation and convolution (np_signal.hip; DESIGN.md "convolve2d") ------------------------
+ * scipy.signal.correlate2d(a, b, mode, boundary, fillvalue) for real fp32 arrays, ROW-MAJOR, and with flip != 0
+ * scipy.signal.convolve2d: what the loop of the reference's signal.c:152-207 computes, which the reference refuses for
+ * GPU arrays (signal.c:219-221).  mode and boundary take the reference's values (signal.h).
+ * np_correlate2d_shape: the result's extents, no device needed.  'full' ah + bh - 1, 'same' those of a (whichever operand
+ *   is larger), 'valid' |ah - bh| + 1, where one operand must be at least as large as the other in every dimension.
+ * np_correlate2d: the whole SciPy call.  In 'valid' mode an a that does not cover b changes places with it, and the
+ *   correlation computed that way is stored reversed along both axes, as SciPy returns it.  out: contiguous, of the extents
+ *   _shape reports; it must not overlap a or b.  fill_value is what lies outside a under NP_CONV_FILL.
+ * Fine print:
+ *   - every tap is multiplied and added: no coefficient and no fill cell is skipped because it is zero, so an Inf under a
+ *     0 tap gives NaN, as in SciPy.
+ *   - fixed order: each element starts from +0.0f and adds its taps with one fp32 fmaf each, in the order np_signal.hip
+ *     documents (footprint columns left to right, each top to bottom; windows beyond 15 x 15 in chunks of 16 x 16 taps,
+ *     chunks in row-major order).  The order is stated over the window as it lies on the image, so a convolution and the
+ *     correlation with the reversed window agree bit for bit; it does not depend on where the element sits in a tile, and
+ *     the result is bit-identical from run to run.
+ *   - boundary once per cell: fill / wrap / symm, also many image lengths away, is resolved when a cell of the image's
+ *     surroundings is staged, never per tap.
+ *   - windows up to 15 x 15 are staged once with their whole halo; larger ones of any size, larger than the image
+ *     included, run through LDS in chunks with the accumulators in registers.
+ * All extents >= 1.  NP_ERR_INVALID before any launch: a null pointer, an unknown mode or boundary, an extent (of an
+ * operand, or of a 'full' result) beyond INT_MAX, the shape of struct NDArray, and the 'valid' case in which neither operand
+ * covers the other.  Library stream, no scratch, no atomics. */
+typedef enum np_conv_mode { NP_CONV_VALID = 0, NP_CONV_SAME = 1, NP_CONV_FULL = 2 } np_conv_mode;
+typedef enum np_conv_boundary { NP_CONV_FILL = 0, NP_CONV_SYMM = 4, NP_CONV_WRAP = 8 } np_conv_boundary;   /* PAD, REFLECT, CIRCULAR */
+int np_correlate2d_shape(size_t ah, size_t aw, size_t bh, size_t bw, int mode, size_t *oh, size_t *ow);
+int np_correlate2d(const float *a, size_t ah, size_t aw, const float *b, size_t bh, size_t bw,
+                   int mode, int boundary, float fill_value, int flip, float *out);
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

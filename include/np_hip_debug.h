@@ -110,6 +110,12 @@ int np_debug_svd_last_sweeps(int *host_sweeps);
 /* testing / A-B: on = 0 sends every shape through the blocked path, on != 0 (the default) lets min(m, n) <= 64 with a row
  * length that fits LDS take the one-launch kernel.  Process-global. */
 int np_debug_svd_small_path(int on);
+/* tests / tools: the path the last np_correlate2d call of the process took: 1 = staged once (window up to 15 x 15), 2 = chunked,
+ * 0 = none yet.  A plain process global. */
+int np_debug_conv2d_last_path(int *host_path);
+/* testing / A-B: on = 0 sends every window through the chunked path, on != 0 (the default) lets windows up to 15 x 15 be staged
+ * once.  Process-global. */
+int np_debug_conv2d_staged_path(int on);
 
 #ifdef __cplusplus
 }

@@ -338,6 +338,20 @@ NDArray *NDArray_MatrixRank(NDArray *target, float *tol);
 NDArray *NDArray_Norm(NDArray *target, int type);
 NDArray *NDArray_Cond(NDArray *a);
 
+/* ---- 2-D correlation and convolution (host/numpower_signal.cpp; signal.c:217-303) ----
+ * NDArray_Correlate2D  scipy.signal.correlate2d(a, b, mode, boundary, fillvalue) of two 2-D GPU arrays, with flip != 0
+ *                      scipy.signal.convolve2d; mode 0 valid / 1 same / 2 full, boundary 0 fill / 4 symm / 8 wrap (signal.h).
+ *                      fill_value: NULL (0) or an array with one element on either device, read under boundary 0 only.
+ *                      Views are made contiguous; ext/hip_signal.c (NPH_Correlate2D, np_correlate2d) does the work.  A new
+ *                      GPU array of SciPy's shape: 'full' (ah + bh - 1, aw + bw - 1), 'same' a's, 'valid' |a - b| + 1 with
+ *                      the operands changing places when a does not cover b (DESIGN.md §3.11 lists where the
+ *                      reference's CPU wrapper differs).
+ * Errors: "NDArray::correlate2d inputs must be both 2-D arrays", "For 'valid' mode, one input must be at least as large as
+ * the other in every dimension", "fillValue must be a scalar or an array with one element.", "invalid mode.", for one
+ * operand on each device "correlate2d not implemented for GPU computation.", for two CPU operands "... only computes on
+ * the GPU". */
+NDArray *NDArray_Correlate2D(NDArray *a, NDArray *b, int mode, int boundary, NDArray *fill_value, int flip);
+
 #ifdef __cplusplus
 }
 #endif

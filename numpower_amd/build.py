@@ -30,7 +30,7 @@ LIBDIR = ROOT / "numpower_amd" / "lib"
 OBJDIR = ROOT / "build" / "obj"
 
 HIP_SOURCES = ["np_runtime.hip", "np_elementwise.hip", "np_fused_static.hip", "np_reduce.hip", "np_sgemm.hip", "np_layout.hip",
-               "np_select.hip", "np_comm.hip", "np_linalg.hip"]
+               "np_select.hip", "np_comm.hip", "np_linalg.hip", "np_signal.hip"]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{INCLUDE}", f"-I{CSRC}"]
 
 
@@ -133,7 +133,7 @@ def build_host(force: bool = False, verbose: bool = False) -> Path:
     if not srcs:
         return lib
     headers = list(INCLUDE.glob("*.h")) + list(HOST.glob("*.h"))
-    ext_objs = _ext_objects(EXT_GLUE + ["hip_math_drivers.c", "hip_fast.c", "hip_lazy.c", "hip_linalg.c"], force, verbose)
+    ext_objs = _ext_objects(EXT_GLUE + ["hip_math_drivers.c", "hip_fast.c", "hip_lazy.c", "hip_linalg.c", "hip_signal.c"], force, verbose)
     if force or _newer(lib, srcs + headers + ext_objs + [LIBDIR / "libnp_hip.so"]):
         if verbose:
             print("[build] compiling host layer", flush=True)
@@ -261,6 +261,31 @@ def build_svd_bodies(force: bool = False, verbose: bool = False) -> Path:
     return exe
 
 
+def build_signal_bodies(force: bool = False, verbose: bool = False) -> Path:
+    """The text tools/apply_with_hip.py inserts into the reference's NDArray_Correlate2D (correlate2d), wrapped
+    into a C99 program by the tool itself (signal_program_source) -> build/gen/signal_bodies.c ->
+    numpower_amd/lib/signal_bodies; -Wall -Wextra -Werror against numpower_host.h + hip_signal.h."""
+    exe = LIBDIR / "signal_bodies"
+    tool = ROOT / "tools" / "apply_with_hip.py"
+    gen = ROOT / "build" / "gen" / "signal_bodies.c"
+    deps = [tool, LIBDIR / "libnumpower_host.so"] + list(INCLUDE.glob("*.h")) + list(EXT.glob("*.h"))
+    if force or _newer(exe, deps):
+        if verbose:
+            print("[build] generating + compiling signal_bodies", flush=True)
+        import importlib.util
+        spec = importlib.util.spec_from_file_location("np_apply_with_hip", tool)
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules[spec.name] = mod
+        spec.loader.exec_module(mod)
+        gen.parent.mkdir(parents=True, exist_ok=True)
+        gen.write_text(mod.signal_program_source())
+        cc = shutil.which("gcc") or "gcc"
+        flags = [f for f in EXT_CFLAGS if f != "-fPIC"]
+        _run([cc, *flags, str(gen), "-o", str(exe), f"-L{LIBDIR}", "-lnumpower_host", "-lnp_hip",
+              "-Wl,-rpath,$ORIGIN"])
+    return exe
+
+
 def build_lazy_bodies(force: bool = False, verbose: bool = False) -> Path:
     """The text tools/apply_with_hip.py inserts for the pending chains (buffer_get's flush, the appenders of
     numpower.c's operator handler, static arithmetic methods and unary methods), wrapped by the tool itself into a C99 program
@@ -332,6 +357,7 @@ def build_all(force: bool = False, verbose: bool = False):
     build_linalg_bodies(force, verbose)
     build_cholesky_bodies(force, verbose)
     build_svd_bodies(force, verbose)
+    build_signal_bodies(force, verbose)
     oracle = build_oracle(force, verbose)
     build_loopback_rccl(force, verbose)
     return hip, host, oracle

@@ -24,18 +24,11 @@
 #include "np_ext_hooks.h"
 #include "np_hip.h"
 #include "numpower_host.h"
+#include "numpower_operand.h"
 
 namespace {
 
-// an operand made contiguous for the duration of one call
-struct Operand {
-    NDArray *arr = nullptr;
-    NDArray *owned = nullptr;
-    explicit Operand(NDArray *a) { arr = numpower_host_contiguous(a, &owned); }
-    ~Operand() {
-        if (owned) NDArray_FREE(owned);
-    }
-};
+using numpower_host::Operand;
 
 // the singular values of a contiguous 2-d GPU array on the host (np_svdvals), descending; false after a raised error
 bool singular_values(NDArray *a, const char *who, std::vector<float> &out) {

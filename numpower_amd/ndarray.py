@@ -152,6 +152,7 @@ def _load_host():
     sig["NDArray_LU"] = (C.POINTER(_P), [_P])
     sig["NDArray_Solve"] = (_P, [_P, _P])
     sig["NDArray_Cholesky"] = (_P, [_P])
+    sig["NDArray_Correlate2D"] = (_P, [_P, _P, C.c_int, C.c_int, _P, C.c_int])
     sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
     sig["NDArray_MatrixRank"] = (_P, [_P, fp])
     sig["NDArray_Norm"] = (_P, [_P, C.c_int])
@@ -789,6 +790,31 @@ class NDArray:
         h = _load_host()
         x, _ = NDArray._coerce(a)
         return NDArray._wrap(h.NDArray_Cond(x._p))
+
+    @staticmethod
+    def _signal2d(a, b, mode, boundary, fill_value, flip):
+        """PHP_METHOD(convolve2d) / (correlate2d), numpower.c:4399-4420 / 4460-4481: the first letter of `mode` (valid / same / full)
+        and of `boundary` (fill / wrap / symm) picks the flag.  A deviation: the PHP methods leave the flag at 0 (valid, fill)
+        for an empty string or an unknown letter; here that is an Error.  And fill_value is passed on (PHP parses it and passes
+        NULL)."""
+        h = _load_host()
+        modes, boundaries = {"v": 0, "s": 1, "f": 2}, {"f": 0, "s": 4, "w": 8}
+        if not isinstance(mode, str) or mode[:1] not in modes:
+            raise Error("mode must begin with 'v' (valid), 's' (same) or 'f' (full), not %r" % (mode,))
+        if not isinstance(boundary, str) or boundary[:1] not in boundaries:
+            raise Error("boundary must begin with 'f' (fill), 'w' (wrap) or 's' (symm), not %r" % (boundary,))
+        x, _ = NDArray._coerce(a)
+        y, _ = NDArray._coerce(b)
+        f, _ = NDArray._coerce(float(fill_value) if isinstance(fill_value, (int, float)) and not isinstance(fill_value, bool) else fill_value)
+        return NDArray._wrap(h.NDArray_Correlate2D(x._p, y._p, modes[mode[0]], boundaries[boundary[0]], f._p, flip))
+
+    @staticmethod
+    def convolve2d(a, b, mode, boundary, fill_value=0.0):    # numpower.c:4379: scipy.signal.convolve2d
+        return NDArray._signal2d(a, b, mode, boundary, fill_value, 1)
+
+    @staticmethod
+    def correlate2d(a, b, mode, boundary, fill_value=0.0):   # numpower.c:4440: scipy.signal.correlate2d
+        return NDArray._signal2d(a, b, mode, boundary, fill_value, 0)
 
     def copy(self):          # PHP_METHOD copy: NDArray_Copy on the array's own device
         return NDArray._wrap(_load_host().NDArray_Copy(self._p, C.cast(self._p, _P).contents.device))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """apply_with_hip.py — turn a NumPower checkout into a `--with-hip` tree (INTEGRATION.md sections 2a and 2b, as code).
 
-    python tools/apply_with_hip.py [--keep-cuda] <NumPower checkout> <output directory>
+    python tools/apply_with_hip.py [--keep-cuda] [--no-signal] <NumPower checkout> <output directory>
 
 Copies the checkout to <output directory>, applies every edit of INTEGRATION.md section 2a by ANCHORED regex and
 copies the glue (ext/*.c, ext/*.h, include/np_hip.h) to <output>/src/hip/.  Every edit names its file, the exact
@@ -534,6 +534,24 @@ SVD_EDITS = [
 ]
 EDITS += SVD_EDITS
 
+# ---- section 2b, correlate2d / convolve2d: the reference's NDArray_Correlate2D throws "correlate2d not implemented for GPU
+# computation." when either operand is a GPU array; the early-out sits in front of that throw and replaces nothing.  A list of
+# its own that is NOT part of EDITS: apply() takes it as `extra` (main() passes it unless --no-signal), applies it after EDITS and
+# reports it apart, so the counts of the 77 edits above stay what they were.  Its text runs as a program of its own (signal_bodies) ----
+SIGNAL_EDITS = [
+    Edit("src/ndmath/signal.c", "signal.c:41: <hip_signal.h>",
+         r"^(?P<old>#include \"\.\./initializers\.h\")$",
+         "#include <hip_signal.h>", after=True),
+    Edit("src/ndmath/signal.c", "signal.c:218 NDArray_Correlate2D: GPU early-out",
+         r"^(?P<old>NDArray_Correlate2D\(NDArray \*a, NDArray \*b, int mode, int boundary, NDArray\* fill_value, int flip\) \{)"
+         r"(?=\n[ \t]*if \(NDArray_DEVICE\(a\) == NDARRAY_DEVICE_GPU \|\| NDArray_DEVICE\(b\) == NDARRAY_DEVICE_GPU\) \{\n"
+         r"[ \t]*zend_throw_error\(NULL, \"correlate2d not implemented for GPU computation\.\"\);)",
+         "    /* numpower_amd 2b: two GPU operands are correlated on the device (np_correlate2d, ext/hip_signal.c); two CPU operands\n"
+         "     * fall through to the reference's loop below, one operand on each device to its throw, untouched */\n"
+         "    if (NPH_SIGNAL_TAKES(a, b)) return NPH_Correlate2D(a, b, mode, boundary, fill_value, flip);", after=True,
+         context="NDArray *a = 0, *b = 0, *fill_value = 0; int mode = 0, boundary = 0, flip = 0;"),   # behind the function's opening line: indented by hand
+]
+
 CONTEXTS = {
     "ndarray.c:1055-1060 NDArray_ToGPU: H2D copy": "float *tmp_gpu = 0; NDArray *target = 0;",
     "ndarray.c:1090 NDArray_ToCPU: D2H copy": "NDArray *rtn = 0, *target = 0;",
@@ -621,11 +639,11 @@ if test "$PHP_HIP" != "no"; then
   AC_DEFINE([HAVE_CUBLAS], [1], [a device back end is present (the C files gate every GPU branch on this name)])
   AC_DEFINE([HAVE_NP_HIP], [1], [the device back end is numpower_amd / MI355X])
   CFLAGS+=" -DNUMPOWER_NDARRAY_HEADER='\\"src/initializers.h\\"' -DNP_GPU_ALLOC_WIDE=1 "
-  NP_GPU_ALLOC_SOURCES="src/hip/gpu_alloc_hip.c src/hip/hip_math.c src/hip/hip_math_drivers.c src/hip/hip_fast.c src/hip/hip_lazy.c src/hip/hip_linalg.c src/hip/zend_hooks.c"
+  NP_GPU_ALLOC_SOURCES="src/hip/gpu_alloc_hip.c src/hip/hip_math.c src/hip/hip_math_drivers.c src/hip/hip_fast.c src/hip/hip_lazy.c src/hip/hip_linalg.c src/hip/hip_signal.c src/hip/zend_hooks.c"
 fi'''
 
 GLUE_FILES = ["ext/gpu_alloc_hip.c", "ext/hip_math.c", "ext/hip_math.h", "ext/hip_math_drivers.c", "ext/hip_fast.c",
-              "ext/hip_fast.h", "ext/hip_lazy.c", "ext/hip_lazy.h", "ext/hip_linalg.c", "ext/hip_linalg.h", "ext/zend_hooks.c", "ext/np_ext_hooks.h", "include/np_hip.h"]
+              "ext/hip_fast.h", "ext/hip_lazy.c", "ext/hip_lazy.h", "ext/hip_linalg.c", "ext/hip_linalg.h", "ext/hip_signal.c", "ext/hip_signal.h", "ext/zend_hooks.c", "ext/np_ext_hooks.h", "include/np_hip.h"]
 # not compiled in a --with-hip build: replaced wholesale by the glue
 REPLACED_BY_GLUE = ("src/gpu_alloc.c", "src/ndmath/cuda/")
 
@@ -635,15 +653,16 @@ for _e in EDITS:
 assert all(k in {e.what for e in EDITS} for k in CONTEXTS), "CONTEXTS names an edit that does not exist"
 
 
-def snippet_check_source() -> str:
-    """One C translation unit holding the HAVE_NP_HIP side of every statement-level edit, each in a function of its own
+def snippet_check_source(edits=None) -> str:
+    """(edits: the list to check, EDITS unless given — snippet_check_source(SIGNAL_EDITS) is the unit for the list apply() takes as
+    `extra`.)  One C translation unit holding the HAVE_NP_HIP side of every statement-level edit, each in a function of its own
     with the locals it uses declared as in the reference.  `gcc -fsyntax-only -Wall -Werror` on it (tests/
     test_apply_with_hip_cpu.py) proves that the new statements are well-typed against the C ABI and the glue headers —
     a wrong argument order, a missing status check's type, a misspelt entry point fail THERE, not in a maintainer's
     PHP build.  The only foreign declarations are the three reference symbols the new text itself calls."""
     out = ["/* generated by tools/apply_with_hip.py: snippet_check_source() */",
            "#include <stdio.h>", "#include <stddef.h>",
-           '#include "np_hip.h"', '#include "numpower_host.h"', '#include "hip_math.h"', '#include "hip_fast.h"', '#include "hip_lazy.h"', '#include "hip_linalg.h"',
+           '#include "np_hip.h"', '#include "numpower_host.h"', '#include "hip_math.h"', '#include "hip_fast.h"', '#include "hip_lazy.h"', '#include "hip_linalg.h"', *(['#include "hip_signal.h"'] if edits is not None else []),
            "void zend_throw_error(void *exception_ce, const char *format, ...);   /* Zend/zend_exceptions.h */",
            "typedef struct _zval_struct zval;                                        /* Zend/zend_types.h */",
            "NDArray *ZVAL_TO_NDARRAY(zval *obj);                                     /* numpower.c:89 */",
@@ -653,7 +672,7 @@ def snippet_check_source() -> str:
            "                    float (*operation)(NDArray *));                        /* src/ndarray.c:431 */",
            "NDArray *NDArray_Map(NDArray *array, float (*op)(float));                /* src/ndarray.h */",
            "float float_exp2(float val);                                             /* src/ndmath/double_math.h */", ""]
-    for k, e in enumerate(EDITS):
+    for k, e in enumerate(EDITS if edits is None else edits):
         if not e.context:
             continue
         ret = ("void *" if ("return NULL;" in e.new or "return NPH_" in e.new) else
@@ -803,6 +822,111 @@ def svd_program_source() -> str:
          "    return reference_body();", "}", ""]
     o.append(_SVD_PROGRAM_MAIN)
     return "\n".join(o)
+
+
+def signal_program_source() -> str:
+    """A C99 PROGRAM around the text SIGNAL_EDITS inserts into signal.c: NDArray_Correlate2D with the reference's signature, the
+    inserted text VERBATIM, then a stand-in for the reference's own code (its GPU throw and its CPU loop) that only counts how
+    often it is reached.  Built and linked like cholesky_bodies, against ext/hip_signal.h.
+
+        signal_bodies cpu    CPU operands fall through to the stand-in, no device is touched
+        signal_bodies gpu    GPU operands never fall through: known answers of both functions in all three modes (SciPy's 'full'
+                             shape, a fill value from either device, the 'valid' swap), every message, no device allocation leaks
+    """
+    edit = SIGNAL_EDITS[-1]
+    o = ["/* generated by tools/apply_with_hip.py: signal_program_source() — do not edit */",
+         "#include <stdio.h>", "#include <string.h>", "",
+         "#define HAVE_NP_HIP 1", '#include "numpower_host.h"', '#include "hip_signal.h"', "",
+         "static int g_fell_through;   /* calls that reached the reference's own code (the stand-in below) */",
+         "static NDArray *reference_body(void) { g_fell_through++; return NULL; }", "",
+         "static NDArray *patched_NDArray_Correlate2D(NDArray *a, NDArray *b, int mode, int boundary, NDArray* fill_value, int flip) {",
+         "#ifdef HAVE_NP_HIP", _indent(edit.new, ""), "#endif",
+         "    (void) mode; (void) boundary; (void) fill_value; (void) flip;", "    return reference_body();", "}", ""]
+    o.append(_SIGNAL_PROGRAM_MAIN)
+    return "\n".join(o)
+
+
+_SIGNAL_PROGRAM_MAIN = r"""static int g_failures;
+#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "signal_bodies: " __VA_ARGS__); fprintf(stderr, "\n"); g_failures++; } } while (0)
+
+static NDArray *make(const float *v, int rows, int cols, int gpu) {
+    int shape[2] = {rows, cols};
+    NDArray *h = NDArray_FromHostBuffer(v, shape, cols ? 2 : 1);
+    if (!gpu) return h;
+    NDArray *d = NDArray_ToGPU(h);
+    NDArray_FREE(h);
+    return d;
+}
+
+/* r is freed here; true when it has the shape rows x cols and exactly the values of want */
+static int is(NDArray *r, int rows, int cols, const float *want) {
+    float got[16];
+    int ok = r && NDArray_NDIM(r) == 2 && NDArray_SHAPE(r)[0] == rows && NDArray_SHAPE(r)[1] == cols && rows * cols <= 16;
+    NDArray *h = ok ? NDArray_ToCPU(r) : NULL;
+    ok = ok && h && NDArray_CopyToHostBuffer(h, got) == 0;
+    for (int i = 0; ok && i < rows * cols; ++i) ok = got[i] == want[i];
+    if (h) NDArray_FREE(h);
+    if (r) NDArray_FREE(r);
+    return ok;
+}
+
+static int raised(NDArray *r, const char *message) {
+    if (r) NDArray_FREE(r);
+    return r == NULL && strcmp(numpower_host_last_error(), message) == 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc < 2 || (strcmp(argv[1], "cpu") && strcmp(argv[1], "gpu"))) {
+        fprintf(stderr, "usage: signal_bodies cpu|gpu\n");
+        return 2;
+    }
+    const int gpu = strcmp(argv[1], "gpu") == 0;
+    enum { VALID = 0, SAME = 1, FULL = 2, PAD = 0, REFLECT = 4, CIRCULAR = 8 };   /* signal.h:16-22 */
+    const float a33[9] = {1, 2, 3, 4, 5, 6, 7, 8, 9}, b22[4] = {1, 2, 3, 4}, row[4] = {1, 1, 1, 1}, ten = 10, two[2] = {1, 2};
+    const long live0 = gpu ? NDArray_LiveDeviceAllocations() : 0;
+    NDArray *a = make(a33, 3, 3, gpu), *b = make(b22, 2, 2, gpu), *r14 = make(row, 1, 4, gpu), *v4 = make(row, 4, 0, gpu);
+    NDArray *fill_d = make(&ten, 1, 1, gpu), *fill_h = make(&ten, 1, 1, 0), *fill2 = make(two, 1, 2, 0);
+    if (!gpu) {
+        CHECK(patched_NDArray_Correlate2D(a, b, VALID, PAD, NULL, 0) == NULL, "CPU operands were computed on the device");
+        CHECK(g_fell_through == 1, "%d of 1 calls reached the reference's code", g_fell_through);
+    } else {
+        const float corr_valid[4] = {37, 47, 67, 77}, conv_valid[4] = {23, 33, 53, 63};
+        const float conv_full[16] = {1, 4, 7, 6, 7, 23, 33, 24, 19, 53, 63, 42, 21, 52, 59, 36};
+        const float corr_same10[9] = {37, 47, 81, 67, 77, 93, 93, 96, 99}, corr_same0[9] = {37, 47, 21, 67, 77, 33, 23, 26, 9};
+        const float corr_wrap[9] = {37, 47, 39, 67, 77, 69, 34, 44, 36}, corr_symm[9] = {37, 47, 51, 67, 77, 81, 76, 86, 90};
+        CHECK(is(patched_NDArray_Correlate2D(a, b, VALID, PAD, NULL, 0), 2, 2, corr_valid), "correlate2d 'valid'");
+        CHECK(is(patched_NDArray_Correlate2D(a, b, VALID, PAD, NULL, 1), 2, 2, conv_valid), "convolve2d 'valid'");
+        /* the smaller operand first: SciPy swaps, a convolution is unchanged, a correlation comes out reversed */
+        CHECK(is(patched_NDArray_Correlate2D(b, a, VALID, PAD, NULL, 1), 2, 2, conv_valid), "convolve2d 'valid', swapped");
+        const float corr_swapped[4] = {77, 67, 47, 37};
+        CHECK(is(patched_NDArray_Correlate2D(b, a, VALID, PAD, NULL, 0), 2, 2, corr_swapped), "correlate2d 'valid', swapped");
+        CHECK(is(patched_NDArray_Correlate2D(a, b, FULL, PAD, NULL, 1), 4, 4, conv_full), "convolve2d 'full' (4 x 4, not the shape of a)");
+        CHECK(is(patched_NDArray_Correlate2D(a, b, SAME, PAD, NULL, 0), 3, 3, corr_same0), "correlate2d 'same', fill 0");
+        CHECK(is(patched_NDArray_Correlate2D(a, b, SAME, PAD, fill_d, 0), 3, 3, corr_same10), "correlate2d 'same', fill 10 from the GPU");
+        CHECK(is(patched_NDArray_Correlate2D(a, b, SAME, PAD, fill_h, 0), 3, 3, corr_same10), "correlate2d 'same', fill 10 from the CPU");
+        CHECK(is(patched_NDArray_Correlate2D(a, b, SAME, CIRCULAR, fill_d, 0), 3, 3, corr_wrap), "correlate2d 'same', wrap");
+        CHECK(is(patched_NDArray_Correlate2D(a, b, SAME, REFLECT, fill2, 0), 3, 3, corr_symm), "correlate2d 'same', symm (fill_value is not looked at)");
+        /* 'same' never swaps: the result is shaped like the first operand, here the smaller one */
+        const float same_small[4] = {23, 33, 53, 63};
+        CHECK(is(patched_NDArray_Correlate2D(b, a, SAME, PAD, NULL, 1), 2, 2, same_small), "convolve2d 'same' with the larger operand second");
+        CHECK(raised(patched_NDArray_Correlate2D(a, v4, SAME, PAD, NULL, 0), "NDArray::correlate2d inputs must be both 2-D arrays"),
+              "a 1-d operand did not raise the reference's message");
+        CHECK(raised(patched_NDArray_Correlate2D(a, r14, VALID, PAD, NULL, 0),
+                     "For 'valid' mode, one input must be at least as large as the other in every dimension"),
+              "3 x 3 against 1 x 4 in 'valid' mode did not raise the reference's message");
+        CHECK(raised(patched_NDArray_Correlate2D(a, b, SAME, PAD, fill2, 0), "fillValue must be a scalar or an array with one element."),
+              "a fill value of two elements did not raise the reference's message");
+        CHECK(raised(patched_NDArray_Correlate2D(a, b, 3, PAD, NULL, 0), "invalid mode."), "mode 3 did not raise the reference's message");
+        CHECK(g_fell_through == 0, "%d GPU calls fell through to the reference's code", g_fell_through);
+    }
+    NDArray *all[] = {a, b, r14, v4, fill_d, fill_h, fill2};
+    for (size_t i = 0; i < sizeof(all) / sizeof(all[0]); ++i)
+        if (all[i]) NDArray_FREE(all[i]);
+    if (gpu) CHECK(NDArray_LiveDeviceAllocations() == live0, "%ld device allocations leaked", NDArray_LiveDeviceAllocations() - live0);
+    printf("signal_bodies %s: %d calls reached the reference's own code, %d failures\n", argv[1], g_fell_through, g_failures);
+    return g_failures ? 1 : 0;
+}
+"""
 
 
 _SVD_PROGRAM_MAIN = r"""static int g_failures;
@@ -1987,16 +2111,23 @@ def check_tree(out: Path, raw: bool = True):
     return problems
 
 
-def apply(checkout: Path, out: Path, keep_cuda: bool = False):
-    """-> {edit description: times applied}.  Raises PatchError on any anchor problem or leftover CUDA name."""
+class Applied(dict):
+    """{edit description: times applied} for EDITS; .extra holds the same for the edits given as `extra`."""
+    extra: dict
+
+
+def apply(checkout: Path, out: Path, keep_cuda: bool = False, extra=()):
+    """-> {edit description: times applied} for EDITS; the edits of `extra` (SIGNAL_EDITS) are applied after them, file by file,
+    and reported in the result's .extra.  Raises PatchError on any anchor problem or leftover CUDA name."""
     if out.exists():
         raise PatchError("%s exists; give a fresh output directory" % out)
     if not (checkout / "numpower.c").exists() or not (checkout / "config.m4").exists():
         raise PatchError("%s does not look like a NumPower checkout (numpower.c / config.m4 missing)" % checkout)
     shutil.copytree(checkout, out, ignore=shutil.ignore_patterns(".git"))
-    applied = {}
+    applied = Applied()
+    applied.extra = {}
     by_file = {}
-    for e in EDITS:
+    for e in EDITS + list(extra):
         by_file.setdefault(e.file, []).append(e)
     for file, edits in by_file.items():
         path = out / file
@@ -2005,7 +2136,7 @@ def apply(checkout: Path, out: Path, keep_cuda: bool = False):
         text = path.read_text()
         for e in edits:
             text, n = apply_edit(text, e, keep_cuda)
-            applied[e.what] = n
+            (applied if e in EDITS else applied.extra)[e.what] = n
         path.write_text(text)
     (out / "src" / "hip").mkdir(parents=True, exist_ok=True)
     for g in GLUE_FILES:
@@ -2019,19 +2150,20 @@ def apply(checkout: Path, out: Path, keep_cuda: bool = False):
 
 def main(argv):
     keep_cuda = "--keep-cuda" in argv
-    argv = [a for a in argv if a != "--keep-cuda"]
+    extra = [] if "--no-signal" in argv else SIGNAL_EDITS
+    argv = [a for a in argv if a not in ("--keep-cuda", "--no-signal")]
     if len(argv) != 3:
         print(__doc__, file=sys.stderr)
         return 2
     try:
-        applied = apply(Path(argv[1]).resolve(), Path(argv[2]).resolve(), keep_cuda)
+        applied = apply(Path(argv[1]).resolve(), Path(argv[2]).resolve(), keep_cuda, extra=extra)
     except PatchError as e:
         print("apply_with_hip: %s" % e, file=sys.stderr)
         return 2
-    for what, n in applied.items():
+    for what, n in list(applied.items()) + list(applied.extra.items()):
         print("applied x%d  %s" % (n, what))
     print("%d edits in %d files; glue in src/hip/.  Next: phpize && ./configure --with-hip=<dir of libnp_hip.so> && make"
-          % (len(applied), len({e.file for e in EDITS})))
+          % (len(applied) + len(applied.extra), len({e.file for e in EDITS + extra})))
     return 0
 
 
