@@ -1,5 +1,5 @@
 /*
- * hip_linalg.c — the device side of NDArray_Det / Inverse / LU / Solve / Cholesky / SVD (hip_linalg.h).  Compiled into a --with-hip tree
+ * hip_linalg.c — the device side of NDArray_Det / Inverse / LU / Solve / Cholesky / SVD / Eig (hip_linalg.h).  Compiled into a --with-hip tree
  * against the reference's headers (-DNUMPOWER_NDARRAY_HEADER='"src/initializers.h"') and into libnumpower_host.so
  * against include/numpower_host.h; it uses only what both declare, with one switch: the reference's arrays take ownership of
  * an emalloc'd shape and its result vectors are emalloc'd, the host library copies shapes and hands out malloc'd vectors.
@@ -193,5 +193,48 @@ NDArray **NPH_SVD(NDArray *a) {
     rtns[0] = u;
     rtns[1] = s;
     rtns[2] = v;
+    return rtns;
+}
+
+NDArray **NPH_Eig(NDArray *a) {
+    if (a == NULL) return NULL;
+    if (NDArray_NDIM(a) != 2 || NDArray_SHAPE(a)[0] != NDArray_SHAPE(a)[1]) {   /* linalg.c:796-799 */
+        np_ext_throw("Error: Input matrix is not square.\n");
+        return NULL;
+    }
+    if (!on_gpu(a)) return NULL;
+    const int n = NDArray_SHAPE(a)[0];
+    int asymmetric = 0;
+    if (np_symmetry_mismatch(NDArray_FDATA(a), (size_t) n, &asymmetric) != NP_OK) {
+        np_ext_throw_last();
+        return NULL;
+    }
+    if (asymmetric) {   /* np_eigh would answer from the lower triangle alone: a wrong answer to the question that was asked */
+        np_ext_throw("eig: the matrix is not symmetric; the device solver is a symmetric eigensolver (real eigenvalues, "
+                     "orthonormal eigenvectors), a general matrix goes through ->cpu() and the reference's own LAPACK path");
+        return NULL;
+    }
+    /* the reference's shapes and order (linalg.c:800-837): rtn[0] the eigenvalues (n), rtn[1] the eigenvectors (n, n),
+     * eigenvector j in column j */
+    NDArray *w = zeros_on_gpu(1, n, 0), *v = zeros_on_gpu(2, n, n);
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 2);
+    int ok = w != NULL && v != NULL && rtns != NULL;
+    int info = 0;
+    if (ok && np_eigh(NDArray_FDATA(a), (size_t) n, NDArray_FDATA(w), NDArray_FDATA(v), &info) != NP_OK) {
+        np_ext_throw_last();
+        ok = 0;
+    }
+    if (ok && info > 0) {   /* unlike the SVD's factors, a half-converged eigendecomposition answers nothing */
+        np_ext_throw("eig: the Jacobi iteration reached its sweep cap before every off-diagonal pair fell under the tolerance");
+        ok = 0;
+    }
+    if (!ok) {
+        if (w != NULL) NDArray_FREE(w);
+        if (v != NULL) NDArray_FREE(v);
+        if (rtns != NULL) NPH_RELEASE(rtns);
+        return NULL;
+    }
+    rtns[0] = w;
+    rtns[1] = v;
     return rtns;
 }

@@ -22,6 +22,10 @@
  *
  * (NDArray_MatrixRank, NDArray_L2Norm and NDArray_Cond are host code over NDArray_SVD and work for GPU arrays with it.)
  *
+ * and, only under the tool's --eig, one into NDArray_Eig, whose GPU branch throws "GPU eig currently unavailable":
+ *
+ *     NDArray_Eig      behind its squareness check, before its first allocation   return NPH_Eig(a);
+ *
  * each guarded by `#ifdef HAVE_NP_HIP` and NPH_LINALG_TAKES: CPU operands fall through to the reference's LAPACK code.
  * The cuda_det_float / cuda_matrix_float_inverse stubs of hip_math.c are never reached in such a tree.
  *
@@ -59,6 +63,11 @@ struct NDArray *NPH_Cholesky(struct NDArray *a);
  * as on the reference's CPU path), +0.0f elsewhere, so U diag(S, 0) V = a.  1-d: "Array must be at least two-dimensional";
  * other ranks are refused (the reference reads the first two extents). */
 struct NDArray **NPH_SVD(struct NDArray *a);
+/* the vector {eigenvalues (n), eigenvectors (n, n)} of a SYMMETRIC a, allocated as NPH_SVD allocates its own: the order and
+ * shapes of the reference's CPU path (linalg.c:800-837), eigenvalues ascending, eigenvector j in column j (np_eigh).  Not 2-d
+ * or not square: "Error: Input matrix is not square.\n"; a[i][j] != a[j][i] anywhere: refused, the message says that the device
+ * solver is a symmetric eigensolver and that a general matrix goes through ->cpu(); the sweep cap reached: a message that names it. */
+struct NDArray **NPH_Eig(struct NDArray *a);
 
 #ifdef __cplusplus
 }

@@ -110,6 +110,11 @@ int np_debug_svd_last_sweeps(int *host_sweeps);
 /* testing / A-B: on = 0 sends every shape through the blocked path, on != 0 (the default) lets min(m, n) <= 64 with a row
  * length that fits LDS take the one-launch kernel.  Process-global. */
 int np_debug_svd_small_path(int on);
+/* the same three for np_eigh / np_eigvalsh: the sweep cap (0 = the default, 60), the sweeps the last call took (the converged
+ * one, which rotates nothing, included), and on = 0 sending n <= 64 through the blocked path too.  Process-global. */
+int np_debug_eigh_max_sweeps(int sweeps);
+int np_debug_eigh_last_sweeps(int *host_sweeps);
+int np_debug_eigh_small_path(int on);
 /* tests / tools: the path the last np_correlate2d call of the process took: 1 = staged once (window up to 15 x 15), 2 = chunked,
  * 0 = none yet.  A plain process global. */
 int np_debug_conv2d_last_path(int *host_path);

@@ -338,6 +338,15 @@ NDArray *NDArray_MatrixRank(NDArray *target, float *tol);
 NDArray *NDArray_Norm(NDArray *target, int type);
 NDArray *NDArray_Cond(NDArray *a);
 
+/* ---- symmetric eigendecomposition (host/numpower_linalg.cpp; linalg.c:795-838) ----
+ * NDArray_Eig  malloc'd vector {eigenvalues (n) ascending, eigenvectors (n, n), eigenvector j in column j}: the order and shapes
+ *              of the reference's CPU path.  GPU operands only, views made contiguous; the device Jacobi eigensolver (np_eigh)
+ *              does the work, and it is a SYMMETRIC eigensolver: a matrix with a[i][j] != a[j][i] anywhere is refused with a
+ *              message that says so (a general matrix goes through ->cpu() in a patched tree).
+ * Errors: "Error: Input matrix is not square.\n" for a non-square or non-2-D operand; the not-symmetric refusal; a message
+ * that names the sweep cap when the iteration did not converge. */
+NDArray **NDArray_Eig(NDArray *a);
+
 /* ---- 2-D correlation and convolution (host/numpower_signal.cpp; signal.c:217-303) ----
  * NDArray_Correlate2D  scipy.signal.correlate2d(a, b, mode, boundary, fillvalue) of two 2-D GPU arrays, with flip != 0
  *                      scipy.signal.convolve2d; mode 0 valid / 1 same / 2 full, boundary 0 fill / 4 symm / 8 wrap (signal.h).

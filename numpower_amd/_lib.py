@@ -138,6 +138,9 @@ PROTOTYPES = {
     "np_cholesky": (C.c_int, [_f32p, C.c_size_t, _f32p, C.POINTER(C.c_int)]),
     "np_svd": (C.c_int, [_f32p, C.c_size_t, C.c_size_t, _f32p, _f32p, _f32p, C.POINTER(C.c_int)]),
     "np_svdvals": (C.c_int, [_f32p, C.c_size_t, C.c_size_t, _f32p, C.POINTER(C.c_int)]),
+    "np_eigh": (C.c_int, [_f32p, C.c_size_t, _f32p, _f32p, C.POINTER(C.c_int)]),
+    "np_eigvalsh": (C.c_int, [_f32p, C.c_size_t, _f32p, C.POINTER(C.c_int)]),
+    "np_symmetry_mismatch": (C.c_int, [_f32p, C.c_size_t, C.POINTER(C.c_int)]),
     "np_correlate2d_shape": (C.c_int, [C.c_size_t] * 4 + [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "np_correlate2d": (C.c_int, [_f32p, C.c_size_t, C.c_size_t, _f32p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int, _f32p]),
     "np_permute": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -157,6 +160,9 @@ PROTOTYPES = {
     "np_debug_svd_max_sweeps": (C.c_int, [C.c_int]),
     "np_debug_svd_last_sweeps": (C.c_int, [C.POINTER(C.c_int)]),
     "np_debug_svd_small_path": (C.c_int, [C.c_int]),
+    "np_debug_eigh_max_sweeps": (C.c_int, [C.c_int]),
+    "np_debug_eigh_last_sweeps": (C.c_int, [C.POINTER(C.c_int)]),
+    "np_debug_eigh_small_path": (C.c_int, [C.c_int]),
     "np_debug_conv2d_last_path": (C.c_int, [C.POINTER(C.c_int)]),
     "np_debug_conv2d_staged_path": (C.c_int, [C.c_int]),
     "np_clear_device_error": (C.c_int, [C.POINTER(C.c_uint)]),

@@ -261,6 +261,31 @@ def build_svd_bodies(force: bool = False, verbose: bool = False) -> Path:
     return exe
 
 
+def build_eig_bodies(force: bool = False, verbose: bool = False) -> Path:
+    """The text tools/apply_with_hip.py inserts into the reference's NDArray_Eig (eig), wrapped
+    into a C99 program by the tool itself (eig_program_source) -> build/gen/eig_bodies.c ->
+    numpower_amd/lib/eig_bodies; -Wall -Wextra -Werror against numpower_host.h + hip_linalg.h."""
+    exe = LIBDIR / "eig_bodies"
+    tool = ROOT / "tools" / "apply_with_hip.py"
+    gen = ROOT / "build" / "gen" / "eig_bodies.c"
+    deps = [tool, LIBDIR / "libnumpower_host.so"] + list(INCLUDE.glob("*.h")) + list(EXT.glob("*.h"))
+    if force or _newer(exe, deps):
+        if verbose:
+            print("[build] generating + compiling eig_bodies", flush=True)
+        import importlib.util
+        spec = importlib.util.spec_from_file_location("np_apply_with_hip", tool)
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules[spec.name] = mod
+        spec.loader.exec_module(mod)
+        gen.parent.mkdir(parents=True, exist_ok=True)
+        gen.write_text(mod.eig_program_source())
+        cc = shutil.which("gcc") or "gcc"
+        flags = [f for f in EXT_CFLAGS if f != "-fPIC"]
+        _run([cc, *flags, str(gen), "-o", str(exe), f"-L{LIBDIR}", "-lnumpower_host", "-lnp_hip",
+              "-Wl,-rpath,$ORIGIN"])
+    return exe
+
+
 def build_signal_bodies(force: bool = False, verbose: bool = False) -> Path:
     """The text tools/apply_with_hip.py inserts into the reference's NDArray_Correlate2D (correlate2d), wrapped
     into a C99 program by the tool itself (signal_program_source) -> build/gen/signal_bodies.c ->
@@ -357,6 +382,7 @@ def build_all(force: bool = False, verbose: bool = False):
     build_linalg_bodies(force, verbose)
     build_cholesky_bodies(force, verbose)
     build_svd_bodies(force, verbose)
+    build_eig_bodies(force, verbose)
     build_signal_bodies(force, verbose)
     oracle = build_oracle(force, verbose)
     build_loopback_rccl(force, verbose)

@@ -1069,6 +1069,405 @@ __global__ __launch_bounds__(256) void svd_gather_kernel(const float *src, size_
     }
 }
 
+// ---- symmetric eigensolver (np_eigh, np_eigvalsh) ----
+// Two-sided (classical) Jacobi, blocked over pairs of 32-row blocks with the SVD's tournament.  W is the symmetric matrix built
+// from the lower triangle of a, padded with zeros to a multiple of 64 (a zero row and column never rotates); Vt starts as I and
+// holds the eigenvectors as ROWS while iterating, so one row operation serves W and Vt.  Per step and block pair (I, J):
+//   eigh_eig_kernel       reads the 64 x 64 pivot block W[IJ, IJ] (its lower triangle) straight from W, counts the pairs above the
+//                         tolerance and, if there are any, diagonalises it in LDS in fp64: M (fp32, rounded once) and the diagonal D
+//   svd_apply_kernel      W[IJ, :] <- M W[IJ, :] and Vt[IJ, :] <- M Vt[IJ, :], all pairs (disjoint rows)
+//   eigh_colapply_kernel  W[:, IJ] <- W[:, IJ] M^T, all pairs (disjoint columns), in a launch of its own: a row half and a column
+//                         half of two pairs overlap.  The pivot block is written as diag(D) with exact zeros off it.
+// A pair (p, q) rotates when |w_pq| > kEighTol * scale, scale = the largest |entry| of the lower triangle of a, fixed at the start
+// of the call: diagonals may be zero or negative, so the SVD's sqrt(g_pp g_qq) has no meaning here.
+// n <= 64 takes eigh_small_kernel: the same 64 x 64 LDS solve on the whole (padded) matrix, sort, signs and output in ONE launch.
+constexpr int kEighSweepCap = 60;
+constexpr double kEighTol = 1.1920928955078125e-7;   // eps: relative to the largest entry, not to the pair's diagonals
+int g_eigh_max_sweeps = 0;                           // np_debug_eigh_max_sweeps
+int g_eigh_last_sweeps = 0;                          // np_debug_eigh_last_sweeps
+int g_eigh_small_off = 0;                            // np_debug_eigh_small_path(0)
+
+struct EighCtl {
+    unsigned long long above;        // pairs found above the tolerance by any workgroup of the sweep (0 = converged)
+    unsigned long long above_once;   // the same with every pair counted once
+    unsigned scalebits;              // bit pattern of the largest |entry| of the lower triangle (a NaN ends on top)
+    int pad;
+};
+
+__device__ __forceinline__ bool eigh_active(double g, double lim) { return fabs(g) > lim; }
+
+// W (npad x npad) from the lower triangle of a (n x n), zeros beyond n; the largest |entry| into ctl->scalebits
+__global__ __launch_bounds__(256) void eigh_pack_kernel(const float *a, size_t n, float *W, size_t npad, EighCtl *ctl) {
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned top = 0u;
+    if (c < npad) {
+        for (size_t r = blockIdx.y; r < npad; r += gridDim.y) {
+            float v = 0.0f;
+            if (r < n && c < n) v = r >= c ? a[r * n + c] : a[c * n + r];
+            W[r * npad + c] = v;
+            const unsigned b = __float_as_uint(v) & 0x7fffffffu;
+            top = b > top ? b : top;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned o = (unsigned)__shfl_down((int)top, off, 64);
+        top = o > top ? o : top;
+    }
+    if ((threadIdx.x & 63) == 0 && top != 0u) atomicMax(&ctl->scalebits, top);   // an integer max: order-independent
+}
+
+// Cyclic two-sided Jacobi on the symmetric G (fp64, LDS, row stride kSvdStr, 64 x 64 of which the leading k x k is the problem and
+// the rest zero) by 256 threads: the round-robin over its k rows (padded to an even count; the dummy never plays), up to 32 disjoint
+// rotations per step, rotations accumulated as rows of M when M is given.  At most `cap` sweeps; a sweep without a rotation ends
+// it.  Returns the sweeps taken (that last one included); *rot_last = the rotations of the last sweep.
+__device__ int eigh_solve64(double *G, double *M, int k, double lim, int cap, int *rot_last) {
+    __shared__ double cs_c[32], cs_s[32];
+    __shared__ int cs_p[32], cs_q[32];
+    __shared__ int s_rot;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_rot = 0;
+    __syncthreads();
+    const int ke = k + (k & 1);
+    int p = 0, q = 0, sweeps = 0, rot = 0;
+    bool mine = false;
+    for (int isw = 0; isw < cap; ++isw) {
+        for (int st = 0; st < ke - 1; ++st) {
+            if (tid < 32) {
+                double c = 1.0, s = 0.0, gpp = 0.0, gqq = 0.0, gpq = 0.0;
+                mine = false;
+                p = q = 0;
+                if (tid < ke / 2) {
+                    svd_pair(ke, st, tid, p, q);
+                    if (q < k) {   // else the dummy of an odd k
+                        gpp = G[p * kSvdStr + p];
+                        gqq = G[q * kSvdStr + q];
+                        gpq = G[p * kSvdStr + q];
+                        mine = eigh_active(gpq, lim);
+                    }
+                }
+                if (mine) {
+                    const double z = (gqq - gpp) / (2.0 * gpq);
+                    const double t = (z >= 0.0 ? 1.0 : -1.0) / (fabs(z) + sqrt(1.0 + z * z));
+                    c = 1.0 / sqrt(1.0 + t * t);
+                    s = c * t;
+                    atomicAdd(&s_rot, 1);
+                }
+                cs_c[tid] = c;
+                cs_s[tid] = s;
+                cs_p[tid] = p;
+                cs_q[tid] = q;
+            }
+            __syncthreads();
+            {   // rows p, q of G and of M
+                const int col = tid & 63;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int pr = (tid >> 6) + 4 * u;
+                    const double c = cs_c[pr], s = cs_s[pr];
+                    if (s != 0.0) {
+                        const int rp = cs_p[pr] * kSvdStr + col, rq = cs_q[pr] * kSvdStr + col;
+                        const double gp_ = G[rp], gq_ = G[rq];
+                        G[rp] = c * gp_ - s * gq_;
+                        G[rq] = s * gp_ + c * gq_;
+                        if (M) {
+                            const double mp_ = M[rp], mq_ = M[rq];
+                            M[rp] = c * mp_ - s * mq_;
+                            M[rq] = s * mp_ + c * mq_;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            {   // columns p, q of G
+                const int row = tid & 63;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int pr = (tid >> 6) + 4 * u;
+                    const double c = cs_c[pr], s = cs_s[pr];
+                    if (s != 0.0) {
+                        const int cp = row * kSvdStr + cs_p[pr], cq = row * kSvdStr + cs_q[pr];
+                        const double gp_ = G[cp], gq_ = G[cq];
+                        G[cp] = c * gp_ - s * gq_;
+                        G[cq] = s * gp_ + c * gq_;
+                    }
+                }
+            }
+            __syncthreads();
+            if (tid < 32 && mine) {
+                G[p * kSvdStr + q] = 0.0;
+                G[q * kSvdStr + p] = 0.0;
+            }
+        }
+        __syncthreads();
+        rot = s_rot;
+        sweeps = isw + 1;
+        __syncthreads();
+        if (tid == 0) s_rot = 0;
+        __syncthreads();
+        if (rot == 0) break;   // uniform: every thread read the same count
+    }
+    *rot_last = rot;
+    return sweeps;
+}
+
+// dynamic LDS: G and M, kSvdP x kSvdStr doubles each
+__global__ __launch_bounds__(256) void eigh_eig_kernel(const float *W, size_t ld, int nblk, int step, EighCtl *ctl, float *Mbuf,
+                                                       float *Dbuf, int *flag) {
+    extern __shared__ double eigh_sm[];
+    double *G = eigh_sm, *M = eigh_sm + kSvdP * kSvdStr;
+    __shared__ int s_cnt[2];
+    const int tid = threadIdx.x, pair = blockIdx.x;
+    int p, q;
+    svd_pair(nblk, step, pair, p, q);
+    for (int idx = tid; idx < kSvdP * kSvdP; idx += 256) {
+        const int r = idx >> 6, c = idx & 63;   // p < q: the block's lower triangle is a part of W's
+        const int hi = r > c ? r : c, lo = r > c ? c : r;
+        G[r * kSvdStr + c] = (double)W[svd_row(p, q, hi) * ld + svd_row(p, q, lo)];
+        M[r * kSvdStr + c] = r == c ? 1.0 : 0.0;
+    }
+    if (tid < 2) s_cnt[tid] = 0;
+    __syncthreads();
+    const double lim = kEighTol * (double)__uint_as_float(ctl->scalebits);
+    int all = 0, once = 0;
+    for (int idx = tid; idx < kSvdP * kSvdP; idx += 256) {
+        const int i = idx >> 6, j = idx & 63;
+        if (i < j && eigh_active(G[i * kSvdStr + j], lim)) {
+            ++all;
+            if (step == 0 || ((i < kSvdB) != (j < kSvdB))) ++once;   // rows of one block meet again in every step
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        all += __shfl_down(all, off, 64);
+        once += __shfl_down(once, off, 64);
+    }
+    if ((tid & 63) == 0) {
+        atomicAdd(&s_cnt[0], all);
+        atomicAdd(&s_cnt[1], once);
+    }
+    __syncthreads();
+    if (s_cnt[0] == 0) {   // uniform: nothing to rotate, both apply kernels skip the pair
+        if (tid == 0) flag[pair] = 0;
+        return;
+    }
+    if (tid == 0) {
+        atomicAdd(&ctl->above, (unsigned long long)s_cnt[0]);
+        atomicAdd(&ctl->above_once, (unsigned long long)s_cnt[1]);
+    }
+    // the call's own cap: a solve that stopped while still rotating would have its remaining off-diagonal mass zeroed below
+    // unseen.  Should it ever happen (it takes an input that does not converge at all), the sweep is reported as not converged.
+    int rot_last;
+    eigh_solve64(G, M, kSvdP, lim, kEighSweepCap, &rot_last);
+    if (tid == 0 && rot_last != 0) {
+        atomicAdd(&ctl->above, (unsigned long long)rot_last);
+        atomicAdd(&ctl->above_once, (unsigned long long)rot_last);
+    }
+    float *out = Mbuf + (size_t)pair * (kSvdP * kSvdP);
+    for (int idx = tid; idx < kSvdP * kSvdP; idx += 256) out[idx] = (float)M[(idx >> 6) * kSvdStr + (idx & 63)];
+    if (tid < kSvdP) Dbuf[(size_t)pair * kSvdP + tid] = (float)G[tid * kSvdStr + tid];
+    if (tid == 0) flag[pair] = 1;
+}
+
+// W[:, IJ] <- W[:, IJ] M^T for the block pair's 64 columns: a workgroup per pair and 128 rows, a wave per 32 rows.  The wave
+// stages its 32 x 64 tile in LDS with row-contiguous loads (2 x 128 bytes per row), multiplies on the MFMA and stores rows again;
+// the tile is read whole before anything is stored, and no other wave of the launch touches it.  The two waves whose rows are
+// the pair's own write the pivot block instead: diag(D), exact zeros off it.
+__global__ __launch_bounds__(256) void eigh_colapply_kernel(float *W, size_t ld, int nblk, int step, const float *Mbuf,
+                                                            const float *Dbuf, const int *flag) {
+    __shared__ float Ms[kSvdP * kSvdStr];
+    __shared__ float Ts[4][kSvdB * kSvdStr];
+    const int pair = blockIdx.x;
+    if (!flag[pair]) return;
+    int p, q;
+    svd_pair(nblk, step, pair, p, q);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float *Mg = Mbuf + (size_t)pair * (kSvdP * kSvdP);
+    for (int idx = tid; idx < kSvdP * kSvdP; idx += 256) Ms[(idx >> 6) * kSvdStr + (idx & 63)] = Mg[idx];
+    const size_t row0 = (size_t)blockIdx.y * 128 + (size_t)wave * 32;
+    const bool live = row0 < ld;   // ld is a multiple of 64: a wave's 32 rows are all there or none is
+    const int rb = (int)(row0 / kSvdB);
+    const bool pivot = rb == p || rb == q;
+    const size_t col = lane < kSvdB ? (size_t)p * kSvdB + lane : (size_t)q * kSvdB + (lane - kSvdB);
+    float *T = Ts[wave];
+    if (live && !pivot) {
+#pragma unroll 8
+        for (int rr = 0; rr < kSvdB; ++rr) T[rr * kSvdStr + lane] = W[(row0 + rr) * ld + col];
+    }
+    __syncthreads();
+    if (!live) return;
+    if (pivot) {
+        const int l0 = rb == p ? 0 : kSvdB;   // local index of the wave's first row
+        const float d = Dbuf[(size_t)pair * kSvdP + lane];
+        for (int rr = 0; rr < kSvdB; ++rr) W[(row0 + rr) * ld + col] = lane == l0 + rr ? d : 0.0f;
+        return;
+    }
+    const int i = lane & 31, kq = lane >> 5;
+    svd_v16f acc0, acc1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        acc0[r] = 0.0f;
+        acc1[r] = 0.0f;
+    }
+#pragma unroll
+    for (int kk = 0; kk < 32; ++kk) {   // out[r][j] = sum_k T[r][k] M[j][k]
+        const float x = T[i * kSvdStr + 2 * kk + kq];
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x, Ms[i * kSvdStr + 2 * kk + kq], acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x, Ms[(32 + i) * kSvdStr + 2 * kk + kq], acc1, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int lr = (r & 3) + 8 * (r >> 2) + 4 * kq;
+        W[(row0 + lr) * ld + (size_t)p * kSvdB + i] = acc0[r];
+        W[(row0 + lr) * ld + (size_t)q * kSvdB + i] = acc1[r];
+    }
+}
+
+// diag[i] = W[i][i] for i < n, or NaN everywhere when the scale of the call is not finite (non-finite input)
+__global__ __launch_bounds__(256) void eigh_diag_kernel(const float *W, size_t ld, size_t n, const EighCtl *ctl, float *diag) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool finite = (ctl->scalebits & 0x7f800000u) != 0x7f800000u;
+    diag[i] = finite ? W[i * ld + i] : __uint_as_float(0x7fc00000u);
+}
+
+// rank[i] = position of diag[i] in ascending order (stable: the lower index first among equals, -0.0f == +0.0f); w[rank[i]] = it
+__device__ __forceinline__ int eigh_rank_of(const float *diag, size_t n, size_t i) {
+    const float vi = diag[i];
+    const bool ni = vi != vi;
+    int r = 0;
+    for (size_t j = 0; j < n; ++j) {   // a NaN counts as larger than every number and equal to a NaN: the ranks are a permutation
+        const float vj = diag[j];
+        const bool nj = vj != vj;
+        const bool less = (ni && !nj) || vj < vi, equal = (nj && ni) || vj == vi;
+        r += (less || (equal && j < i)) ? 1 : 0;
+    }
+    return r;
+}
+
+__global__ __launch_bounds__(256) void eigh_rank_kernel(const float *diag, size_t n, float *w, int *rank) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int r = eigh_rank_of(diag, n, i);
+    rank[i] = r;
+    w[r] = diag[i];
+}
+
+// the sign rule for `rows` rows of length n (stride ld), a wave per row: neg[row] = 1 when the component of largest magnitude,
+// the first such in index order, is negative
+__device__ __forceinline__ void eigh_row_sign(const float *v, int n, int lane, int *neg_out) {
+    float best = -1.0f, val = 0.0f;   // the winner's magnitude and its signed value travel together: no lane reads another's
+    int at = 0x7fffffff;
+    for (int c = lane; c < n; c += 64) {
+        const float x = v[c], m = fabsf(x);
+        if (m > best) {   // strictly: the first index of a lane's own columns stays
+            best = m;
+            val = x;
+            at = c;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ob = __shfl_xor(best, off, 64), ov = __shfl_xor(val, off, 64);
+        const int oa = __shfl_xor(at, off, 64);
+        if (ob > best || (ob == best && oa < at)) {
+            best = ob;
+            val = ov;
+            at = oa;
+        }
+    }
+    if (lane == 0) *neg_out = val < 0.0f ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void eigh_sign_kernel(const float *V, size_t ld, size_t n, int *neg) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t row = (size_t)blockIdx.x * 4 + wave;
+    if (row >= n) return;
+    eigh_row_sign(V + row * ld, (int)n, lane, neg + row);
+}
+
+// dst[rank[i]][c] = +-V[i][c] for c < n: the rows of Vt in ascending order of their eigenvalue, the sign rule applied
+__global__ __launch_bounds__(256) void eigh_gather_kernel(const float *V, size_t ld, size_t n, const int *rank, const int *neg,
+                                                          float *dst) {
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    for (size_t i = blockIdx.y; i < n; i += gridDim.y) {
+        const float x = V[i * ld + c];
+        dst[(size_t)rank[i] * n + c] = neg[i] ? -x : x;
+    }
+}
+
+// any[0] = 1 when some i > j has a[i][j] != a[j][i] (two NaNs count as equal)
+__global__ __launch_bounds__(256) void symmetry_kernel(const float *a, size_t n, int *any) {
+    const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    bool bad = false;
+    for (size_t r = (size_t)blockIdx.y; r < n; r += gridDim.y) {
+        if (r <= c) continue;
+        const float x = a[r * n + c], y = a[c * n + r];
+        bad = bad || (x != y && !(x != x && y != y));
+    }
+    if (bad) atomicOr(any, 1);
+}
+
+// ---- small path: n <= 64 — the whole decomposition in ONE launch of one workgroup ----
+// W (padded with zeros to 64 x 64) and Vt live in LDS as the G and M of eigh_solve64, in fp64; the sweeps, the ascending stable
+// ranks, the sign rule and the transposed output follow in the same launch.
+struct EighSmallArgs {
+    const float *a;
+    int n, vectors, cap;
+    float *w, *v;
+    int *out2;   // out2[0] = info, out2[1] = sweeps taken
+};
+
+__global__ __launch_bounds__(256) void eigh_small_kernel(EighSmallArgs p) {
+    extern __shared__ double eigh_small_sm[];
+    double *G = eigh_small_sm, *M = p.vectors ? eigh_small_sm + kSvdP * kSvdStr : nullptr;
+    __shared__ float s_diag[kSvdP], s_vt[kSvdP * kSvdP];
+    __shared__ int s_rank[kSvdP], s_neg[kSvdP];
+    __shared__ unsigned s_scale;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = p.n;
+    if (tid == 0) s_scale = 0u;
+    __syncthreads();
+    unsigned top = 0u;
+    for (int idx = tid; idx < kSvdP * kSvdP; idx += 256) {
+        const int r = idx >> 6, c = idx & 63;
+        float v = 0.0f;
+        if (r < n && c < n) v = r >= c ? p.a[r * n + c] : p.a[c * n + r];
+        G[r * kSvdStr + c] = (double)v;
+        if (M) M[r * kSvdStr + c] = r == c ? 1.0 : 0.0;
+        const unsigned b = __float_as_uint(v) & 0x7fffffffu;
+        top = b > top ? b : top;
+    }
+    atomicMax(&s_scale, top);
+    __syncthreads();
+    const bool finite = (s_scale & 0x7f800000u) != 0x7f800000u;
+    const double lim = kEighTol * (double)__uint_as_float(s_scale);
+    int rot_last = 0;
+    const int sweeps = eigh_solve64(G, M, n, lim, p.cap, &rot_last);
+    if (tid < n) s_diag[tid] = finite ? (float)G[tid * kSvdStr + tid] : __uint_as_float(0x7fc00000u);
+    __syncthreads();
+    if (tid < n) {
+        const int r = eigh_rank_of(s_diag, (size_t)n, (size_t)tid);
+        s_rank[tid] = r;
+        p.w[r] = s_diag[tid];
+    }
+    if (tid == 0) {
+        p.out2[0] = rot_last;   // 0 when converged; at the cap: the pairs rotated in the last sweep
+        p.out2[1] = sweeps;
+    }
+    if (!p.vectors) return;
+    for (int idx = tid; idx < n * kSvdP; idx += 256) s_vt[idx] = (float)M[(idx >> 6) * kSvdStr + (idx & 63)];   // rounded once
+    __syncthreads();
+    for (int i = wave; i < n; i += 4) eigh_row_sign(s_vt + i * kSvdP, n, lane, &s_neg[i]);   // a wave per row of Vt
+    __syncthreads();
+    for (int idx = tid; idx < n * n; idx += 256) {
+        const int i = idx / n, c = idx % n;
+        const float x = s_vt[i * kSvdP + c];
+        p.v[(size_t)c * n + s_rank[i]] = s_neg[i] ? -x : x;
+    }
+}
+
 // ---- host side ----
 
 int launch_small(const SmallArgs &p0) {
@@ -1360,6 +1759,99 @@ int svd_impl(const char *who, const float *a, size_t m, size_t n, float *u, floa
     return np_sync();   // the scratch goes back to the pool; info is known
 }
 
+constexpr size_t kEighLds = 2 * (size_t)kSvdP * kSvdStr * sizeof(double);   // G and M
+
+int eigh_small(const float *a, size_t n, float *w, float *v, int *info_host) {
+    np::Scratch out2;
+    if (int rc = out2.alloc(2 * sizeof(int))) return rc;
+    EighSmallArgs p = {};
+    p.a = a;
+    p.n = (int)n;
+    p.vectors = v != nullptr ? 1 : 0;
+    p.cap = g_eigh_max_sweeps > 0 ? g_eigh_max_sweeps : kEighSweepCap;
+    p.w = w;
+    p.v = v;
+    p.out2 = (int *)out2.ptr;
+    NP_HIP_CHECK(hipFuncSetAttribute((const void *)eigh_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEighLds));
+    eigh_small_kernel<<<1, 256, kEighLds, np::stream()>>>(p);
+    NP_LAUNCH_CHECK("eigh_small_kernel");
+    int host2[2] = {0, 0};
+    if (int rc = np_memcpy_d2h(host2, out2.ptr, sizeof(host2))) return rc;
+    *info_host = host2[0];
+    g_eigh_last_sweeps = host2[1];
+    return NP_OK;
+}
+
+// v null: eigenvalues only (no Vt; W goes through the same rotations, so w has the same bits)
+int eigh_impl(const char *who, const float *a, size_t n, float *w, float *v, int *info_host) {
+    *info_host = 0;
+    if (n == 0) return NP_OK;
+    if (n > kSvdMaxDim) return np::fail(NP_ERR_INVALID, "%s: n = %zu: larger than %zu", who, n, kSvdMaxDim);
+    if (n <= (size_t)kSvdP && !g_eigh_small_off) return eigh_small(a, n, w, v, info_host);
+    hipStream_t st = np::stream();
+    const bool vectors = v != nullptr;
+    const size_t npad = (n + kSvdP - 1) / kSvdP * kSvdP;
+    const int nblk = (int)(npad / kSvdB), pairs = nblk / 2, steps = nblk - 1;
+    np::Scratch wm, vm, tmp, mbuf, dbuf, flag, ctl, diag, rank, neg;
+    if (int rc = wm.alloc(npad * npad * sizeof(float))) return rc;
+    if (vectors) {
+        if (int rc = vm.alloc(npad * npad * sizeof(float))) return rc;
+        if (int rc = tmp.alloc(n * n * sizeof(float))) return rc;   // the sorted rows of Vt on their way through a transpose
+        if (int rc = neg.alloc(n * sizeof(int))) return rc;
+    }
+    if (int rc = mbuf.alloc((size_t)pairs * kSvdP * kSvdP * sizeof(float))) return rc;
+    if (int rc = dbuf.alloc((size_t)pairs * kSvdP * sizeof(float))) return rc;
+    if (int rc = flag.alloc((size_t)pairs * sizeof(int))) return rc;
+    if (int rc = ctl.alloc(sizeof(EighCtl))) return rc;
+    if (int rc = diag.alloc(n * sizeof(float))) return rc;
+    if (int rc = rank.alloc(n * sizeof(int))) return rc;
+    float *W = (float *)wm.ptr, *V = (float *)vm.ptr;
+    EighCtl *C = (EighCtl *)ctl.ptr;
+    NP_HIP_CHECK(hipMemsetAsync(C, 0, sizeof(EighCtl), st));
+    const unsigned rows_y = (unsigned)(npad < 4096 ? npad : 4096);
+    eigh_pack_kernel<<<dim3(blocks_for(npad, 256), rows_y), 256, 0, st>>>(a, n, W, npad, C);
+    NP_LAUNCH_CHECK("eigh_pack_kernel");
+    if (vectors)
+        if (int rc = np_identity(V, npad)) return rc;
+    NP_HIP_CHECK(hipFuncSetAttribute((const void *)eigh_eig_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEighLds));
+    const int chunks = (int)((npad + 127) / 128);
+    g_eigh_last_sweeps = 0;
+    const int cap = g_eigh_max_sweeps > 0 ? g_eigh_max_sweeps : kEighSweepCap;
+    bool converged = false;
+    unsigned long long last[2] = {0, 0};
+    for (int sweep = 0; sweep < cap && !converged; ++sweep) {
+        NP_HIP_CHECK(hipMemsetAsync(C, 0, 2 * sizeof(unsigned long long), st));   // the counters; the scale stays
+        for (int step = 0; step < steps; ++step) {
+            eigh_eig_kernel<<<pairs, 256, kEighLds, st>>>(W, npad, nblk, step, C, (float *)mbuf.ptr, (float *)dbuf.ptr,
+                                                          (int *)flag.ptr);
+            NP_LAUNCH_CHECK("eigh_eig_kernel");
+            svd_apply_kernel<<<dim3(pairs, chunks + (vectors ? chunks : 0)), 256, 0, st>>>(
+                W, npad, chunks, V, npad, nblk, step, (const float *)mbuf.ptr, (const int *)flag.ptr);
+            NP_LAUNCH_CHECK("svd_apply_kernel");
+            eigh_colapply_kernel<<<dim3(pairs, chunks), 256, 0, st>>>(W, npad, nblk, step, (const float *)mbuf.ptr,
+                                                                      (const float *)dbuf.ptr, (const int *)flag.ptr);
+            NP_LAUNCH_CHECK("eigh_colapply_kernel");
+        }
+        if (int rc = np_memcpy_d2h(last, C, sizeof(last))) return rc;   // the one host read of the sweep
+        converged = last[0] == 0;
+        g_eigh_last_sweeps = sweep + 1;
+    }
+    if (!converged) *info_host = last[1] > (unsigned long long)INT_MAX ? INT_MAX : (last[1] > 0 ? (int)last[1] : 1);
+    eigh_diag_kernel<<<blocks_for(n, 256), 256, 0, st>>>(W, npad, n, C, (float *)diag.ptr);
+    NP_LAUNCH_CHECK("eigh_diag_kernel");
+    eigh_rank_kernel<<<blocks_for(n, 256), 256, 0, st>>>((const float *)diag.ptr, n, w, (int *)rank.ptr);
+    NP_LAUNCH_CHECK("eigh_rank_kernel");
+    if (vectors) {
+        eigh_sign_kernel<<<blocks_for(n, 4), 256, 0, st>>>(V, npad, n, (int *)neg.ptr);
+        NP_LAUNCH_CHECK("eigh_sign_kernel");
+        const dim3 grid(blocks_for(n, 256), (unsigned)(n < 4096 ? n : 4096));
+        eigh_gather_kernel<<<grid, 256, 0, st>>>(V, npad, n, (const int *)rank.ptr, (const int *)neg.ptr, (float *)tmp.ptr);
+        NP_LAUNCH_CHECK("eigh_gather_kernel");
+        if (int rc = np_transpose2d((const float *)tmp.ptr, v, 1, n, n)) return rc;
+    }
+    return np_sync();   // the scratch goes back to the pool; info is known
+}
+
 }  // namespace
 
 extern "C" {
@@ -1570,6 +2062,49 @@ int np_svdvals(const float *a, size_t m, size_t n, float *s, int *info_host) {
     if (int rc = np::ensure_init()) return rc;
     if (!a || !s || !info_host) return np::fail(NP_ERR_INVALID, "np_svdvals: null pointer");
     return svd_impl("np_svdvals", a, m, n, nullptr, s, nullptr, info_host);
+}
+
+int np_eigh(const float *a, size_t n, float *w, float *v, int *info_host) {
+    if (!a || !w || !v || !info_host) return np::fail(NP_ERR_INVALID, "np_eigh: null pointer");   // before any device work
+    if (int rc = np::ensure_init()) return rc;
+    return eigh_impl("np_eigh", a, n, w, v, info_host);
+}
+
+int np_eigvalsh(const float *a, size_t n, float *w, int *info_host) {
+    if (!a || !w || !info_host) return np::fail(NP_ERR_INVALID, "np_eigvalsh: null pointer");   // before any device work
+    if (int rc = np::ensure_init()) return rc;
+    return eigh_impl("np_eigvalsh", a, n, w, nullptr, info_host);
+}
+
+int np_symmetry_mismatch(const float *a, size_t n, int *host_any) {
+    if (!a || !host_any) return np::fail(NP_ERR_INVALID, "np_symmetry_mismatch: null pointer");   // before any device work
+    if (int rc = np::ensure_init()) return rc;
+    *host_any = 0;
+    if (n < 2) return NP_OK;
+    np::Scratch any;
+    if (int rc = any.alloc(sizeof(int))) return rc;
+    NP_HIP_CHECK(hipMemsetAsync(any.ptr, 0, sizeof(int), np::stream()));
+    const dim3 grid(blocks_for(n, 256), (unsigned)(n < 4096 ? n : 4096));
+    symmetry_kernel<<<grid, 256, 0, np::stream()>>>(a, n, (int *)any.ptr);
+    NP_LAUNCH_CHECK("symmetry_kernel");
+    return read_info((const int *)any.ptr, host_any);
+}
+
+int np_debug_eigh_max_sweeps(int sweeps) {
+    if (sweeps < 0) return np::fail(NP_ERR_INVALID, "np_debug_eigh_max_sweeps: %d", sweeps);
+    g_eigh_max_sweeps = sweeps;
+    return NP_OK;
+}
+
+int np_debug_eigh_small_path(int on) {
+    g_eigh_small_off = on ? 0 : 1;
+    return NP_OK;
+}
+
+int np_debug_eigh_last_sweeps(int *host_sweeps) {
+    if (!host_sweeps) return np::fail(NP_ERR_INVALID, "np_debug_eigh_last_sweeps: null pointer");
+    *host_sweeps = g_eigh_last_sweeps;
+    return NP_OK;
 }
 
 int np_debug_svd_max_sweeps(int sweeps) {

@@ -154,6 +154,7 @@ def _load_host():
     sig["NDArray_Cholesky"] = (_P, [_P])
     sig["NDArray_Correlate2D"] = (_P, [_P, _P, C.c_int, C.c_int, _P, C.c_int])
     sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
+    sig["NDArray_Eig"] = (C.POINTER(_P), [_P])
     sig["NDArray_MatrixRank"] = (_P, [_P, fp])
     sig["NDArray_Norm"] = (_P, [_P, C.c_int])
     sig["NDArray_Cond"] = (_P, [_P])
@@ -769,6 +770,17 @@ class NDArray:
         if not rtns:
             _raise_pending(h)
         out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(3))
+        _libc_free(C.cast(rtns, C.c_void_p))
+        return out
+
+    @staticmethod
+    def eig(a):              # numpower.c PHP_METHOD(eig): RETURN_2NDARRAY -> (values (n) ascending, vectors (n, n), vector j in column j); symmetric a only
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        rtns = h.NDArray_Eig(x._p)
+        if not rtns:
+            _raise_pending(h)
+        out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(2))
         _libc_free(C.cast(rtns, C.c_void_p))
         return out
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """apply_with_hip.py — turn a NumPower checkout into a `--with-hip` tree (INTEGRATION.md sections 2a and 2b, as code).
 
-    python tools/apply_with_hip.py [--keep-cuda] [--no-signal] <NumPower checkout> <output directory>
+    python tools/apply_with_hip.py [--keep-cuda] [--no-signal] [--eig] <NumPower checkout> <output directory>
 
 Copies the checkout to <output directory>, applies every edit of INTEGRATION.md section 2a by ANCHORED regex and
 copies the glue (ext/*.c, ext/*.h, include/np_hip.h) to <output>/src/hip/.  Every edit names its file, the exact
@@ -552,6 +552,24 @@ SIGNAL_EDITS = [
          context="NDArray *a = 0, *b = 0, *fill_value = 0; int mode = 0, boundary = 0, flip = 0;"),   # behind the function's opening line: indented by hand
 ]
 
+# ---- section 2b, eig: the reference's NDArray_Eig throws "GPU eig currently unavailable" for a GPU array; the early-out sits
+# behind its squareness check and before its first allocation, so the reference's message and nothing of its bookkeeping runs
+# first.  Like SIGNAL_EDITS a list of its own that is NOT part of EDITS, handed to apply() as `extra`; main() passes it only
+# under --eig, so the counts of the default command line stay what they were.  Its text runs as a program of its own (eig_bodies) ----
+EIG_EDITS = [
+    Edit("src/ndmath/linalg.c", "linalg.c:796-799 NDArray_Eig: GPU early-out",
+         r"^(?P<old>NDArray_Eig\(NDArray \*a\) \{\n"
+         r"[ \t]*if \(NDArray_NDIM\(a\) != 2 \|\| NDArray_SHAPE\(a\)\[0\] != NDArray_SHAPE\(a\)\[1\]\) \{\n"
+         r"[ \t]*zend_throw_error\(NULL, \"Error: Input matrix is not square\.\\n\"\);\n"
+         r"[ \t]*return NULL;\n"
+         r"[ \t]*\})(?=\n[ \t]*NDArray \*\*rtn = emalloc\()",
+         "/* numpower_amd 2b: a SYMMETRIC GPU operand is decomposed on the device (np_eigh, ext/hip_linalg.c; any other GPU operand\n"
+         " * is refused there); CPU operands fall through to the reference's LAPACK code below, untouched */\n"
+         "if (NPH_LINALG_TAKES(a)) {\n"
+         "    return NPH_Eig(a);\n"
+         "}", after=True, context="NDArray *a = 0;"),
+]
+
 CONTEXTS = {
     "ndarray.c:1055-1060 NDArray_ToGPU: H2D copy": "float *tmp_gpu = 0; NDArray *target = 0;",
     "ndarray.c:1090 NDArray_ToCPU: D2H copy": "NDArray *rtn = 0, *target = 0;",
@@ -824,6 +842,27 @@ def svd_program_source() -> str:
     return "\n".join(o)
 
 
+def eig_program_source() -> str:
+    """A C99 PROGRAM around the text EIG_EDITS inserts into linalg.c: NDArray_Eig with the reference's signature, the inserted
+    text VERBATIM (in the tree it sits behind the reference's squareness check, which NPH_Eig repeats), then a stand-in for the
+    reference's own code (LAPACK's sgeev / its GPU throw) that only counts how often it is reached.  Built and linked like svd_bodies.
+
+        eig_bodies cpu    a CPU operand falls through to the stand-in, no device is touched
+        eig_bodies gpu    GPU operands never fall through: known answers with the reference's shapes (values (n), vectors (n, n),
+                          vector j in column j, the sign rule), the not-symmetric refusal, no device allocation leaks
+    """
+    (edit,) = EIG_EDITS
+    o = ["/* generated by tools/apply_with_hip.py: eig_program_source() — do not edit */",
+         "#include <math.h>", "#include <stdio.h>", "#include <stdlib.h>", "#include <string.h>", "",
+         "#define HAVE_NP_HIP 1", '#include "numpower_host.h"', '#include "hip_linalg.h"', "",
+         "static int g_fell_through;   /* calls that reached the reference's own code (the stand-in below) */",
+         "static NDArray **reference_body(void) { g_fell_through++; return NULL; }", "",
+         "static NDArray **patched_NDArray_Eig(NDArray *a) {", "#ifdef HAVE_NP_HIP", _indent(edit.new, "    "), "#endif",
+         "    return reference_body();", "}", ""]
+    o.append(_EIG_PROGRAM_MAIN)
+    return "\n".join(o)
+
+
 def signal_program_source() -> str:
     """A C99 PROGRAM around the text SIGNAL_EDITS inserts into signal.c: NDArray_Correlate2D with the reference's signature, the
     inserted text VERBATIM, then a stand-in for the reference's own code (its GPU throw and its CPU loop) that only counts how
@@ -924,6 +963,75 @@ int main(int argc, char **argv) {
         if (all[i]) NDArray_FREE(all[i]);
     if (gpu) CHECK(NDArray_LiveDeviceAllocations() == live0, "%ld device allocations leaked", NDArray_LiveDeviceAllocations() - live0);
     printf("signal_bodies %s: %d calls reached the reference's own code, %d failures\n", argv[1], g_fell_through, g_failures);
+    return g_failures ? 1 : 0;
+}
+"""
+
+
+_EIG_PROGRAM_MAIN = r"""static int g_failures;
+#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "eig_bodies: " __VA_ARGS__); fprintf(stderr, "\n"); g_failures++; } } while (0)
+
+static NDArray *make(const float *v, int rows, int cols, int gpu) {
+    int shape[2] = {rows, cols};
+    NDArray *h = NDArray_FromHostBuffer(v, shape, cols ? 2 : 1);
+    if (!gpu) return h;
+    NDArray *d = NDArray_ToGPU(h);
+    NDArray_FREE(h);
+    return d;
+}
+
+static int values(NDArray *a, float *out) {
+    NDArray *h = NDArray_ToCPU(a);
+    const int rc = h ? NDArray_CopyToHostBuffer(h, out) : -1;
+    if (h) NDArray_FREE(h);
+    return rc;
+}
+
+static void release(NDArray **r) {
+    if (!r) return;
+    for (int i = 0; i < 2; ++i) NDArray_FREE(r[i]);
+    free(r);
+}
+
+int main(int argc, char **argv) {
+    if (argc < 2 || (strcmp(argv[1], "cpu") && strcmp(argv[1], "gpu"))) {
+        fprintf(stderr, "usage: eig_bodies cpu|gpu\n");
+        return 2;
+    }
+    const int gpu = strcmp(argv[1], "gpu") == 0;
+    /* [[2, 1], [1, 2]]: 1 with (1, -1) / sqrt 2 and 3 with (1, 1) / sqrt 2; diag(5, -1, 2): a permutation */
+    const float a22[4] = {2, 1, 1, 2}, d33[9] = {5, 0, 0, 0, -1, 0, 0, 0, 2}, skew[4] = {2, 1, 3, 2};
+    const long live0 = gpu ? NDArray_LiveDeviceAllocations() : 0;
+    NDArray *a = make(a22, 2, 2, gpu), *d = make(d33, 3, 3, gpu), *ns = make(skew, 2, 2, gpu);
+    NDArray **r = patched_NDArray_Eig(a);
+    if (!gpu) {
+        CHECK(!r, "a CPU operand was computed on the device");
+        CHECK(g_fell_through == 1, "%d of 1 calls reached the reference's code", g_fell_through);
+    } else {
+        float w[3], v[9];
+        const float h = 0.70710678f;
+        int ok = r && NDArray_NDIM(r[0]) == 1 && NDArray_SHAPE(r[0])[0] == 2 && NDArray_NDIM(r[1]) == 2 &&
+                 NDArray_SHAPE(r[1])[0] == 2 && NDArray_SHAPE(r[1])[1] == 2;
+        CHECK(ok, "the result shapes are not values (2), vectors (2, 2)");
+        ok = ok && values(r[0], w) == 0 && values(r[1], v) == 0 && w[0] == 1.0f && w[1] == 3.0f;
+        ok = ok && fabsf(v[0] - h) < 1e-6f && fabsf(v[2] + h) < 1e-6f && fabsf(v[1] - h) < 1e-6f && fabsf(v[3] - h) < 1e-6f;
+        CHECK(ok, "eig of [[2, 1], [1, 2]] differs from 1, 3 and (1, -1), (1, 1) / sqrt 2 in columns");
+        release(r);
+        r = patched_NDArray_Eig(d);
+        const float perm[9] = {0, 0, 1, 1, 0, 0, 0, 1, 0};
+        ok = r && values(r[0], w) == 0 && values(r[1], v) == 0 && w[0] == -1.0f && w[1] == 2.0f && w[2] == 5.0f;
+        for (int i = 0; ok && i < 9; ++i) ok = v[i] == perm[i];
+        CHECK(ok, "eig of diag(5, -1, 2) differs from -1, 2, 5 and the permutation");
+        CHECK(patched_NDArray_Eig(ns) == NULL && strstr(numpower_host_last_error(), "symmetric eigensolver") &&
+              strstr(numpower_host_last_error(), "->cpu()"), "a non-symmetric operand was not refused");
+        CHECK(g_fell_through == 0, "%d GPU calls fell through to the reference's code", g_fell_through);
+    }
+    release(r);
+    NDArray_FREE(a);
+    NDArray_FREE(d);
+    NDArray_FREE(ns);
+    if (gpu) CHECK(NDArray_LiveDeviceAllocations() == live0, "%ld device allocations leaked", NDArray_LiveDeviceAllocations() - live0);
+    printf("eig_bodies %s: %d calls reached the reference's own code, %d failures\n", argv[1], g_fell_through, g_failures);
     return g_failures ? 1 : 0;
 }
 """
@@ -2117,7 +2225,7 @@ class Applied(dict):
 
 
 def apply(checkout: Path, out: Path, keep_cuda: bool = False, extra=()):
-    """-> {edit description: times applied} for EDITS; the edits of `extra` (SIGNAL_EDITS) are applied after them, file by file,
+    """-> {edit description: times applied} for EDITS; the edits of `extra` (SIGNAL_EDITS, EIG_EDITS) are applied after them, file by file,
     and reported in the result's .extra.  Raises PatchError on any anchor problem or leftover CUDA name."""
     if out.exists():
         raise PatchError("%s exists; give a fresh output directory" % out)
@@ -2150,8 +2258,8 @@ def apply(checkout: Path, out: Path, keep_cuda: bool = False, extra=()):
 
 def main(argv):
     keep_cuda = "--keep-cuda" in argv
-    extra = [] if "--no-signal" in argv else SIGNAL_EDITS
-    argv = [a for a in argv if a not in ("--keep-cuda", "--no-signal")]
+    extra = ([] if "--no-signal" in argv else SIGNAL_EDITS) + (EIG_EDITS if "--eig" in argv else [])
+    argv = [a for a in argv if a not in ("--keep-cuda", "--no-signal", "--eig")]
     if len(argv) != 3:
         print(__doc__, file=sys.stderr)
         return 2

@@ -15,7 +15,12 @@ that of numpy's fp32 cholesky, and numpy's time on the host (the median of five 
 warm-up); it ends with the gate "the device call at n = 2048 is faster than numpy's".  --svd --accuracy prints instead the four
 metrics of tests/svd_family.py for every input of the bound tests next to their limits (profiles/linalg/svd_accuracy.log).
 The SVD leg imports tests/svd_family.py: the inputs, the metrics and the CPU emulator have that one definition, which the tests
-use too.  Sizes of up to 64 are timed twice, on the one-launch path and with it switched off (np_debug_svd_small_path)."""
+use too.  Sizes of up to 64 are timed twice, on the one-launch path and with it switched off (np_debug_svd_small_path).
+
+--eigh runs the symmetric eigensolver's leg (profiles/linalg/eigh_sweep.log): np_eigh and np_eigvalsh on the seeded random symmetric
+matrix of tests/eig_family.py, ms per call (the median of single calls after two untimed ones), sweeps taken, launches per call, the three metrics of tests/eig_family.py in
+n eps, np_svd of the same matrix in the same run (the same machinery plus a Gram step) and numpy's fp32 eigh on the host (median
+of five after a warm-up).  Sizes of up to 64 are timed on the blocked path too (np_debug_eigh_small_path)."""
 import argparse
 import ctypes as C
 import sys
@@ -30,10 +35,13 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--sizes", default=None, help="default 64,256,1024,4096,8192,16384 (with --cholesky also 128)")
 ap.add_argument("--cholesky", action="store_true", help="the Cholesky leg: np_potrf against np_getrf")
 ap.add_argument("--svd", action="store_true", help="the SVD leg: np_svd / np_svdvals against numpy's svd on the host")
+ap.add_argument("--eigh", action="store_true", help="the eigensolver's leg: np_eigh / np_eigvalsh against np_svd and numpy's eigh")
 ap.add_argument("--accuracy", action="store_true", help="with --svd: the accuracy table of the bound tests' inputs")
 ap.add_argument("--reps", type=int, default=0, help="0: as many as fit ~0.5 s per size (at least 3)")
 ap.add_argument("--no-host", action="store_true", help="skip numpy's solve on the host")
 args = ap.parse_args()
+if args.sizes is None and args.eigh:
+    args.sizes = "8,32,64,128,256,512,1024,2048,4096"
 if args.sizes is None and args.svd:
     args.sizes = "8,32,64,256,1024,2048,4096"
 if args.sizes is None:
@@ -77,6 +85,23 @@ gc.free()
 
 
 
+def timed_median(fn, reps):
+    """median ms of `reps` single calls after two untimed ones, and the launches of a call; fn must block until its result is known
+    (np_eigh, np_eigvalsh and np_svd do: they hand info to the host), so a host clock around the call measures it"""
+    fn()
+    l0 = launches()
+    fn()
+    per_call = launches() - l0
+    ts = []
+    for _ in range(reps):
+        D.sync()
+        h0 = time.perf_counter()
+        fn()
+        D.sync()
+        ts.append((time.perf_counter() - h0) * 1e3)
+    return float(np.median(ts)), per_call
+
+
 def reps_for(fn):
     t0 = time.time()
     fn()
@@ -88,6 +113,52 @@ def residual_over_eps(a64, l):
     l64 = l.astype(np.float64)
     return float(np.abs(a64 - l64 @ l64.T).sum(axis=0).max() / np.abs(a64).sum(axis=0).max()) * 2.0 ** 23
 
+
+if args.eigh:
+    from tests import eig_family as E
+
+    print("%6s %10s %14s %7s %9s %10s %11s   %-22s %s" % ("n", "np_eigh ms", "np_eigvalsh ms", "sweeps", "launches", "np_svd ms", "svd sweeps",
+                                                         "res / orth / werr (n eps)", "host numpy fp32 eigh"), flush=True)
+    for n in [int(x) for x in args.sizes.split(",")]:
+        a = E.random_symmetric(n)
+        da, dw, dv, du = D.DeviceArray.from_host(a), D.DeviceArray((n,)), D.DeviceArray((n, n)), D.DeviceArray((n, n))
+        ih, sw, ssw = C.c_int(), C.c_int(), C.c_int()
+
+        def eigh():
+            check(lib.np_eigh(da.ptr, n, dw.ptr, dv.ptr, C.byref(ih)))
+
+        def eigvalsh():
+            check(lib.np_eigvalsh(da.ptr, n, dw.ptr, C.byref(ih)))
+
+        def svd():
+            check(lib.np_svd(da.ptr, n, n, du.ptr, dw.ptr, dv.ptr, C.byref(ih)))
+
+        rows = [("", 1)] + ([(" (the one-launch path switched off)", 0)] if n <= 64 else [])
+        for note, small in rows:
+            check(lib.np_debug_eigh_small_path(small))
+            ms, per_call = timed_median(eigh, reps_for(eigh))
+            check(lib.np_debug_eigh_last_sweeps(C.byref(sw)))
+            assert ih.value == 0
+            got = E.metrics(a, dw.to_host().reshape(n), dv.to_host().reshape(n, n))
+            msv, _ = timed_median(eigvalsh, reps_for(eigvalsh))
+            check(lib.np_debug_eigh_small_path(1))
+            mss, _ = timed_median(svd, reps_for(svd))
+            check(lib.np_debug_svd_last_sweeps(C.byref(ssw)))
+            host = "-"
+            if not args.no_host and not note:
+                np.linalg.eigh(a)                   # warm-up
+                ts = []
+                for _ in range(5):
+                    h0 = time.perf_counter()
+                    np.linalg.eigh(a)
+                    ts.append((time.perf_counter() - h0) * 1e3)
+                host = "%.3f ms (median of 5 after a warm-up)" % float(np.median(ts))
+            print("%6d %10.3f %14.3f %7d %9d %10.3f %11d   %-22s %s%s" % (
+                n, ms, msv, sw.value, per_call, mss, ssw.value,
+                " / ".join("%.3f" % (got[k] / (n * E.EPS)) for k in E.METRICS), host, note), flush=True)
+        for d in (da, dw, dv, du):
+            d.free()
+    sys.exit(0)
 
 if args.svd:
     from tests import svd_family as F
