@@ -377,7 +377,7 @@ int np_strided_copy(const float *in, float *out, int ndim, const int *host_shape
  * where NDArray_AssignArray copies element by element through the sliding view). */
 int np_copy2d(float *dst, size_t dst_pitch, const float *src, size_t src_pitch, size_t width, size_t rows);
 
-/* ---- dense LU factorization (np_linalg.hip; DESIGN.md "LU") ------------------------------------
+/* ---- dense LU factorization (np_lu.hip; DESIGN.md "LU") ----------------------------------------
  * All matrices are n x n fp32 on the device; every call runs on the library stream and takes its
  * scratch from the caching pool.  Results are bit-identical from run to run.
  * np_getrf:   LAPACK sgetrf on the COLUMN-MAJOR a, in place: a = P^T L U, ipiv[n] = 0-based pivot rows
@@ -400,7 +400,7 @@ int np_inverse(const float *a, size_t n, float *out, int *info_host);
 int np_solve(const float *a, const float *b, size_t n, size_t nrhs, float *x, int *info_host);
 int np_lu(const float *a, size_t n, float *p, float *l, float *u);
 
-/* ---- dense Cholesky factorization (np_linalg.hip; DESIGN.md "Cholesky") --------------------------
+/* ---- dense Cholesky factorization (np_cholesky.hip; DESIGN.md "Cholesky") ------------------------
  * a = L L^T for a symmetric positive definite n x n fp32 matrix, ROW-MAJOR, with LAPACK's spotrf('L')
  * semantics: only the lower triangle of a (diagonal included) is read, whatever the strict upper triangle
  * holds.  info = 1 + the first column whose pivot a_jj - sum_k l_jk^2 is not greater than zero (or is NaN),
@@ -414,7 +414,7 @@ int np_lu(const float *a, size_t n, float *p, float *l, float *u);
 int np_potrf(float *a, size_t n, int *info);
 int np_cholesky(const float *a, size_t n, float *out, int *info_host);
 
-/* ---- singular value decomposition (np_linalg.hip; DESIGN.md "SVD") --------------------------------
+/* ---- singular value decomposition (np_jacobi.hip; DESIGN.md "SVD") --------------------------------
  * One-sided (Hestenes) Jacobi, blocked: replaces cuda_svd_float (cuda_math.cu:947, cuSOLVER's gesvdj) behind NDArray_SVD.
  * a: m x n fp32, ROW-MAJOR, untouched.  k = min(m, n).
  * u: m x k row-major, s: k, vt: k x n row-major, with  a = u . diag(s) . vt,  s >= 0 and non-increasing.
@@ -443,7 +443,7 @@ int np_cholesky(const float *a, size_t n, float *out, int *info_host);
 int np_svd(const float *a, size_t m, size_t n, float *u, float *s, float *vt, int *info_host);
 int np_svdvals(const float *a, size_t m, size_t n, float *s, int *info_host);
 
-/* ---- symmetric eigensolver (np_linalg.hip; DESIGN.md "eigh") --------------------------------------
+/* ---- symmetric eigensolver (np_jacobi.hip; DESIGN.md "eigh") --------------------------------------
  * Two-sided (classical) Jacobi, blocked: what cuda_matrix_eig_float (cuda_math.cu:1645, cuSOLVER's Ssyevd) would have
  * done behind NDArray_Eig, which the reference refuses for GPU arrays (linalg.c:826-833).
  * a: n x n fp32, ROW-MAJOR, untouched.  LAPACK ssyevd('L') semantics, the rule np_potrf documents: only the lower triangle

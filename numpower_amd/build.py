@@ -30,7 +30,7 @@ LIBDIR = ROOT / "numpower_amd" / "lib"
 OBJDIR = ROOT / "build" / "obj"
 
 HIP_SOURCES = ["np_runtime.hip", "np_elementwise.hip", "np_fused_static.hip", "np_reduce.hip", "np_sgemm.hip", "np_layout.hip",
-               "np_select.hip", "np_comm.hip", "np_linalg.hip", "np_signal.hip"]
+               "np_select.hip", "np_comm.hip", "np_lu.hip", "np_cholesky.hip", "np_jacobi.hip", "np_signal.hip"]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{INCLUDE}", f"-I{CSRC}"]
 
 
@@ -79,7 +79,7 @@ def build_hip(force: bool = False, verbose: bool = False, tuning: bool = False) 
     if jobs:
         if verbose:
             print("[build] compiling %d HIP translation unit(s) for gfx950" % len(jobs), flush=True)
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1, 16)) as ex:
             list(ex.map(_run, jobs))
     lib = LIBDIR / ("libnp_hip_tuning.so" if tuning else "libnp_hip.so")
     if force or jobs or _newer(lib, objs):
@@ -161,174 +161,38 @@ def build_method_bodies(force: bool = False, verbose: bool = False) -> Path:
     return exe
 
 
-def build_fast_path_bodies(force: bool = False, verbose: bool = False) -> Path:
-    """The text tools/apply_with_hip.py inserts into the reference's device-dispatching L2 functions,
-    wrapped into a C99 program by the tool itself (fast_path_program_source) -> build/gen/fast_path_bodies.c ->
-    numpower_amd/lib/fast_path_bodies; -Wall -Wextra -Werror against numpower_host.h + hip_fast.h."""
-    exe = LIBDIR / "fast_path_bodies"
-    tool = ROOT / "tools" / "apply_with_hip.py"
-    gen = ROOT / "build" / "gen" / "fast_path_bodies.c"
-    deps = [tool, LIBDIR / "libnumpower_host.so"] + list(INCLUDE.glob("*.h")) + list(EXT.glob("*.h"))
-    if force or _newer(exe, deps):
-        if verbose:
-            print("[build] generating + compiling fast_path_bodies", flush=True)
+# The programs tools/apply_with_hip.py wraps around the text it inserts into the reference: <name>_program_source()
+# -> build/gen/<name>_bodies.c -> numpower_amd/lib/<name>_bodies, in the order build_all compiles them.  fast_path: the
+# device-dispatching L2 functions; lazy: the pending chains around a stand-in for the Zend object table; linalg: NDArray_Det /
+# Inverse / LU / Solve; cholesky, svd, eig: NDArray_Cholesky / _SVD / _Eig; signal: NDArray_Correlate2D.
+BODIES = ("fast_path", "lazy", "linalg", "cholesky", "svd", "eig", "signal")
+_apply_with_hip = None
+
+
+def _apply_with_hip_module():
+    """tools/apply_with_hip.py as a module, imported once per process."""
+    global _apply_with_hip
+    if _apply_with_hip is None:
         import importlib.util
-        spec = importlib.util.spec_from_file_location("np_apply_with_hip", tool)
+        spec = importlib.util.spec_from_file_location("np_apply_with_hip", ROOT / "tools" / "apply_with_hip.py")
         mod = importlib.util.module_from_spec(spec)
         sys.modules[spec.name] = mod          # dataclasses looks the module up while the class body runs
         spec.loader.exec_module(mod)
-        gen.parent.mkdir(parents=True, exist_ok=True)
-        gen.write_text(mod.fast_path_program_source())
-        cc = shutil.which("gcc") or "gcc"
-        flags = [f for f in EXT_CFLAGS if f != "-fPIC"]
-        _run([cc, *flags, str(gen), "-o", str(exe), f"-L{LIBDIR}", "-lnumpower_host", "-lnp_hip",
-              "-Wl,-rpath,$ORIGIN"])
-    return exe
+        _apply_with_hip = mod
+    return _apply_with_hip
 
 
-def build_linalg_bodies(force: bool = False, verbose: bool = False) -> Path:
-    """The text tools/apply_with_hip.py inserts into the reference's NDArray_Det / Inverse / LU / Solve (linear algebra),
-    wrapped into a C99 program by the tool itself (linalg_program_source) -> build/gen/linalg_bodies.c ->
-    numpower_amd/lib/linalg_bodies; -Wall -Wextra -Werror against numpower_host.h + hip_linalg.h."""
-    exe = LIBDIR / "linalg_bodies"
-    tool = ROOT / "tools" / "apply_with_hip.py"
-    gen = ROOT / "build" / "gen" / "linalg_bodies.c"
-    deps = [tool, LIBDIR / "libnumpower_host.so"] + list(INCLUDE.glob("*.h")) + list(EXT.glob("*.h"))
+def build_bodies(name: str, force: bool = False, verbose: bool = False) -> Path:
+    """One of BODIES as a C99 program: -Wall -Wextra -Werror against numpower_host.h and the ext/ headers, so a signature that
+    drifts from the reference's call sites fails here."""
+    exe = LIBDIR / (name + "_bodies")
+    gen = ROOT / "build" / "gen" / (name + "_bodies.c")
+    deps = [ROOT / "tools" / "apply_with_hip.py", LIBDIR / "libnumpower_host.so"] + list(INCLUDE.glob("*.h")) + list(EXT.glob("*.h"))
     if force or _newer(exe, deps):
         if verbose:
-            print("[build] generating + compiling linalg_bodies", flush=True)
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("np_apply_with_hip", tool)
-        mod = importlib.util.module_from_spec(spec)
-        sys.modules[spec.name] = mod
-        spec.loader.exec_module(mod)
+            print("[build] generating + compiling %s_bodies" % name, flush=True)
         gen.parent.mkdir(parents=True, exist_ok=True)
-        gen.write_text(mod.linalg_program_source())
-        cc = shutil.which("gcc") or "gcc"
-        flags = [f for f in EXT_CFLAGS if f != "-fPIC"]
-        _run([cc, *flags, str(gen), "-o", str(exe), f"-L{LIBDIR}", "-lnumpower_host", "-lnp_hip",
-              "-Wl,-rpath,$ORIGIN"])
-    return exe
-
-
-def build_cholesky_bodies(force: bool = False, verbose: bool = False) -> Path:
-    """The text tools/apply_with_hip.py inserts into the reference's NDArray_Cholesky (Cholesky), wrapped
-    into a C99 program by the tool itself (cholesky_program_source) -> build/gen/cholesky_bodies.c ->
-    numpower_amd/lib/cholesky_bodies; -Wall -Wextra -Werror against numpower_host.h + hip_linalg.h."""
-    exe = LIBDIR / "cholesky_bodies"
-    tool = ROOT / "tools" / "apply_with_hip.py"
-    gen = ROOT / "build" / "gen" / "cholesky_bodies.c"
-    deps = [tool, LIBDIR / "libnumpower_host.so"] + list(INCLUDE.glob("*.h")) + list(EXT.glob("*.h"))
-    if force or _newer(exe, deps):
-        if verbose:
-            print("[build] generating + compiling cholesky_bodies", flush=True)
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("np_apply_with_hip", tool)
-        mod = importlib.util.module_from_spec(spec)
-        sys.modules[spec.name] = mod
-        spec.loader.exec_module(mod)
-        gen.parent.mkdir(parents=True, exist_ok=True)
-        gen.write_text(mod.cholesky_program_source())
-        cc = shutil.which("gcc") or "gcc"
-        flags = [f for f in EXT_CFLAGS if f != "-fPIC"]
-        _run([cc, *flags, str(gen), "-o", str(exe), f"-L{LIBDIR}", "-lnumpower_host", "-lnp_hip",
-              "-Wl,-rpath,$ORIGIN"])
-    return exe
-
-
-def build_svd_bodies(force: bool = False, verbose: bool = False) -> Path:
-    """The text tools/apply_with_hip.py inserts into the reference's NDArray_SVD (SVD), wrapped
-    into a C99 program by the tool itself (svd_program_source) -> build/gen/svd_bodies.c ->
-    numpower_amd/lib/svd_bodies; -Wall -Wextra -Werror against numpower_host.h + hip_linalg.h."""
-    exe = LIBDIR / "svd_bodies"
-    tool = ROOT / "tools" / "apply_with_hip.py"
-    gen = ROOT / "build" / "gen" / "svd_bodies.c"
-    deps = [tool, LIBDIR / "libnumpower_host.so"] + list(INCLUDE.glob("*.h")) + list(EXT.glob("*.h"))
-    if force or _newer(exe, deps):
-        if verbose:
-            print("[build] generating + compiling svd_bodies", flush=True)
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("np_apply_with_hip", tool)
-        mod = importlib.util.module_from_spec(spec)
-        sys.modules[spec.name] = mod
-        spec.loader.exec_module(mod)
-        gen.parent.mkdir(parents=True, exist_ok=True)
-        gen.write_text(mod.svd_program_source())
-        cc = shutil.which("gcc") or "gcc"
-        flags = [f for f in EXT_CFLAGS if f != "-fPIC"]
-        _run([cc, *flags, str(gen), "-o", str(exe), f"-L{LIBDIR}", "-lnumpower_host", "-lnp_hip",
-              "-Wl,-rpath,$ORIGIN"])
-    return exe
-
-
-def build_eig_bodies(force: bool = False, verbose: bool = False) -> Path:
-    """The text tools/apply_with_hip.py inserts into the reference's NDArray_Eig (eig), wrapped
-    into a C99 program by the tool itself (eig_program_source) -> build/gen/eig_bodies.c ->
-    numpower_amd/lib/eig_bodies; -Wall -Wextra -Werror against numpower_host.h + hip_linalg.h."""
-    exe = LIBDIR / "eig_bodies"
-    tool = ROOT / "tools" / "apply_with_hip.py"
-    gen = ROOT / "build" / "gen" / "eig_bodies.c"
-    deps = [tool, LIBDIR / "libnumpower_host.so"] + list(INCLUDE.glob("*.h")) + list(EXT.glob("*.h"))
-    if force or _newer(exe, deps):
-        if verbose:
-            print("[build] generating + compiling eig_bodies", flush=True)
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("np_apply_with_hip", tool)
-        mod = importlib.util.module_from_spec(spec)
-        sys.modules[spec.name] = mod
-        spec.loader.exec_module(mod)
-        gen.parent.mkdir(parents=True, exist_ok=True)
-        gen.write_text(mod.eig_program_source())
-        cc = shutil.which("gcc") or "gcc"
-        flags = [f for f in EXT_CFLAGS if f != "-fPIC"]
-        _run([cc, *flags, str(gen), "-o", str(exe), f"-L{LIBDIR}", "-lnumpower_host", "-lnp_hip",
-              "-Wl,-rpath,$ORIGIN"])
-    return exe
-
-
-def build_signal_bodies(force: bool = False, verbose: bool = False) -> Path:
-    """The text tools/apply_with_hip.py inserts into the reference's NDArray_Correlate2D (correlate2d), wrapped
-    into a C99 program by the tool itself (signal_program_source) -> build/gen/signal_bodies.c ->
-    numpower_amd/lib/signal_bodies; -Wall -Wextra -Werror against numpower_host.h + hip_signal.h."""
-    exe = LIBDIR / "signal_bodies"
-    tool = ROOT / "tools" / "apply_with_hip.py"
-    gen = ROOT / "build" / "gen" / "signal_bodies.c"
-    deps = [tool, LIBDIR / "libnumpower_host.so"] + list(INCLUDE.glob("*.h")) + list(EXT.glob("*.h"))
-    if force or _newer(exe, deps):
-        if verbose:
-            print("[build] generating + compiling signal_bodies", flush=True)
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("np_apply_with_hip", tool)
-        mod = importlib.util.module_from_spec(spec)
-        sys.modules[spec.name] = mod
-        spec.loader.exec_module(mod)
-        gen.parent.mkdir(parents=True, exist_ok=True)
-        gen.write_text(mod.signal_program_source())
-        cc = shutil.which("gcc") or "gcc"
-        flags = [f for f in EXT_CFLAGS if f != "-fPIC"]
-        _run([cc, *flags, str(gen), "-o", str(exe), f"-L{LIBDIR}", "-lnumpower_host", "-lnp_hip",
-              "-Wl,-rpath,$ORIGIN"])
-    return exe
-
-
-def build_lazy_bodies(force: bool = False, verbose: bool = False) -> Path:
-    """The text tools/apply_with_hip.py inserts for the pending chains (buffer_get's flush, the appenders of
-    numpower.c's operator handler, static arithmetic methods and unary methods), wrapped by the tool itself into a C99 program
-    around a stand-in for the Zend object table (lazy_program_source) -> build/gen/lazy_bodies.c -> numpower_amd/lib/lazy_bodies."""
-    exe = LIBDIR / "lazy_bodies"
-    tool = ROOT / "tools" / "apply_with_hip.py"
-    gen = ROOT / "build" / "gen" / "lazy_bodies.c"
-    deps = [tool, LIBDIR / "libnumpower_host.so"] + list(INCLUDE.glob("*.h")) + list(EXT.glob("*.h"))
-    if force or _newer(exe, deps):
-        if verbose:
-            print("[build] generating + compiling lazy_bodies", flush=True)
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("np_apply_with_hip", tool)
-        mod = importlib.util.module_from_spec(spec)
-        sys.modules[spec.name] = mod
-        spec.loader.exec_module(mod)
-        gen.parent.mkdir(parents=True, exist_ok=True)
-        gen.write_text(mod.lazy_program_source())
+        gen.write_text(getattr(_apply_with_hip_module(), name + "_program_source")())
         cc = shutil.which("gcc") or "gcc"
         flags = [f for f in EXT_CFLAGS if f != "-fPIC"]
         _run([cc, *flags, str(gen), "-o", str(exe), f"-L{LIBDIR}", "-lnumpower_host", "-lnp_hip",
@@ -377,13 +241,8 @@ def build_all(force: bool = False, verbose: bool = False):
     host = build_host(force, verbose)
     build_ext_glue(force, verbose)
     build_method_bodies(force, verbose)
-    build_fast_path_bodies(force, verbose)
-    build_lazy_bodies(force, verbose)
-    build_linalg_bodies(force, verbose)
-    build_cholesky_bodies(force, verbose)
-    build_svd_bodies(force, verbose)
-    build_eig_bodies(force, verbose)
-    build_signal_bodies(force, verbose)
+    for name in BODIES:
+        build_bodies(name, force, verbose)
     oracle = build_oracle(force, verbose)
     build_loopback_rccl(force, verbose)
     return hip, host, oracle

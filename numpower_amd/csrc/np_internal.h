@@ -93,7 +93,7 @@ int sgemm_batched_with_progress(size_t batch, size_t M, size_t N, size_t K, cons
 int sgemm_batched_piece(size_t count, size_t whole, size_t M, size_t N, size_t K, const float *A, size_t stride_a, const float *B,
                         size_t stride_b, float *C, size_t stride_c);
 // C (M x N, row stride ldc) -= A (M x K, row stride lda) . B (K x N, row stride ldb), one MFMA tile launch (np_sgemm.hip; the
-// LU's trailing updates and blocked triangular solves, np_linalg.hip).  None of the np_sgemm* plans uses it.
+// LU's trailing updates and blocked triangular solves, np_lu.hip, and the Cholesky's trailing updates, np_cholesky.hip).  None of the np_sgemm* plans uses it.
 int sgemm_sub_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, const float *B, size_t ldb, float *C, size_t ldc);
 // Compiled chains (np_fused_static.hip): what np_elementwise.hip's fused_chain_impl hands over when a chain of 1-3 steps
 // might be on the menu of straight-line kernels.  operand[k] == nullptr: a scalar operand (or a unary step); idx[k]: how an

@@ -3356,7 +3356,7 @@ int sgemm_batched_piece(size_t count, size_t whole, size_t M, size_t N, size_t K
 }
 
 // C (M x N, row stride ldc) -= A (M x K, row stride lda) . B (K x N, row stride ldb): one launch of the 128 x 128 tile kernel
-// with the subtracting epilogue, on the library stream.  Only the LU (np_linalg.hip) calls it; no np_sgemm* plan reaches it.
+// with the subtracting epilogue, on the library stream.  Only the LU (np_lu.hip) and the Cholesky (np_cholesky.hip) call it; no np_sgemm* plan reaches it.
 int sgemm_sub_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, const float *B, size_t ldb, float *C, size_t ldc) {
     if (M == 0 || N == 0 || K == 0) return NP_OK;
     if (M > 0x7fffffffu || N > 0x7fffffffu || K > 0x7fffffffu || lda > 0x7fffffffu || ldb > 0x7fffffffu || ldc > 0x7fffffffu)

@@ -1,4 +1,4 @@
-"""CPU-tier checks of the Cholesky factorization's boundary (np_linalg.hip, ext/hip_linalg.c, host/numpower_linalg.cpp):
+"""CPU-tier checks of the Cholesky factorization's boundary (np_cholesky.hip, ext/hip_linalg.c, host/numpower_linalg.cpp):
 np_potrf / np_cholesky are declared, prototyped and exported and refuse null arguments; NDArray_Cholesky has the
 reference's signature and messages; the --with-hip early-out applies once, in front of the reference's GPU throw."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""CPU-tier checks of the symmetric eigensolver's boundary (np_linalg.hip, ext/hip_linalg.c, host/numpower_linalg.cpp): np_eigh /
+"""CPU-tier checks of the symmetric eigensolver's boundary (np_jacobi.hip, ext/hip_linalg.c, host/numpower_linalg.cpp): np_eigh /
 np_eigvalsh / np_symmetry_mismatch and the three debug knobs are declared, prototyped and exported and refuse null arguments;
 NDArray_Eig has the reference's signature and message; the --with-hip early-out is one edit in a list of its own that is NOT part
 of EDITS and reaches a tree only under --eig; eig_bodies shows a CPU operand reaching the reference's own code."""
@@ -48,7 +48,7 @@ def test_abi_is_declared_prototyped_and_exported():
 
 def test_the_header_states_the_fine_print():
     raw = re.sub(r"\s+", " ", (ROOT / "include" / "np_hip.h").read_text().replace(" * ", " "))
-    block = raw[raw.index("symmetric eigensolver (np_linalg.hip"):raw.index("int np_eigh(")]
+    block = raw[raw.index("symmetric eigensolver (np_jacobi.hip"):raw.index("int np_eigh(")]
     for phrase in ("only the lower triangle", "ssyevd('L')", "eigenvalues ascending", "ties kept in the order of their diagonal position",
                    "column j is the eigenvector of w[j]", "not renormalised", "the first such in index order, is positive",
                    "same w bit for bit", "the sweep cap (60)", "clipped to INT_MAX", "the largest |entry| of the lower triangle",

@@ -1,4 +1,4 @@
-"""The device Cholesky factorization (np_linalg.hip: np_potrf / np_cholesky, NDArray.cholesky).
+"""The device Cholesky factorization (np_cholesky.hip: np_potrf / np_cholesky, NDArray.cholesky).
 
 Exact tests.  L0 is lower triangular with strict-lower entries in -2 .. 2 and diagonal entries in {1, 2, 4}, A = L0 L0^T.
 Every intermediate of any correct factorization order is an integer of magnitude <= 4 n + 16 < 2^24, every square root is

@@ -1,4 +1,4 @@
-"""The device symmetric eigensolver (np_linalg.hip: np_eigh / np_eigvalsh / np_symmetry_mismatch; NDArray.eig).
+"""The device symmetric eigensolver (np_jacobi.hip: np_eigh / np_eigvalsh / np_symmetry_mismatch; NDArray.eig).
 
 Exact tests.  diag(d) with distinct +-j 2^e at permuted positions, one +0.0 and one -0.0 (tests/eig_family.py): nothing rotates,
 so w is the stably sorted d bit for bit, v a permutation matrix of 0 / +1, info = 0 and a untouched — through np_eigh,

@@ -1,4 +1,4 @@
-"""det / inv / solve / lu on the device LU (np_linalg.hip, host/numpower_linalg.cpp, DESIGN.md "LU").
+"""det / inv / solve / lu on the device LU (np_lu.hip, host/numpower_linalg.cpp, DESIGN.md "LU").
 
 Known answers are exact; everything else is checked against numpy in float64 with normwise bounds
 (eps = 2^-23): inv ||a x - I|| / (||a|| ||x||), solve ||a x - b|| / (||a|| ||x||) and lu ||P a - L U|| / ||a||

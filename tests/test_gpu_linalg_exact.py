@@ -1,4 +1,4 @@
-"""The device LU (np_linalg.hip) on exact-arithmetic inputs: element-for-element against the expected factors.
+"""The device LU (np_lu.hip) on exact-arithmetic inputs: element-for-element against the expected factors.
 
 Every input is a tests/linalg_exact.py construction M = Q L U whose exactness certificate holds, so fp32 partial pivoting
 must return exactly its pivots, info, L and U whatever the order of summation, and a solve with an integer x must return
@@ -21,7 +21,7 @@ LADDER = [1, 2, 3, 15, 16, 17, 63, 64, 65, 127, 128, 129, 130, 131, 132, 191, 19
           2047, 2048, 2049, 3073, 4095, 4097, 8193]
 SINGULAR = "LU factorization failed. Unable to compute the matrix inverse.\n"
 CHUNK_BYTES = 256 << 20
-SMALL_LDS_FLOATS = 156 * 1024 // 4   # np_linalg.hip kSmallLdsFloats: the n <= 128 path's LDS budget
+SMALL_LDS_FLOATS = 156 * 1024 // 4   # np_linalg_common.h kSmallLdsFloats: the n <= 128 path's LDS budget
 
 
 def _nd():

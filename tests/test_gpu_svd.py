@@ -1,4 +1,4 @@
-"""The device SVD (np_linalg.hip: np_svd / np_svdvals; NDArray.svd, matrix_rank, norm, cond).
+"""The device SVD (np_jacobi.hip: np_svd / np_svdvals; NDArray.svd, matrix_rank, norm, cond).
 
 Exact tests.  a = P diag(d) Q with signed permutations and distinct d = j 2^e (tests/svd_family.py): the columns are already
 orthogonal, every dot product has one non-zero term and every norm is the root of an exactly represented perfect square, so

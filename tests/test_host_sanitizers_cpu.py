@@ -33,8 +33,8 @@ def programs(tmp_path_factory):
     if not gcc or not gxx:
         pytest.skip("no gcc / g++")
     from numpower_amd import build
-    build.build_fast_path_bodies()        # (re)generates build/gen/*.c from the tool when it is newer
-    build.build_lazy_bodies()
+    build.build_bodies("fast_path")      # (re)generates build/gen/*.c from the tool when it is newer
+    build.build_bodies("lazy")
     gen = ROOT / "build" / "gen"
     d = tmp_path_factory.mktemp("san")
     probe = d / "probe.c"

@@ -1,4 +1,4 @@
-"""CPU-tier checks of the LU's boundary (np_linalg.hip, host/numpower_linalg.cpp): the new C-ABI names are declared,
+"""CPU-tier checks of the LU's boundary (np_lu.hip, host/numpower_linalg.cpp): the new C-ABI names are declared,
 prototyped and exported, the four host functions are declared with the reference's signatures (linalg.h) and
 exported, and their argument checks raise the reference's messages without touching a device."""
 import ctypes as C

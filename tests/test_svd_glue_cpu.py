@@ -1,4 +1,4 @@
-"""CPU-tier checks of the SVD's boundary (np_linalg.hip, ext/hip_linalg.c, host/numpower_linalg.cpp): np_svd / np_svdvals
+"""CPU-tier checks of the SVD's boundary (np_jacobi.hip, ext/hip_linalg.c, host/numpower_linalg.cpp): np_svd / np_svdvals
 and the sweep-cap knob are declared, prototyped and exported and refuse null arguments; NDArray_SVD / MatrixRank / Norm /
 Cond have the reference's signatures and messages; the --with-hip early-out is one edit in a list of its own, at the top of
 NDArray_SVD; svd_bodies shows a CPU operand reaching the reference's own code."""

@@ -1,4 +1,4 @@
-"""Timing of the device LU (np_linalg.hip): getrf, inverse and solve (one right-hand side) over n, after a GEMM warm-up
+"""Timing of the device LU (np_lu.hip): getrf, inverse and solve (one right-hand side) over n, after a GEMM warm-up
 that covers the clock ramp.  getrf is timed together with the copy that restores its input (2 n^2 floats, included).
 Prints ms per call, TFLOP/s (2/3 n^3 for getrf, 2 n^3 for the inverse, 2/3 n^3 + 2 n^2 for solve), kernel launches per
 call, and numpy's fp32 solve on the host for comparison (the median of a few calls after a warm-up call).  The share of the trailing GEMMs comes from a run under
@@ -20,7 +20,12 @@ use too.  Sizes of up to 64 are timed twice, on the one-launch path and with it 
 --eigh runs the symmetric eigensolver's leg (profiles/linalg/eigh_sweep.log): np_eigh and np_eigvalsh on the seeded random symmetric
 matrix of tests/eig_family.py, ms per call (the median of single calls after two untimed ones), sweeps taken, launches per call, the three metrics of tests/eig_family.py in
 n eps, np_svd of the same matrix in the same run (the same machinery plus a Gram step) and numpy's fp32 eigh on the host (median
-of five after a warm-up).  Sizes of up to 64 are timed on the blocked path too (np_debug_eigh_small_path)."""
+of five after a warm-up).  Sizes of up to 64 are timed on the blocked path too (np_debug_eigh_small_path).
+
+--digest times nothing: one line per call with its info and a sha256 of everything it wrote, for a fixed list of seeded inputs that
+reaches every path of the LU, the Cholesky, the SVD and the eigensolver (np_lu.hip, np_cholesky.hip, np_jacobi.hip).  Two builds
+of the library compute the same bits exactly when the two outputs are the same text: run it once as it is and once with
+NP_HIP_LIB=<the other libnp_hip.so>, each in a process of its own, and diff (profiles/linalg/split_digest.log)."""
 import argparse
 import ctypes as C
 import sys
@@ -37,6 +42,7 @@ ap.add_argument("--cholesky", action="store_true", help="the Cholesky leg: np_po
 ap.add_argument("--svd", action="store_true", help="the SVD leg: np_svd / np_svdvals against numpy's svd on the host")
 ap.add_argument("--eigh", action="store_true", help="the eigensolver's leg: np_eigh / np_eigvalsh against np_svd and numpy's eigh")
 ap.add_argument("--accuracy", action="store_true", help="with --svd: the accuracy table of the bound tests' inputs")
+ap.add_argument("--digest", action="store_true", help="no timing: info and a sha256 of the outputs of a fixed list of calls")
 ap.add_argument("--reps", type=int, default=0, help="0: as many as fit ~0.5 s per size (at least 3)")
 ap.add_argument("--no-host", action="store_true", help="skip numpy's solve on the host")
 args = ap.parse_args()
@@ -70,6 +76,95 @@ def timed(fn, reps):
         fn()
     t.stop()
     return t.elapsed_ms() / reps, per_call
+
+
+if args.digest:
+    import hashlib
+    from tests import eig_family as E
+    from tests import svd_family as F
+
+    def line(name, info, outs):
+        h = hashlib.sha256()
+        for o in outs:
+            h.update(np.ascontiguousarray(o.to_host()).tobytes())
+        print("%-44s info %-6d sha256 %s" % (name, info, h.hexdigest()), flush=True)
+
+    def dev_int(d):
+        return int(d.to_host().view(np.int32).reshape(-1)[0])
+
+    ih = C.c_int()
+    # LU: the LDS path and its edge (5, 128), the first blocked size, a ragged last panel, two rows per thread in the panel
+    for n in (5, 128, 129, 200, 1030):
+        rng = np.random.default_rng(51000 + n)
+        g = rng.standard_normal((n, n)).astype(np.float32)
+        b3 = rng.standard_normal((n, 3)).astype(np.float32)
+        for tag, a in (("gaussian", g), ("gaussian + n I", g + np.float32(n) * np.eye(n, dtype=np.float32))):
+            da = D.DeviceArray.from_host(a)
+            o1, o2, o3, det = D.DeviceArray((n, n)), D.DeviceArray((n, n)), D.DeviceArray((n, n)), D.DeviceArray((1,))
+            check(lib.np_det(da.ptr, n, det.ptr))
+            line("np_det %d %s" % (n, tag), 0, [det])
+            check(lib.np_inverse(da.ptr, n, o1.ptr, C.byref(ih)))
+            line("np_inverse %d %s" % (n, tag), ih.value, [o1])
+            for nrhs in (1, 3):
+                db, dx = D.DeviceArray.from_host(np.ascontiguousarray(b3[:, :nrhs])), D.DeviceArray((n, nrhs))
+                check(lib.np_solve(da.ptr, db.ptr, n, nrhs, dx.ptr, C.byref(ih)))
+                line("np_solve %d nrhs %d %s" % (n, nrhs, tag), ih.value, [dx])
+                db.free()
+                dx.free()
+            check(lib.np_lu(da.ptr, n, o1.ptr, o2.ptr, o3.ptr))
+            line("np_lu %d %s" % (n, tag), 0, [o1, o2, o3])
+            for d in (da, o1, o2, o3, det):
+                d.free()
+    # Cholesky: the single-kernel path, the first blocked size, ragged, several strips (a Gaussian's lower triangle fails: info > 0)
+    for n in (64, 65, 200, 600):
+        g = np.random.default_rng(52000 + n).standard_normal((n, n)).astype(np.float32)
+        for tag, a in (("gaussian", g), ("gaussian + n I", g + np.float32(n) * np.eye(n, dtype=np.float32))):
+            da, work, out, info = D.DeviceArray.from_host(a), D.DeviceArray((n, n)), D.DeviceArray((n, n)), D.DeviceArray((1,))
+            check(lib.np_memcpy_d2d(work.ptr, da.ptr, 4 * n * n))
+            check(lib.np_potrf(work.ptr, n, info.ptr))
+            line("np_potrf %d %s" % (n, tag), dev_int(info), [work])
+            check(lib.np_memset0(out.ptr, 4 * n * n))   # past a failing column np_cholesky leaves what was there
+            check(lib.np_cholesky(da.ptr, n, out.ptr, C.byref(ih)))
+            line("np_cholesky %d %s" % (n, tag), ih.value, [out])
+            for d in (da, work, out, info):
+                d.free()
+    # SVD: the one-launch path, then the blocked one (64 x 64 with the one-launch path off first)
+    svd_cases = [((1, 1), 1), ((3, 7), 1), ((64, 64), 1), ((64, 64), 0), ((65, 65), 1), ((64, 200), 1), ((200, 64), 1), ((130, 64), 1),
+                 ((300, 300), 1), ((129, 257), 1)]
+    for (m, n), small in svd_cases:
+        a = F.shifted_square(n) if m == n and n != 300 else F.gaussian(m, n)
+        k = min(m, n)
+        da, du, ds, dv = D.DeviceArray.from_host(a), D.DeviceArray((m, k)), D.DeviceArray((k,)), D.DeviceArray((k, n))
+        note = "" if small else " small path off"
+        check(lib.np_debug_svd_small_path(small))
+        check(lib.np_svd(da.ptr, m, n, du.ptr, ds.ptr, dv.ptr, C.byref(ih)))
+        line("np_svd %d x %d%s" % (m, n, note), ih.value, [du, ds, dv])
+        check(lib.np_svdvals(da.ptr, m, n, ds.ptr, C.byref(ih)))
+        line("np_svdvals %d x %d%s" % (m, n, note), ih.value, [ds])
+        check(lib.np_debug_svd_small_path(1))
+        for d in (da, du, ds, dv):
+            d.free()
+    # eigensolver: the one-launch path, then the blocked one
+    eigh_cases = [(E.random_symmetric, n, 1) for n in (1, 5, 64)] + [(E.random_symmetric, 64, 0)]
+    eigh_cases += [(E.random_symmetric, n, 1) for n in (65, 130, 257)] + [(E.graded, 130, 1)]
+    for family, n, small in eigh_cases:
+        da, dw, dv = D.DeviceArray.from_host(family(n)), D.DeviceArray((n,)), D.DeviceArray((n, n))
+        note = "%s%s" % (family.__name__, "" if small else " small path off")
+        check(lib.np_debug_eigh_small_path(small))
+        check(lib.np_eigh(da.ptr, n, dw.ptr, dv.ptr, C.byref(ih)))
+        line("np_eigh %d %s" % (n, note), ih.value, [dw, dv])
+        check(lib.np_eigvalsh(da.ptr, n, dw.ptr, C.byref(ih)))
+        line("np_eigvalsh %d %s" % (n, note), ih.value, [dw])
+        check(lib.np_debug_eigh_small_path(1))
+        for d in (da, dw, dv):
+            d.free()
+    sym = E.random_symmetric(130)
+    for tag, a in (("symmetric", sym), ("not symmetric", np.triu(sym) + 2 * np.tril(sym, -1))):
+        da = D.DeviceArray.from_host(np.ascontiguousarray(a, dtype=np.float32))
+        check(lib.np_symmetry_mismatch(da.ptr, 130, C.byref(ih)))
+        print("%-44s any  %d" % ("np_symmetry_mismatch 130 %s" % tag, ih.value), flush=True)
+        da.free()
+    sys.exit(0)
 
 
 # clock ramp: ~1 s of 4096^3 GEMMs
