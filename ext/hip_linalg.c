@@ -1,5 +1,5 @@
 /*
- * hip_linalg.c — the device side of NDArray_Det / Inverse / LU / Solve / Cholesky / SVD / Eig (hip_linalg.h).  Compiled into a --with-hip tree
+ * hip_linalg.c — the device side of NDArray_Det / Inverse / LU / Solve / Cholesky / SVD / Eig / Qr / Lstsq (hip_linalg.h).  Compiled into a --with-hip tree
  * against the reference's headers (-DNUMPOWER_NDARRAY_HEADER='"src/initializers.h"') and into libnumpower_host.so
  * against include/numpower_host.h; it uses only what both declare, with one switch: the reference's arrays take ownership of
  * an emalloc'd shape and its result vectors are emalloc'd, the host library copies shapes and hands out malloc'd vectors.
@@ -10,6 +10,7 @@
 #include NUMPOWER_NDARRAY_HEADER
 
 #include <stddef.h>
+#include <stdio.h>
 
 #include "hip_linalg.h"
 #include "np_ext_hooks.h"
@@ -237,4 +238,73 @@ NDArray **NPH_Eig(NDArray *a) {
     rtns[0] = w;
     rtns[1] = v;
     return rtns;
+}
+
+NDArray **NPH_Qr(NDArray *a) {
+    if (a == NULL) return NULL;
+    /* the reference returns NULL without a message in both cases (linalg.c:916-926), which its PHP_METHOD then dereferences */
+    if (NDArray_NDIM(a) != 2) {
+        np_ext_throw("qr: the operand must be two-dimensional");
+        return NULL;
+    }
+    if (NDArray_SHAPE(a)[0] < NDArray_SHAPE(a)[1]) {
+        np_ext_throw("qr: the operand must have at least as many rows as columns (m >= n)");
+        return NULL;
+    }
+    if (!on_gpu(a)) return NULL;
+    const int m = NDArray_SHAPE(a)[0], n = NDArray_SHAPE(a)[1];
+    /* the reference's shapes and order (linalg.c:929-968): rtn[0] = Q (m, n), rtn[1] = R (n, n); Q is the reduced orthonormal
+     * factor (np_qr), not the packed reflectors the reference's CPU path hands back */
+    NDArray *q = zeros_on_gpu(2, m, n), *r = zeros_on_gpu(2, n, n);
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 2);
+    int ok = q != NULL && r != NULL && rtns != NULL;
+    if (ok && np_qr(NDArray_FDATA(a), (size_t) m, (size_t) n, NDArray_FDATA(q), NDArray_FDATA(r)) != NP_OK) {
+        np_ext_throw_last();
+        ok = 0;
+    }
+    if (!ok) {
+        if (q != NULL) NDArray_FREE(q);
+        if (r != NULL) NDArray_FREE(r);
+        if (rtns != NULL) NPH_RELEASE(rtns);
+        return NULL;
+    }
+    rtns[0] = q;
+    rtns[1] = r;
+    return rtns;
+}
+
+NDArray *NPH_Lstsq(NDArray *a, NDArray *b) {
+    if (a == NULL || b == NULL) return NULL;
+    if (NDArray_NDIM(a) != 2 || NDArray_NDIM(b) != 2 || NDArray_SHAPE(a)[0] != NDArray_SHAPE(b)[0]) {   /* linalg.c:856-859 */
+        np_ext_throw("Invalid dimensions to calculate lstsq, both arrays must have 2 dimensions and $b must contain the same "
+                     "amount of rows as $a");
+        return NULL;
+    }
+    if (NDArray_DEVICE(a) != NDArray_DEVICE(b)) {
+        np_ext_throw("lstsq: both operands must be on the same device");
+        return NULL;
+    }
+    if (!on_gpu(a)) return NULL;
+    const int m = NDArray_SHAPE(a)[0], n = NDArray_SHAPE(a)[1], nrhs = NDArray_SHAPE(b)[1];
+    if (m < n) {   /* the reference's sgels answers with the minimum-norm solution there */
+        np_ext_throw("lstsq: the device solver needs at least as many rows as columns (m >= n); an underdetermined system goes "
+                     "through ->cpu() and the reference's own LAPACK path");
+        return NULL;
+    }
+    NDArray *x = zeros_on_gpu(2, n, nrhs);                                       /* linalg.c:865-868 */
+    if (x == NULL) return NULL;
+    int info = 0;
+    if (np_lstsq(NDArray_FDATA(a), NDArray_FDATA(b), (size_t) m, (size_t) n, (size_t) nrhs, NDArray_FDATA(x), &info) != NP_OK) {
+        np_ext_throw_last();
+        NDArray_FREE(x);
+        return NULL;
+    }
+    if (info > 0) {                                                              /* linalg.c:882-886 */
+        char msg[160];
+        snprintf(msg, sizeof msg, "The diagonal element %i of the triangular factor of $a is zero, so that $a does not have full rank.", info);
+        np_ext_throw(msg);
+        NDArray_FREE(x);
+        return NULL;
+    }
+    return x;
 }

@@ -26,6 +26,11 @@
  *
  *     NDArray_Eig      behind its squareness check, before its first allocation   return NPH_Eig(a);
  *
+ * and, only under the tool's --qr, one each into NDArray_Lstsq and NDArray_Qr, in front of their "not implemented for GPU" throws:
+ *
+ *     NDArray_Lstsq    at the top, before its GPU throw             return NPH_Lstsq(a, b);
+ *     NDArray_Qr       at the top, before its GPU throw             return NPH_Qr(a);
+ *
  * each guarded by `#ifdef HAVE_NP_HIP` and NPH_LINALG_TAKES: CPU operands fall through to the reference's LAPACK code.
  * The cuda_det_float / cuda_matrix_float_inverse stubs of hip_math.c are never reached in such a tree.
  *
@@ -68,6 +73,16 @@ struct NDArray **NPH_SVD(struct NDArray *a);
  * or not square: "Error: Input matrix is not square.\n"; a[i][j] != a[j][i] anywhere: refused, the message says that the device
  * solver is a symmetric eigensolver and that a general matrix goes through ->cpu(); the sweep cap reached: a message that names it. */
 struct NDArray **NPH_Eig(struct NDArray *a);
+/* the vector {Q (m, n), R (n, n)} of a (m, n) with m >= n, allocated as NPH_SVD allocates its own: the reduced factorization
+ * (np_qr), Q with orthonormal columns, R upper triangular with a strict lower triangle of +0.0f and a diagonal of either sign.
+ * Not the reference's CPU result, which holds the packed reflectors in place of Q.  Not 2-d, or m < n: an error with a message
+ * of this project's (the reference returns NULL without one). */
+struct NDArray **NPH_Qr(struct NDArray *a);
+/* x (n, nrhs) minimising ||a x - b|| for a (m, n), m >= n, and b (m, nrhs) (np_lstsq).  Shapes: "Invalid dimensions to calculate
+ * lstsq, both arrays must have 2 dimensions and $b must contain the same amount of rows as $a"; a zero on R's diagonal: "The
+ * diagonal element %i of the triangular factor of $a is zero, so that $a does not have full rank."; one operand on each
+ * device and m < n are refused. */
+struct NDArray *NPH_Lstsq(struct NDArray *a, struct NDArray *b);
 
 #ifdef __cplusplus
 }

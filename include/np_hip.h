@@ -482,6 +482,37 @@ int np_eigh(const float *a, size_t n, float *w, float *v, int *info_host);
 int np_eigvalsh(const float *a, size_t n, float *w, int *info_host);
 int np_symmetry_mismatch(const float *a, size_t n, int *host_any);
 
+/* ---- Householder QR and least squares (np_qr.hip; DESIGN.md "qr") -----------------------------------
+ * Blocked compact-WY Householder QR of a: m x n fp32, ROW-MAJOR, m >= n; what the reference refuses for GPU arrays
+ * ("ndarray::qr not implemented for GPU", "ndarray::lstsq not implemented for GPU", linalg.c:850, 910).
+ * Convention: LAPACK's sgeqr2 / slarfg.  H_j = I - tau_j v_j v_j^T with v_j[j] = 1.  With alpha = a_jj and x the part of
+ * column j below the diagonal: beta = -sign(alpha) ||(alpha, x)||_2 with sign(+0) = sign(-0) = +, tau_j = (beta - alpha) / beta,
+ * v_j = x / (alpha - beta), R_jj = beta.  A zero sub-column (x == 0 exactly) gives tau_j = 0, H_j = I and R_jj = alpha.
+ * R's diagonal is not normalised: it is not made positive, and Q's columns carry the matching signs.
+ * np_geqrf: in place.  R on and above the diagonal, v_j below it (its leading 1 implied), tau: n device floats.
+ * np_qr: the reduced factorization, numpy.linalg.qr's mode='reduced': q (m x n) = H_0 ... H_{n-1} I[:, :n], r (n x n) with a
+ * strict lower triangle of exact +0.0f.  a is untouched; q and r must not overlap a.
+ *   Different from the reference's CPU qr on purpose: its NDArray_Qr calls sgeqrf and never sorgqr, and hands the packed
+ *   reflectors back as "Q".  The device qr returns the mathematically defined Q (Q^T Q = I, Q R = a).
+ * np_lstsq: x (n x nrhs) minimises ||a x - b||_2 for b m x nrhs: C = Q^T b by applying the reflectors in order, then
+ * x = R^-1 C[:n] by back-substitution.  *info_host (host int): 0, or j + 1 for the first j with R_jj == 0 exactly; then x
+ * is not written (LAPACK sgels' rule: a does not have full rank).  Blocks until info is known.  a and b are untouched.
+ * m < n is refused by all three with NP_ERR_INVALID before any device work (the reference's NDArray_Qr requires m >= n as well;
+ * the minimum-norm branch of sgels for m < n is out of scope).  Null pointers are NP_ERR_INVALID.  n == 0 (and nrhs == 0) does nothing.
+ * Limits: m <= 16777216, n <= 65536, nrhs < 2^31; larger sizes are refused, not truncated.
+ * The panel (one workgroup per kNB = 64 columns) accumulates the column norm and every v . x inner product in fp64 and rounds once:
+ * the factorization is invariant under power-of-two scaling of a (Q bit for bit, R times the power) and entries of 2^+-62
+ * neither overflow nor flush in the squares.  The trailing updates, the formation of Q and Q^T b run on the MFMA GEMM.
+ * Non-finite input: there is no iteration, the call finishes with NP_OK and NaN / Inf propagate; np_lstsq reports info only
+ * for an exact zero on R's diagonal.
+ * Scratch (caching pool, released on every path): V (m x 64), V^T (64 x m), two 64 x max(n, nrhs) matrices, 8192 floats per panel
+ * for T and T^T; np_qr and np_lstsq add a copy of a (np_lstsq also one of b).
+ * Library stream, no float atomics, every fold in a fixed order: bit-identical from run to run.
+ * Speed and the crossover with the host's LAPACK: DESIGN.md §3.13, profiles/linalg/qr_sweep.log. */
+int np_geqrf(float *a, size_t m, size_t n, float *tau);
+int np_qr(const float *a, size_t m, size_t n, float *q, float *r);
+int np_lstsq(const float *a, const float *b, size_t m, size_t n, size_t nrhs, float *x, int *info_host);
+
 /* ---- 2-D correlation and convolution (np_signal.hip; DESIGN.md "convolve2d") ------------------------
  * scipy.signal.correlate2d(a, b, mode, boundary, fillvalue) for real fp32 arrays, ROW-MAJOR, and with flip != 0
  * scipy.signal.convolve2d: what the loop of the reference's signal.c:152-207 computes, which the reference refuses for

@@ -347,6 +347,18 @@ NDArray *NDArray_Cond(NDArray *a);
  * that names the sweep cap when the iteration did not converge. */
 NDArray **NDArray_Eig(NDArray *a);
 
+/* ---- Householder QR and least squares (host/numpower_linalg.cpp; linalg.c:848-899, 908-970) ----
+ * NDArray_Qr     malloc'd vector {Q (m, n), R (n, n)} for a (m, n) with m >= n: the reduced factorization (np_qr), Q^T Q = I,
+ *                Q R = a, R upper triangular with a strict lower triangle of +0.0f and a diagonal of either sign.  NOT what the
+ *                reference's CPU path returns: that calls sgeqrf without sorgqr and hands the packed reflectors back as Q.
+ * NDArray_Lstsq  x (n, nrhs) minimising ||a x - b|| for a (m, n), m >= n, and b (m, nrhs) (np_lstsq).
+ * GPU operands only, views made contiguous.  Errors: qr of a non-2-D operand or with m < n (this project's messages; the
+ * reference returns NULL without one); "Invalid dimensions to calculate lstsq, both arrays must have 2 dimensions and $b must
+ * contain the same amount of rows as $a"; "The diagonal element %i of the triangular factor of $a is zero, so that $a does not
+ * have full rank."; lstsq with one operand on each device or with m < n is refused. */
+NDArray **NDArray_Qr(NDArray *a);
+NDArray *NDArray_Lstsq(NDArray *a, NDArray *b);
+
 /* ---- 2-D correlation and convolution (host/numpower_signal.cpp; signal.c:217-303) ----
  * NDArray_Correlate2D  scipy.signal.correlate2d(a, b, mode, boundary, fillvalue) of two 2-D GPU arrays, with flip != 0
  *                      scipy.signal.convolve2d; mode 0 valid / 1 same / 2 full, boundary 0 fill / 4 symm / 8 wrap (signal.h).

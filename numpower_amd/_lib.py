@@ -141,6 +141,9 @@ PROTOTYPES = {
     "np_eigh": (C.c_int, [_f32p, C.c_size_t, _f32p, _f32p, C.POINTER(C.c_int)]),
     "np_eigvalsh": (C.c_int, [_f32p, C.c_size_t, _f32p, C.POINTER(C.c_int)]),
     "np_symmetry_mismatch": (C.c_int, [_f32p, C.c_size_t, C.POINTER(C.c_int)]),
+    "np_geqrf": (C.c_int, [_f32p, C.c_size_t, C.c_size_t, _f32p]),
+    "np_qr": (C.c_int, [_f32p, C.c_size_t, C.c_size_t, _f32p, _f32p]),
+    "np_lstsq": (C.c_int, [_f32p, _f32p, C.c_size_t, C.c_size_t, C.c_size_t, _f32p, C.POINTER(C.c_int)]),
     "np_correlate2d_shape": (C.c_int, [C.c_size_t] * 4 + [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "np_correlate2d": (C.c_int, [_f32p, C.c_size_t, C.c_size_t, _f32p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int, _f32p]),
     "np_permute": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

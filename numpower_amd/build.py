@@ -30,7 +30,7 @@ LIBDIR = ROOT / "numpower_amd" / "lib"
 OBJDIR = ROOT / "build" / "obj"
 
 HIP_SOURCES = ["np_runtime.hip", "np_elementwise.hip", "np_fused_static.hip", "np_reduce.hip", "np_sgemm.hip", "np_layout.hip",
-               "np_select.hip", "np_comm.hip", "np_lu.hip", "np_cholesky.hip", "np_jacobi.hip", "np_signal.hip"]
+               "np_select.hip", "np_comm.hip", "np_lu.hip", "np_cholesky.hip", "np_jacobi.hip", "np_signal.hip", "np_qr.hip"]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{INCLUDE}", f"-I{CSRC}"]
 
 
@@ -164,8 +164,8 @@ def build_method_bodies(force: bool = False, verbose: bool = False) -> Path:
 # The programs tools/apply_with_hip.py wraps around the text it inserts into the reference: <name>_program_source()
 # -> build/gen/<name>_bodies.c -> numpower_amd/lib/<name>_bodies, in the order build_all compiles them.  fast_path: the
 # device-dispatching L2 functions; lazy: the pending chains around a stand-in for the Zend object table; linalg: NDArray_Det /
-# Inverse / LU / Solve; cholesky, svd, eig: NDArray_Cholesky / _SVD / _Eig; signal: NDArray_Correlate2D.
-BODIES = ("fast_path", "lazy", "linalg", "cholesky", "svd", "eig", "signal")
+# Inverse / LU / Solve; cholesky, svd, eig: NDArray_Cholesky / _SVD / _Eig; signal: NDArray_Correlate2D; qr: NDArray_Qr / _Lstsq.
+BODIES = ("fast_path", "lazy", "linalg", "cholesky", "svd", "eig", "signal", "qr")
 _apply_with_hip = None
 
 

@@ -1,7 +1,8 @@
 // NDArray_Det / NDArray_Inverse / NDArray_LU / NDArray_Solve (linalg.c:253, 584, 620, 981) on the device LU, and
 // NDArray_Cholesky (linalg.c:1056) on the device Cholesky factorization, NDArray_SVD / NDArray_MatrixRank / NDArray_Norm /
 // NDArray_Cond (linalg.c:111, 668, 402-470, 1038) on the device Jacobi SVD, NDArray_Eig (linalg.c:795) on the
-// device symmetric eigensolver.
+// device symmetric eigensolver, NDArray_Qr / NDArray_Lstsq (linalg.c:909, 849) on the device Householder QR
+// (DESIGN.md §3.13).
 // The work — argument checks, the reference's messages, the np_det / np_inverse / np_lu / np_solve / np_cholesky calls — is
 // ext/hip_linalg.c, the same code a --with-hip tree reaches through the early-outs tools/apply_with_hip.py inserts into
 // the reference's functions; here strided views are first made contiguous (numpower_host_contiguous).
@@ -127,6 +128,20 @@ NDArray **NDArray_Eig(NDArray *a) {   // linalg.c:795-838: the vector is malloc'
     if (!a) return nullptr;
     Operand ca(a);
     return ca.arr ? NPH_Eig(ca.arr) : nullptr;
+}
+
+NDArray **NDArray_Qr(NDArray *a) {   // linalg.c:908-970: the vector is malloc'd here; {Q (m, n) reduced, R (n, n)}, m >= n
+    if (!a) return nullptr;
+    Operand ca(a);
+    return ca.arr ? NPH_Qr(ca.arr) : nullptr;
+}
+
+NDArray *NDArray_Lstsq(NDArray *a, NDArray *b) {   // linalg.c:848-899, m >= n
+    if (!a || !b) return nullptr;
+    Operand ca(a);
+    if (!ca.arr) return nullptr;
+    Operand cb(b);
+    return cb.arr ? NPH_Lstsq(ca.arr, cb.arr) : nullptr;
 }
 
 NDArray *NDArray_MatrixRank(NDArray *target, float *tol) {   // linalg.c:668-715, on the singular values alone

@@ -155,6 +155,8 @@ def _load_host():
     sig["NDArray_Correlate2D"] = (_P, [_P, _P, C.c_int, C.c_int, _P, C.c_int])
     sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
     sig["NDArray_Eig"] = (C.POINTER(_P), [_P])
+    sig["NDArray_Qr"] = (C.POINTER(_P), [_P])
+    sig["NDArray_Lstsq"] = (_P, [_P, _P])
     sig["NDArray_MatrixRank"] = (_P, [_P, fp])
     sig["NDArray_Norm"] = (_P, [_P, C.c_int])
     sig["NDArray_Cond"] = (_P, [_P])
@@ -783,6 +785,24 @@ class NDArray:
         out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(2))
         _libc_free(C.cast(rtns, C.c_void_p))
         return out
+
+    @staticmethod
+    def qr(a):               # numpower.c PHP_METHOD(qr): RETURN_2NDARRAY -> (Q (m, n) with orthonormal columns, R (n, n) upper triangular); m >= n
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        rtns = h.NDArray_Qr(x._p)
+        if not rtns:
+            _raise_pending(h)
+        out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(2))
+        _libc_free(C.cast(rtns, C.c_void_p))
+        return out
+
+    @staticmethod
+    def lstsq(a, b):         # numpower.c PHP_METHOD(lstsq): x (n, nrhs) minimising ||a x - b||; m >= n
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        y, _ = NDArray._coerce(b)
+        return NDArray._wrap(h.NDArray_Lstsq(x._p, y._p))
 
     @staticmethod
     def matrix_rank(a, tol=None):   # PHP_METHOD(matrix_rank): singular values > tol (default s_max * max(m, n) * FLT_EPSILON)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """apply_with_hip.py — turn a NumPower checkout into a `--with-hip` tree (INTEGRATION.md sections 2a and 2b, as code).
 
-    python tools/apply_with_hip.py [--keep-cuda] [--no-signal] [--eig] <NumPower checkout> <output directory>
+    python tools/apply_with_hip.py [--keep-cuda] [--no-signal] [--eig] [--qr] <NumPower checkout> <output directory>
 
 Copies the checkout to <output directory>, applies every edit of INTEGRATION.md section 2a by ANCHORED regex and
 copies the glue (ext/*.c, ext/*.h, include/np_hip.h) to <output>/src/hip/.  Every edit names its file, the exact
@@ -570,6 +570,31 @@ EIG_EDITS = [
          "}", after=True, context="NDArray *a = 0;"),
 ]
 
+# ---- section 2b, qr / lstsq: the reference's NDArray_Lstsq and NDArray_Qr throw "ndarray::lstsq not implemented for GPU" and
+# "ndarray::qr not implemented for GPU"; each early-out sits in front of that throw and replaces nothing.  Like EIG_EDITS a list of
+# its own that is NOT part of EDITS, handed to apply() as `extra`; main() passes it only under --qr, so the counts of the default
+# command line stay what they were.  Its text runs as a program of its own (qr_bodies) ----
+QR_EDITS = [
+    Edit("src/ndmath/linalg.c", "linalg.c:849 NDArray_Lstsq: GPU early-out",
+         r"^(?P<old>NDArray_Lstsq\(NDArray \*a, NDArray \*b\) \{)"
+         r"(?=\n[ \t]*if \(NDArray_DEVICE\(a\) == NDARRAY_DEVICE_GPU \|\| NDArray_DEVICE\(b\) == NDARRAY_DEVICE_GPU\) \{\n"
+         r"[ \t]*zend_throw_error\(NULL, \"ndarray::lstsq not implemented for GPU\"\);)",
+         "    /* numpower_amd 2b: GPU operands are solved on the device (np_lstsq, ext/hip_linalg.c; one operand on each device is\n"
+         "     * refused there); two CPU operands fall through to the reference's LAPACK code below, untouched */\n"
+         "    if (NPH_LINALG_TAKES(a) || NPH_LINALG_TAKES(b)) {\n"
+         "        return NPH_Lstsq(a, b);\n"
+         "    }", after=True, context="NDArray *a = 0, *b = 0;"),   # behind the function's opening line: indented by hand
+    Edit("src/ndmath/linalg.c", "linalg.c:909 NDArray_Qr: GPU early-out",
+         r"^(?P<old>NDArray_Qr\(NDArray \*a\) \{)"
+         r"(?=\n[ \t]*if \(NDArray_DEVICE\(a\) == NDARRAY_DEVICE_GPU\) \{\n"
+         r"[ \t]*zend_throw_error\(NULL, \"ndarray::qr not implemented for GPU\"\);)",
+         "    /* numpower_amd 2b: a GPU operand is factored on the device (np_qr, ext/hip_linalg.c: the reduced Q and R); a CPU\n"
+         "     * operand falls through to the reference's LAPACK code below, untouched */\n"
+         "    if (NPH_LINALG_TAKES(a)) {\n"
+         "        return NPH_Qr(a);\n"
+         "    }", after=True, context="NDArray *a = 0;"),   # behind the function's opening line: indented by hand
+]
+
 CONTEXTS = {
     "ndarray.c:1055-1060 NDArray_ToGPU: H2D copy": "float *tmp_gpu = 0; NDArray *target = 0;",
     "ndarray.c:1090 NDArray_ToCPU: D2H copy": "NDArray *rtn = 0, *target = 0;",
@@ -863,6 +888,29 @@ def eig_program_source() -> str:
     return "\n".join(o)
 
 
+def qr_program_source() -> str:
+    """A C99 PROGRAM around the text QR_EDITS inserts into linalg.c: NDArray_Lstsq and NDArray_Qr with the reference's signatures,
+    the inserted text VERBATIM, then a stand-in for the reference's own code (its GPU throw and LAPACK calls) that only counts how
+    often it is reached.  Built and linked like eig_bodies.
+
+        qr_bodies cpu    CPU operands fall through to the stand-in, no device is touched
+        qr_bodies gpu    GPU operands never fall through: a known exact answer with the reference's shapes (Q (m, n), R (n, n)), the
+                         exact least-squares solution, the rank and shape messages, no device allocation leaks
+    """
+    lstsq, qr = QR_EDITS
+    o = ["/* generated by tools/apply_with_hip.py: qr_program_source() — do not edit */",
+         "#include <stdio.h>", "#include <stdlib.h>", "#include <string.h>", "",
+         "#define HAVE_NP_HIP 1", '#include "numpower_host.h"', '#include "hip_linalg.h"', "",
+         "static int g_fell_through;   /* calls that reached the reference's own code (the stand-ins below) */",
+         "static void *reference_body(void) { g_fell_through++; return NULL; }", "",
+         "static NDArray *patched_NDArray_Lstsq(NDArray *a, NDArray *b) {", "#ifdef HAVE_NP_HIP", _indent(lstsq.new, ""), "#endif",
+         "    return (NDArray *) reference_body();", "}", "",
+         "static NDArray **patched_NDArray_Qr(NDArray *a) {", "#ifdef HAVE_NP_HIP", _indent(qr.new, ""), "#endif",
+         "    return (NDArray **) reference_body();", "}", ""]
+    o.append(_QR_PROGRAM_MAIN)
+    return "\n".join(o)
+
+
 def signal_program_source() -> str:
     """A C99 PROGRAM around the text SIGNAL_EDITS inserts into signal.c: NDArray_Correlate2D with the reference's signature, the
     inserted text VERBATIM, then a stand-in for the reference's own code (its GPU throw and its CPU loop) that only counts how
@@ -963,6 +1011,82 @@ int main(int argc, char **argv) {
         if (all[i]) NDArray_FREE(all[i]);
     if (gpu) CHECK(NDArray_LiveDeviceAllocations() == live0, "%ld device allocations leaked", NDArray_LiveDeviceAllocations() - live0);
     printf("signal_bodies %s: %d calls reached the reference's own code, %d failures\n", argv[1], g_fell_through, g_failures);
+    return g_failures ? 1 : 0;
+}
+"""
+
+
+_QR_PROGRAM_MAIN = r"""static int g_failures;
+#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "qr_bodies: " __VA_ARGS__); fprintf(stderr, "\n"); g_failures++; } } while (0)
+
+static NDArray *make(const float *v, int rows, int cols, int gpu) {
+    int shape[2] = {rows, cols};
+    NDArray *h = NDArray_FromHostBuffer(v, shape, cols ? 2 : 1);
+    if (!gpu) return h;
+    NDArray *d = NDArray_ToGPU(h);
+    NDArray_FREE(h);
+    return d;
+}
+
+/* true when r has the shape rows x cols and exactly the values of want */
+static int is(NDArray *r, int rows, int cols, const float *want) {
+    float got[16];
+    int ok = r && NDArray_NDIM(r) == 2 && NDArray_SHAPE(r)[0] == rows && NDArray_SHAPE(r)[1] == cols && rows * cols <= 16;
+    NDArray *h = ok ? NDArray_ToCPU(r) : NULL;
+    ok = ok && h && NDArray_CopyToHostBuffer(h, got) == 0;
+    for (int i = 0; ok && i < rows * cols; ++i) ok = got[i] == want[i];
+    if (h) NDArray_FREE(h);
+    return ok;
+}
+
+static int raised(const void *r, const char *message) {
+    return r == NULL && strcmp(numpower_host_last_error(), message) == 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc < 2 || (strcmp(argv[1], "cpu") && strcmp(argv[1], "gpu"))) {
+        fprintf(stderr, "usage: qr_bodies cpu|gpu\n");
+        return 2;
+    }
+    const int gpu = strcmp(argv[1], "gpu") == 0;
+    /* a32 = H [[-1, 3], [0, 2], [0, 0]] with H the exchange of rows 0 and 1: every step of the factorization is exact */
+    const float a32[6] = {0, 2, -1, 3, 0, 0}, b31[3] = {-4, -7, 5}, low32[6] = {1, 1, 0, 0, 0, 0}, wide23[6] = {1, 2, 3, 4, 5, 6};
+    const float v3[3] = {1, 2, 3};
+    const long live0 = gpu ? NDArray_LiveDeviceAllocations() : 0;
+    NDArray *a = make(a32, 3, 2, gpu), *b = make(b31, 3, 1, gpu), *low = make(low32, 3, 2, gpu), *wide = make(wide23, 2, 3, gpu);
+    NDArray *vec = make(v3, 3, 0, gpu), *b_host = make(b31, 3, 1, 0);
+    NDArray **r = patched_NDArray_Qr(a);
+    NDArray *x = patched_NDArray_Lstsq(a, b);
+    if (!gpu) {
+        CHECK(!r && !x, "a CPU operand was computed on the device");
+        CHECK(g_fell_through == 2, "%d of 2 calls reached the reference's code", g_fell_through);
+    } else {
+        const float q_want[6] = {0, 1, 1, 0, 0, 0}, r_want[4] = {-1, 3, 0, 2}, x_want[2] = {1, -2};
+        CHECK(r && is(r[0], 3, 2, q_want), "Q of [[0, 2], [-1, 3], [0, 0]] differs from the exchange of its first two rows (3 x 2)");
+        CHECK(r && is(r[1], 2, 2, r_want), "R of [[0, 2], [-1, 3], [0, 0]] differs from [[-1, 3], [0, 2]]");
+        CHECK(is(x, 2, 1, x_want), "lstsq did not return (1, -2)");
+        CHECK(raised(patched_NDArray_Lstsq(low, b), "The diagonal element 2 of the triangular factor of $a is zero, so that $a does not have full rank."),
+              "a rank-deficient operand did not raise the reference's message");
+        CHECK(raised(patched_NDArray_Lstsq(a, wide), "Invalid dimensions to calculate lstsq, both arrays must have 2 dimensions and $b must contain the same amount of rows as $a"),
+              "3 rows against 2 did not raise the reference's message");
+        CHECK(raised(patched_NDArray_Lstsq(a, vec), "Invalid dimensions to calculate lstsq, both arrays must have 2 dimensions and $b must contain the same amount of rows as $a"),
+              "a 1-d right-hand side did not raise the reference's message");
+        CHECK(patched_NDArray_Lstsq(a, b_host) == NULL && strstr(numpower_host_last_error(), "same device"), "one operand on each device was not refused");
+        CHECK(patched_NDArray_Qr(wide) == NULL && strstr(numpower_host_last_error(), "m >= n"), "qr of a 2 x 3 operand was not refused");
+        CHECK(patched_NDArray_Qr(vec) == NULL && strstr(numpower_host_last_error(), "two-dimensional"), "qr of a 1-d operand was not refused");
+        CHECK(g_fell_through == 0, "%d GPU calls fell through to the reference's code", g_fell_through);
+    }
+    if (r) {
+        NDArray_FREE(r[0]);
+        NDArray_FREE(r[1]);
+        free(r);
+    }
+    if (x) NDArray_FREE(x);
+    NDArray *all[] = {a, b, low, wide, vec, b_host};
+    for (size_t i = 0; i < sizeof(all) / sizeof(all[0]); ++i)
+        if (all[i]) NDArray_FREE(all[i]);
+    if (gpu) CHECK(NDArray_LiveDeviceAllocations() == live0, "%ld device allocations leaked", NDArray_LiveDeviceAllocations() - live0);
+    printf("qr_bodies %s: %d calls reached the reference's own code, %d failures\n", argv[1], g_fell_through, g_failures);
     return g_failures ? 1 : 0;
 }
 """
@@ -2225,7 +2349,7 @@ class Applied(dict):
 
 
 def apply(checkout: Path, out: Path, keep_cuda: bool = False, extra=()):
-    """-> {edit description: times applied} for EDITS; the edits of `extra` (SIGNAL_EDITS, EIG_EDITS) are applied after them, file by file,
+    """-> {edit description: times applied} for EDITS; the edits of `extra` (SIGNAL_EDITS, EIG_EDITS, QR_EDITS) are applied after them, file by file,
     and reported in the result's .extra.  Raises PatchError on any anchor problem or leftover CUDA name."""
     if out.exists():
         raise PatchError("%s exists; give a fresh output directory" % out)
@@ -2258,8 +2382,8 @@ def apply(checkout: Path, out: Path, keep_cuda: bool = False, extra=()):
 
 def main(argv):
     keep_cuda = "--keep-cuda" in argv
-    extra = ([] if "--no-signal" in argv else SIGNAL_EDITS) + (EIG_EDITS if "--eig" in argv else [])
-    argv = [a for a in argv if a not in ("--keep-cuda", "--no-signal", "--eig")]
+    extra = ([] if "--no-signal" in argv else SIGNAL_EDITS) + (EIG_EDITS if "--eig" in argv else []) + (QR_EDITS if "--qr" in argv else [])
+    argv = [a for a in argv if a not in ("--keep-cuda", "--no-signal", "--eig", "--qr")]
     if len(argv) != 3:
         print(__doc__, file=sys.stderr)
         return 2

@@ -22,6 +22,13 @@ matrix of tests/eig_family.py, ms per call (the median of single calls after two
 n eps, np_svd of the same matrix in the same run (the same machinery plus a Gram step) and numpy's fp32 eigh on the host (median
 of five after a warm-up).  Sizes of up to 64 are timed on the blocked path too (np_debug_eigh_small_path).
 
+--qr runs the Householder QR's leg (profiles/linalg/qr_sweep.log): np_geqrf (timed with the copy that restores its input), np_qr and
+np_lstsq with one and with 64 right-hand sides on a seeded Gaussian matrix at the squares of --sizes and at 16384 x 128 and 65536 x 64,
+ms per call (the median of single calls after two untimed ones), TFLOP/s of np_geqrf over 2 n^2 (m - n / 3), launches per call, res and
+orth of np_qr's factors in sqrt(n) eps (tests/qr_family.py), np_getrf (squares) and np_svd (up to 4096 columns) of the same matrix in the same
+run, and the host's float32 QR: SciPy's (LAPACK sgeqrf + sorgqr) when it imports, otherwise numpy's, which computes in float64 and
+rounds.  --no-host times np_geqrf alone (a run under the profiler).
+
 --digest times nothing: one line per call with its info and a sha256 of everything it wrote, for a fixed list of seeded inputs that
 reaches every path of the LU, the Cholesky, the SVD and the eigensolver (np_lu.hip, np_cholesky.hip, np_jacobi.hip).  Two builds
 of the library compute the same bits exactly when the two outputs are the same text: run it once as it is and once with
@@ -41,6 +48,7 @@ ap.add_argument("--sizes", default=None, help="default 64,256,1024,4096,8192,163
 ap.add_argument("--cholesky", action="store_true", help="the Cholesky leg: np_potrf against np_getrf")
 ap.add_argument("--svd", action="store_true", help="the SVD leg: np_svd / np_svdvals against numpy's svd on the host")
 ap.add_argument("--eigh", action="store_true", help="the eigensolver's leg: np_eigh / np_eigvalsh against np_svd and numpy's eigh")
+ap.add_argument("--qr", action="store_true", help="the QR leg: np_geqrf / np_qr / np_lstsq against np_getrf, np_svd and the host's float32 QR")
 ap.add_argument("--accuracy", action="store_true", help="with --svd: the accuracy table of the bound tests' inputs")
 ap.add_argument("--digest", action="store_true", help="no timing: info and a sha256 of the outputs of a fixed list of calls")
 ap.add_argument("--reps", type=int, default=0, help="0: as many as fit ~0.5 s per size (at least 3)")
@@ -48,6 +56,8 @@ ap.add_argument("--no-host", action="store_true", help="skip numpy's solve on th
 args = ap.parse_args()
 if args.sizes is None and args.eigh:
     args.sizes = "8,32,64,128,256,512,1024,2048,4096"
+if args.sizes is None and args.qr:
+    args.sizes = "512,1024,2048,4096,8192"
 if args.sizes is None and args.svd:
     args.sizes = "8,32,64,256,1024,2048,4096"
 if args.sizes is None:
@@ -208,6 +218,84 @@ def residual_over_eps(a64, l):
     l64 = l.astype(np.float64)
     return float(np.abs(a64 - l64 @ l64.T).sum(axis=0).max() / np.abs(a64).sum(axis=0).max()) * 2.0 ** 23
 
+
+if args.qr:
+    from tests import qr_family as Q
+    try:
+        from scipy.linalg import qr as host_qr
+        host_name, host_kw = "scipy float32 qr (sgeqrf + sorgqr)", {"mode": "economic"}
+    except ImportError:
+        host_qr, host_name, host_kw = np.linalg.qr, "numpy qr (float64 arithmetic, rounded to float32)", {}
+
+    squares = [int(x) for x in args.sizes.split(",")]
+    shapes = [(n, n) for n in squares] + ([(16384, 128), (65536, 64)] if len(squares) > 1 else [])
+    print("%13s %9s %8s %8s %9s %11s %12s %9s %9s  %-15s %s" % ("m x n", "geqrf ms", "TFLOP/s", "launches", "np_qr ms", "lstsq(1) ms", "lstsq(64) ms",
+                                                               "getrf ms", "np_svd ms", "res / orth", "host " + host_name), flush=True)
+    for m, n in shapes:
+        a = Q.gaussian(m, n)
+        b = Q.gaussian(m, 64, 9)
+        da, work, dtau = D.DeviceArray.from_host(a), D.DeviceArray((m, n)), D.DeviceArray((n,))
+        ih = C.c_int()
+
+        def geqrf():
+            check(lib.np_memcpy_d2d(work.ptr, da.ptr, 4 * m * n))
+            check(lib.np_geqrf(work.ptr, m, n, dtau.ptr))
+
+        reps = args.reps or (5 if m * n <= 4096 * 4096 else 2)
+        g_ms, g_launches = timed_median(geqrf, reps)
+        cells = ["-"] * 6
+        host = "-"
+        if not args.no_host:
+            dq, dr = D.DeviceArray((m, n)), D.DeviceArray((n, n))
+            db1, db64 = D.DeviceArray.from_host(np.ascontiguousarray(b[:, :1])), D.DeviceArray.from_host(b)
+            dx = D.DeviceArray((n, 64))
+            piv, info = D.DeviceArray((n,)), D.DeviceArray((1,))
+
+            def qr():
+                check(lib.np_qr(da.ptr, m, n, dq.ptr, dr.ptr))
+
+            def lstsq1():
+                check(lib.np_lstsq(da.ptr, db1.ptr, m, n, 1, dx.ptr, C.byref(ih)))
+
+            def lstsq64():
+                check(lib.np_lstsq(da.ptr, db64.ptr, m, n, 64, dx.ptr, C.byref(ih)))
+
+            def getrf():
+                check(lib.np_memcpy_d2d(work.ptr, da.ptr, 4 * n * n))
+                check(lib.np_getrf(work.ptr, n, piv.ptr, info.ptr))
+
+            cells[0] = "%.3f" % timed_median(qr, reps)[0]
+            got = Q.growth(a, dq.to_host(), dr.to_host())
+            cells[1] = "%.3f" % timed_median(lstsq1, reps)[0]
+            cells[2] = "%.3f" % timed_median(lstsq64, reps)[0]
+            assert ih.value == 0
+            if m == n:
+                cells[3] = "%.3f" % timed_median(getrf, reps)[0]
+            if n <= 4096:
+                k = min(m, n)
+                du, ds, dv = D.DeviceArray((m, k)), D.DeviceArray((k,)), D.DeviceArray((k, n))
+
+                def svd():
+                    check(lib.np_svd(da.ptr, m, n, du.ptr, ds.ptr, dv.ptr, C.byref(ih)))
+
+                cells[4] = "%.3f" % timed_median(svd, 1 if n >= 2048 else 3)[0]
+                for d in (du, ds, dv):
+                    d.free()
+            cells[5] = "%.3f / %.3f" % (got["res"], got["orth"])
+            host_qr(a, **host_kw)                       # warm-up
+            ts = []
+            for _ in range(3):
+                h0 = time.perf_counter()
+                host_qr(a, **host_kw)
+                ts.append((time.perf_counter() - h0) * 1e3)
+            host = "%.3f ms (median of 3 after a warm-up)" % float(np.median(ts))
+            for d in (dq, dr, db1, db64, dx, piv, info):
+                d.free()
+        print("%6d x %-5d %9.3f %8.2f %8d %9s %11s %12s %9s %9s  %-15s %s" % (
+            m, n, g_ms, 2.0 * n * n * (m - n / 3.0) / g_ms / 1e9, g_launches, cells[0], cells[1], cells[2], cells[3], cells[4], cells[5], host), flush=True)
+        for d in (da, work, dtau):
+            d.free()
+    sys.exit(0)
 
 if args.eigh:
     from tests import eig_family as E
