@@ -20,7 +20,9 @@ dnl      ext/hip_math_drivers.c instead of src/ndmath/cuda/cuda_math.cu, ext/hip
 dnl      tools/apply_with_hip.py inserts into arithmetics.c / logic.c / ndarray.c call), ext/hip_lazy.c (the pending
 dnl      elementwise chains behind the NDArray handle: numpower.c's operators / unary methods append, buffer_get flushes),
 dnl      ext/hip_linalg.c (det / inv / lu / solve / cholesky / svd of GPU arrays), ext/hip_signal.c (correlate2d / convolve2d of
-dnl      GPU arrays: what the early-out in front of signal.c's GPU throw calls), ext/zend_hooks.c
+dnl      GPU arrays: what the early-out in front of signal.c's GPU throw calls), ext/hip_dnn.c (dnn_conv2d_forward / _backward of
+dnl      GPU arrays: what the early-outs `tools/apply_with_hip.py --dnn` puts at the top of dnn.c's two functions call; without
+dnl      them nothing reaches it), ext/zend_hooks.c
 
 PHP_ARG_WITH([hip],
   [for MI355X (HIP, gfx950) support through numpower_amd],
@@ -57,7 +59,7 @@ if test "$PHP_HIP" != "no"; then
   AC_DEFINE([HAVE_NP_HIP], [1], [the device back end is numpower_amd / MI355X])
 
   dnl glue sources, compiled by the ordinary C compiler together with the extension's own files
-  NP_HIP_GLUE="$PHP_HIP/ext/gpu_alloc_hip.c $PHP_HIP/ext/hip_math.c $PHP_HIP/ext/hip_math_drivers.c $PHP_HIP/ext/hip_fast.c $PHP_HIP/ext/hip_lazy.c $PHP_HIP/ext/hip_linalg.c $PHP_HIP/ext/hip_signal.c $PHP_HIP/ext/zend_hooks.c"
+  NP_HIP_GLUE="$PHP_HIP/ext/gpu_alloc_hip.c $PHP_HIP/ext/hip_math.c $PHP_HIP/ext/hip_math_drivers.c $PHP_HIP/ext/hip_fast.c $PHP_HIP/ext/hip_lazy.c $PHP_HIP/ext/hip_linalg.c $PHP_HIP/ext/hip_signal.c $PHP_HIP/ext/hip_dnn.c $PHP_HIP/ext/zend_hooks.c"
   NP_HIP_GLUE_CFLAGS="-DNUMPOWER_NDARRAY_HEADER='\"src/initializers.h\"'"
   PHP_SUBST([NP_HIP_GLUE])
   dnl In PHP_NEW_EXTENSION(ndarray, ...) of the reference's config.m4: drop src/gpu_alloc.c from the source

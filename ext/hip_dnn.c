@@ -1,0 +1,121 @@
+/*
+ * hip_dnn.c — the device side of NDArrayDNN_Conv2D_Forward / _Backward (hip_dnn.h).  Compiled into a --with-hip tree against the
+ * reference's headers (-DNUMPOWER_NDARRAY_HEADER='"src/initializers.h"') and into libnumpower_host.so against
+ * include/numpower_host.h; it uses only what both declare, with one switch: the reference's arrays take ownership of an
+ * emalloc'd shape and its result vectors are emalloc'd, the host library copies shapes and hands out malloc'd vectors.
+ */
+#ifndef NUMPOWER_NDARRAY_HEADER
+#define NUMPOWER_NDARRAY_HEADER "numpower_host.h"
+#endif
+#include NUMPOWER_NDARRAY_HEADER
+
+#include <stddef.h>
+
+#include "hip_dnn.h"
+#include "np_ext_hooks.h"
+#include "np_hip.h"
+
+#ifdef NUMPOWER_AMD_HOST_H
+#include <stdlib.h>
+#define NPH_ALLOC(bytes) malloc(bytes)
+#define NPH_RELEASE(ptr) free(ptr)
+#define NPH_SHAPE_IS_COPIED 1
+#else
+#define NPH_ALLOC(bytes) emalloc(bytes)
+#define NPH_RELEASE(ptr) efree(ptr)
+#define NPH_SHAPE_IS_COPIED 0
+#endif
+
+/* the layer's extents, read once the shapes have been checked */
+typedef struct { size_t N, C, H, W, F, kh, kw; } nph_layer;
+
+/* the checks both directions share; y == NULL: forward.  0 after a raised error */
+static int layer_of(NDArray *x, NDArray *y, NDArray *filters, nph_layer *l) {
+    if (NDArray_NDIM(x) != 4 || NDArray_NDIM(filters) != 4 || (y != NULL && NDArray_NDIM(y) != 4)) {
+        np_ext_throw(NPH_DNN_MSG_NDIM);
+        return 0;
+    }
+    const int *xs = NDArray_SHAPE(x), *fs = NDArray_SHAPE(filters);
+    if (fs[1] != xs[1]) {
+        np_ext_throw(NPH_DNN_MSG_CHANNELS);
+        return 0;
+    }
+    if (fs[2] > xs[2] || fs[3] > xs[3]) {
+        np_ext_throw(NPH_DNN_MSG_WINDOW);
+        return 0;
+    }
+    if (y != NULL) {
+        const int *ys = NDArray_SHAPE(y);
+        if (ys[0] != xs[0] || ys[1] != fs[0] || ys[2] != xs[2] - fs[2] + 1 || ys[3] != xs[3] - fs[3] + 1) {
+            np_ext_throw(NPH_DNN_MSG_GRADIENT);
+            return 0;
+        }
+    }
+    if (NDArray_DEVICE(x) != NDArray_DEVICE(filters) || (y != NULL && NDArray_DEVICE(y) != NDArray_DEVICE(x))) {
+        np_ext_throw(NPH_DNN_MSG_DEVICE);
+        return 0;
+    }
+    if (NDArray_DEVICE(x) != NDARRAY_DEVICE_GPU) {
+        np_ext_throw(NPH_DNN_MSG_CPU);
+        return 0;
+    }
+    l->N = (size_t) xs[0], l->C = (size_t) xs[1], l->H = (size_t) xs[2], l->W = (size_t) xs[3];
+    l->F = (size_t) fs[0], l->kh = (size_t) fs[2], l->kw = (size_t) fs[3];
+    return 1;
+}
+
+/* a new 4-d GPU array, allocated as the reference allocates its results (NDArray_Empty over an emalloc'd shape, dnn.c:284) */
+static NDArray *empty4_on_gpu(size_t d0, size_t d1, size_t d2, size_t d3) {
+    int *shape = (int *) NPH_ALLOC(sizeof(int) * 4);
+    if (shape == NULL) return NULL;
+    shape[0] = (int) d0, shape[1] = (int) d1, shape[2] = (int) d2, shape[3] = (int) d3;
+    NDArray *rtn = NDArray_Empty(shape, 4, "float32", NDARRAY_DEVICE_GPU);
+    if (NPH_SHAPE_IS_COPIED) NPH_RELEASE(shape);
+    return rtn;
+}
+
+NDArray *NPH_Conv2D_Forward(NDArray *x, NDArray *filters) {
+    nph_layer l;
+    if (x == NULL || filters == NULL || !layer_of(x, NULL, filters, &l)) return NULL;
+    size_t oh = 0, ow = 0;
+    if (np_conv2d_shape(l.H, l.W, l.kh, l.kw, 0, 0, &oh, &ow) != NP_OK || l.N < 1 || l.C < 1 || l.F < 1) {
+        if (l.N < 1 || l.C < 1 || l.F < 1) np_ext_throw("dnn_conv2d: an operand has no elements");
+        else np_ext_throw_last();
+        return NULL;
+    }
+    NDArray *rtn = empty4_on_gpu(l.N, l.F, oh, ow);
+    if (rtn == NULL) return NULL;
+    if (np_conv2d_forward(NDArray_FDATA(x), NDArray_FDATA(filters), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, 0, 0, NDArray_FDATA(rtn)) != NP_OK) {
+        np_ext_throw_last();
+        NDArray_FREE(rtn);
+        return NULL;
+    }
+    return rtn;
+}
+
+NDArray **NPH_Conv2D_Backward(NDArray *x, NDArray *y, NDArray *filters) {
+    nph_layer l;
+    if (x == NULL || y == NULL || filters == NULL || !layer_of(x, y, filters, &l)) return NULL;
+    if (NDArray_NUMELEMENTS(x) < 1 || NDArray_NUMELEMENTS(filters) < 1) {
+        np_ext_throw("dnn_conv2d: an operand has no elements");
+        return NULL;
+    }
+    /* the reference's order (dnn.c:365-366): rtn[0] = dW in the filters' shape, rtn[1] = dX in the input's */
+    NDArray *dw = empty4_on_gpu(l.F, l.C, l.kh, l.kw), *dx = empty4_on_gpu(l.N, l.C, l.H, l.W);
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 2);
+    int ok = dw != NULL && dx != NULL && rtns != NULL;
+    if (ok && (np_conv2d_backward_filter(NDArray_FDATA(x), NDArray_FDATA(y), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, 0, 0, NDArray_FDATA(dw)) != NP_OK ||
+               np_conv2d_backward_data(NDArray_FDATA(y), NDArray_FDATA(filters), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, 0, 0, NDArray_FDATA(dx)) != NP_OK)) {
+        np_ext_throw_last();
+        ok = 0;
+    }
+    if (!ok) {
+        if (dw != NULL) NDArray_FREE(dw);
+        if (dx != NULL) NDArray_FREE(dx);
+        if (rtns != NULL) NPH_RELEASE(rtns);
+        return NULL;
+    }
+    rtns[0] = dw;
+    rtns[1] = dx;
+    return rtns;
+}

@@ -1,0 +1,63 @@
+/*
+ * hip_dnn.h — dnn_conv2d_forward / dnn_conv2d_backward of GPU arrays on the device convolution layer (np_conv2d_forward,
+ * np_conv2d_backward_data, np_conv2d_backward_filter of include/np_hip.h).
+ *
+ * The reference computes these on the CPU, or through cuDNN when it is built with HAVE_CUDNN; a --with-hip tree never defines
+ * that name, so for a GPU array NDArrayDNN_Conv2D_Forward / _Backward (dnn.c:273-368) throw "DNN features for GPU not enabled.
+ * ..." (dnn.c:305, 361).  `tools/apply_with_hip.py --dnn` inserts one early-out at the top of each function, which replaces
+ * nothing:
+ *
+ *     NDArrayDNN_Conv2D_Forward at the top
+ *         if (NPH_DNN_TAKES(x, filters)) return NPH_Conv2D_Forward(x, filters);
+ *     NDArrayDNN_Conv2D_Backward at the top, before its first allocation
+ *         if (NPH_DNN_TAKES3(input, y, filters)) return NPH_Conv2D_Backward(input, y, filters);
+ *
+ * guarded by `#ifdef HAVE_NP_HIP`: CPU operands fall through to the reference's code, untouched; as soon as ONE operand lives on
+ * the GPU the call is taken, so a mixed pair (which the reference would read blindly) is refused here with a message.
+ *
+ * What is computed: x (N, C, H, W), filters (F, C, kh, kw), cross-correlation, stride 1, no padding ('valid'),
+ * no bias, no activation — the reference ignores `activation` and `use_bias` on both paths, and `kernel_size` is ignored here.
+ * Where the reference's CPU path is inconsistent this glue defines the mathematics and does NOT follow it:
+ *   - F is filters.shape[0], as the reference's backward and its cuDNN filter descriptor read it (its forward reads shape[3]);
+ *   - kh != kw is allowed (the reference reads shape[2] for both);
+ *   - dW comes back in the filters' own shape (F, C, kh, kw), not as the all-axes NDArray_Transpose view the reference wraps it in;
+ *   - the reference's backward swaps out_w and out_h, and sizes its im2col workspace as N.C.H.W floats for a C.k^2.oh.ow matrix;
+ *   - NDArray_DNN_Conv1D is a placeholder with hard-coded extents and stays out.
+ *
+ * Plain C over the reference's headers in a PHP build (results are the reference's own arrays and die in its NDArray_FREE), over
+ * include/numpower_host.h in libnumpower_host.so, whose NDArrayDNN_Conv2D_Forward / _Backward call these functions after making
+ * their operands contiguous.  Operands must be contiguous (the reference's arrays are).
+ * Errors: this project's messages, the reference has none and reads blindly; NULL after a raised error.
+ */
+#ifndef NUMPOWER_AMD_EXT_HIP_DNN_H
+#define NUMPOWER_AMD_EXT_HIP_DNN_H
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+struct NDArray;
+
+/* true when the early-out takes the call: at least one operand lives on the GPU */
+#define NPH_DNN_TAKES(a, b) (NDArray_DEVICE(a) == NDARRAY_DEVICE_GPU || NDArray_DEVICE(b) == NDARRAY_DEVICE_GPU)
+#define NPH_DNN_TAKES3(a, b, c) (NPH_DNN_TAKES(a, b) || NDArray_DEVICE(c) == NDARRAY_DEVICE_GPU)
+
+/* The messages, checked in this order (the fourth by NPH_Conv2D_Backward alone). */
+#define NPH_DNN_MSG_NDIM "dnn_conv2d: the operands must be 4-dimensional: the input (N, C, H, W), the filters (F, C, kh, kw)"
+#define NPH_DNN_MSG_CHANNELS "dnn_conv2d: the filters' second extent must equal the input's number of channels"
+#define NPH_DNN_MSG_WINDOW "dnn_conv2d: the filter window must not be larger than the input (kh <= H and kw <= W)"
+#define NPH_DNN_MSG_GRADIENT "dnn_conv2d_backward: the gradient must have the shape of the forward result (N, F, H - kh + 1, W - kw + 1)"
+#define NPH_DNN_MSG_DEVICE "dnn_conv2d: the operands must be on the same device"
+#define NPH_DNN_MSG_CPU "dnn_conv2d: operands are on the CPU; numpower_amd only computes on the GPU (call ->gpu() first, the CPU path is the reference's own)"
+
+/* y (N, F, H - kh + 1, W - kw + 1), a new GPU array */
+struct NDArray *NPH_Conv2D_Forward(struct NDArray *x, struct NDArray *filters);
+/* y: the gradient of the forward result, of its shape.  A vector of two new GPU arrays in the reference's order, rtn[0] = dW
+ * (F, C, kh, kw), rtn[1] = dX (N, C, H, W); the vector is emalloc'd in a PHP build (the reference efree's it), malloc'd in
+ * libnumpower_host.so. */
+struct NDArray **NPH_Conv2D_Backward(struct NDArray *x, struct NDArray *y, struct NDArray *filters);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

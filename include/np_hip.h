@@ -543,6 +543,38 @@ int np_correlate2d_shape(size_t ah, size_t aw, size_t bh, size_t bw, int mode, s
 int np_correlate2d(const float *a, size_t ah, size_t aw, const float *b, size_t bh, size_t bw,
                    int mode, int boundary, float fill_value, int flip, float *out);
 
+/* ---- convolution layers (np_dnn.hip; DESIGN.md "dnn_conv2d") ----------------------------------------
+ * The layer behind NDArray::dnn_conv2d_forward / dnn_conv2d_backward, which the reference refuses for GPU arrays unless it is
+ * built against cuDNN (dnn.c:305, 361).  x (N, C, H, W), w (F, C, kh, kw), y and dy (N, F, oh, ow): ROW-MAJOR fp32, contiguous.
+ * Cross-correlation with stride 1, dilation 1 and zero padding (ph, pw), 0 <= ph < kh, 0 <= pw < kw; no bias, no activation.
+ *   y[n,f,i,j]  = sum_{c,p,q} w[f,c,p,q] . x~[n,c,i+p-ph,j+q-pw]            oh = H + 2 ph - kh + 1, ow = W + 2 pw - kw + 1
+ *   dW[f,c,p,q] = sum_{n,i,j} dy[n,f,i,j] . x~[n,c,i+p-ph,j+q-pw]           the filters' own shape
+ *   dX[n,c,u,v] = sum_{f,p,q} dy[n,f,u-p+ph,v-q+pw] . w[f,c,p,q]            the input's own shape
+ * where x~ is x with STORED zeros around it: a padded zero under an Inf tap gives NaN, as a materialised padded array would.
+ * np_conv2d_shape: (oh, ow), no device needed.  The three others compute one array each; the result must not overlap an operand.
+ * Fine print:
+ *   - implicit GEMM on the fp32 MFMA: no im2col matrix is written.  The data gradient is the forward kernel on dy with the
+ *     filters flipped and transposed into pool scratch, pad (kh - 1 - ph, kw - 1 - pw); the filter gradient cuts its reduction
+ *     over N.oh.ow into S slices (S from the extents alone), whose partial results go to pool scratch and are added in slice
+ *     order by a second kernel.  No float atomics.
+ *   - fixed order: every element of y (dX) is one fp32 fmaf chain from +0.0f over k = (c.kh + p).kw + q ascending (over
+ *     (f.kh + p').kw + q' of the flipped window); the order depends on (C, kh, kw) (resp. F, kh, kw) alone, never on N, on where
+ *     the pixel lies or on the tile, so an image gives the same bits at any batch size and position.  dW: a chain over
+ *     n.oh.ow + i.ow + j inside a slice, slices added in order.  All three are bit-identical from run to run.
+ *   - nothing outside an output's receptive field is read into it: a NaN in x, w or dy reaches exactly the outputs the formulas
+ *     above give it.
+ * Convention: pointers are checked first, then the shape, then work begins.  NP_ERR_INVALID before any device work: a null
+ * pointer; an extent of zero; ph >= kh or pw >= kw; kh > H + 2 ph or kw > W + 2 pw; any of numel(x), numel(w), numel(y),
+ * N.oh.ow, C.kh.kw or F.kh.kw at 2^31 or more (refused, never truncated).  Library stream; scratch comes from the caching pool
+ * and is released on every path. */
+int np_conv2d_shape(size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw, size_t *oh, size_t *ow);
+int np_conv2d_forward(const float *x, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
+                      size_t ph, size_t pw, float *y);
+int np_conv2d_backward_data(const float *dy, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
+                            size_t ph, size_t pw, float *dx);
+int np_conv2d_backward_filter(const float *x, const float *dy, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
+                              size_t ph, size_t pw, float *dw);
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

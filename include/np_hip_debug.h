@@ -121,6 +121,10 @@ int np_debug_conv2d_last_path(int *host_path);
 /* testing / A-B: on = 0 sends every window through the chunked path, on != 0 (the default) lets windows up to 15 x 15 be staged
  * once.  Process-global. */
 int np_debug_conv2d_staged_path(int on);
+/* tests / tools: what the last np_conv2d_forward / _backward_data / _backward_filter call of the process launched: the tile's row
+ * count TM (32, 64 or 128; 0 = none yet) and, for _backward_filter, the number of slices S its reduction was cut into (1: written
+ * directly, no fold kernel); 0 slices after the two others.  Plain process globals. */
+int np_debug_dnn_last_path(int *host_tm, int *host_slices);
 
 #ifdef __cplusplus
 }

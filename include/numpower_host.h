@@ -373,6 +373,21 @@ NDArray *NDArray_Lstsq(NDArray *a, NDArray *b);
  * the GPU". */
 NDArray *NDArray_Correlate2D(NDArray *a, NDArray *b, int mode, int boundary, NDArray *fill_value, int flip);
 
+/* ---- convolution layers (host/numpower_dnn.cpp; dnn.c:273-368, dnn.h:7-8) ----
+ * NDArrayDNN_Conv2D_Forward   y (N, F, H - kh + 1, W - kw + 1) of a GPU input x (N, C, H, W) and GPU filters (F, C, kh, kw):
+ *                             cross-correlation, stride 1, no padding, no bias, no activation.
+ * NDArrayDNN_Conv2D_Backward  for y = the gradient of that result: a malloc'd vector {dW (F, C, kh, kw), dX (N, C, H, W)}, the
+ *                             reference's order.
+ * The reference's signatures; kernel_size, activation and use_bias are ignored (the reference ignores the last two on both of
+ * its paths; PHP passes NULL / 3, 'r', 1).  Views are made contiguous; ext/hip_dnn.c (NPH_Conv2D_Forward / _Backward over
+ * np_conv2d_forward / _backward_filter / _backward_data) does the work.  DESIGN.md §3.14 lists where the reference's CPU path
+ * differs: F is shape[0], kh != kw is allowed, dW has the filters' own shape.
+ * Errors (ext/hip_dnn.h, NPH_DNN_MSG_*): operands that are not 4-dimensional, a channel mismatch, a window larger than the input,
+ * a gradient of the wrong shape, operands on different devices, and for CPU operands "... only computes on the GPU": the host
+ * library has no CPU convolution. */
+NDArray *NDArrayDNN_Conv2D_Forward(NDArray *x, NDArray *filters, int *kernel_size, char activation, int use_bias);
+NDArray **NDArrayDNN_Conv2D_Backward(NDArray *input, NDArray *y, NDArray *filters, int kernel_size, char activation, int use_bias);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,10 @@ PROTOTYPES = {
     "np_lstsq": (C.c_int, [_f32p, _f32p, C.c_size_t, C.c_size_t, C.c_size_t, _f32p, C.POINTER(C.c_int)]),
     "np_correlate2d_shape": (C.c_int, [C.c_size_t] * 4 + [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "np_correlate2d": (C.c_int, [_f32p, C.c_size_t, C.c_size_t, _f32p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int, _f32p]),
+    "np_conv2d_shape": (C.c_int, [C.c_size_t] * 6 + [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "np_conv2d_forward": (C.c_int, [_f32p, _f32p] + [C.c_size_t] * 9 + [_f32p]),
+    "np_conv2d_backward_data": (C.c_int, [_f32p, _f32p] + [C.c_size_t] * 9 + [_f32p]),
+    "np_conv2d_backward_filter": (C.c_int, [_f32p, _f32p] + [C.c_size_t] * 9 + [_f32p]),
     "np_permute": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "np_strided_copy": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "np_identity": (C.c_int, [_f32p, C.c_size_t]),
@@ -168,6 +172,7 @@ PROTOTYPES = {
     "np_debug_eigh_small_path": (C.c_int, [C.c_int]),
     "np_debug_conv2d_last_path": (C.c_int, [C.POINTER(C.c_int)]),
     "np_debug_conv2d_staged_path": (C.c_int, [C.c_int]),
+    "np_debug_dnn_last_path": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "np_clear_device_error": (C.c_int, [C.POINTER(C.c_uint)]),
     "np_debug_clock_mhz": (C.c_int, [C.POINTER(C.c_float)]),
 }

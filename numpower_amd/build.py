@@ -30,7 +30,7 @@ LIBDIR = ROOT / "numpower_amd" / "lib"
 OBJDIR = ROOT / "build" / "obj"
 
 HIP_SOURCES = ["np_runtime.hip", "np_elementwise.hip", "np_fused_static.hip", "np_reduce.hip", "np_sgemm.hip", "np_layout.hip",
-               "np_select.hip", "np_comm.hip", "np_lu.hip", "np_cholesky.hip", "np_jacobi.hip", "np_signal.hip", "np_qr.hip"]
+               "np_select.hip", "np_comm.hip", "np_lu.hip", "np_cholesky.hip", "np_jacobi.hip", "np_signal.hip", "np_qr.hip", "np_dnn.hip"]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{INCLUDE}", f"-I{CSRC}"]
 
 
@@ -133,7 +133,7 @@ def build_host(force: bool = False, verbose: bool = False) -> Path:
     if not srcs:
         return lib
     headers = list(INCLUDE.glob("*.h")) + list(HOST.glob("*.h"))
-    ext_objs = _ext_objects(EXT_GLUE + ["hip_math_drivers.c", "hip_fast.c", "hip_lazy.c", "hip_linalg.c", "hip_signal.c"], force, verbose)
+    ext_objs = _ext_objects(EXT_GLUE + ["hip_math_drivers.c", "hip_fast.c", "hip_lazy.c", "hip_linalg.c", "hip_signal.c", "hip_dnn.c"], force, verbose)
     if force or _newer(lib, srcs + headers + ext_objs + [LIBDIR / "libnp_hip.so"]):
         if verbose:
             print("[build] compiling host layer", flush=True)
@@ -164,8 +164,9 @@ def build_method_bodies(force: bool = False, verbose: bool = False) -> Path:
 # The programs tools/apply_with_hip.py wraps around the text it inserts into the reference: <name>_program_source()
 # -> build/gen/<name>_bodies.c -> numpower_amd/lib/<name>_bodies, in the order build_all compiles them.  fast_path: the
 # device-dispatching L2 functions; lazy: the pending chains around a stand-in for the Zend object table; linalg: NDArray_Det /
-# Inverse / LU / Solve; cholesky, svd, eig: NDArray_Cholesky / _SVD / _Eig; signal: NDArray_Correlate2D; qr: NDArray_Qr / _Lstsq.
-BODIES = ("fast_path", "lazy", "linalg", "cholesky", "svd", "eig", "signal", "qr")
+# Inverse / LU / Solve; cholesky, svd, eig: NDArray_Cholesky / _SVD / _Eig; signal: NDArray_Correlate2D; qr: NDArray_Qr / _Lstsq;
+# dnn: NDArrayDNN_Conv2D_Forward / _Backward.
+BODIES = ("fast_path", "lazy", "linalg", "cholesky", "svd", "eig", "signal", "qr", "dnn")
 _apply_with_hip = None
 
 

@@ -1,0 +1,387 @@
+// Convolution layers for GPU arrays: np_conv2d_forward, np_conv2d_backward_data, np_conv2d_backward_filter.
+//
+// x (N, C, H, W), w (F, C, kh, kw), y (N, F, oh, ow), row-major fp32; cross-correlation, stride 1, dilation 1, zero padding (ph, pw).
+// Everything is an implicit GEMM on v_mfma_f32_32x32x2_f32; no im2col matrix is ever written.
+//
+//   forward   Y (F x N.P) = Wm (F x K) . Col (K x N.P),  K = C.kh.kw with k = (c.kh + p).kw + q — the filters' own memory, so
+//             Wm is a plain row-major matrix — and the pixel index flattened over the batch, jg = n.P + i.ow + j, P = oh.ow.
+//             Col[k][jg] = x~[n, c, i + p - ph, j + q - pw] is gathered from x while a tile is staged; taps outside the image are
+//             STORED zeros (an Inf tap over the padding gives NaN, as a materialised padded array would).
+//   dX        the same kernel: dX = forward(dy as an input with F channels, w', pad (kh - 1 - ph, kw - 1 - pw)), where
+//             w'[c, f, p, q] = w[f, c, kh - 1 - p, kw - 1 - q] is written to pool scratch by dnn_filter_flip_kernel.
+//   dW        dW (F x K) = dYm (F x N.P) . Col^T, the same gather on the other operand.  The output is small and the reduction
+//             long: it is cut into S slices of whole kTK-steps, each slice's tile goes to pool scratch and dnn_wgrad_fold_kernel
+//             adds the slices in slice order (S == 1 writes dW directly).  No float atomics.
+//
+// Tiles: a workgroup of 4 waves computes TM x kTN outputs through LDS in reduction steps of kTK; TM is 32, 64 or 128 and is the
+// smallest that covers F (beyond 128: 128), so a layer with few filters does not burn a 128-row tile.  Out-of-range taps, the
+// reduction's tail and the tile edges are zero-filled on BOTH operands: nothing outside the receptive field reaches an output.
+//
+// Reduction order: every output is ONE fp32 fmaf chain from +0.0f over its reduction index in ascending order (the MFMA is
+// bit for bit that chain), continued over the zero-filled tail of the last step.  For y and dX the order depends on (C, kh, kw)
+// resp. (F, kh, kw) alone — not on N, the position of the pixel, TM or any device state — so the same image gives the same bits
+// at any batch size and position.  For dW the chain runs over jg inside a slice and the slices are then added in order; S is a
+// function of the extents alone.  Results are bit-identical from run to run.
+#include <limits.h>
+
+#include "np_internal.h"
+
+namespace {
+
+// ---- tile constants (tests/test_gpu_dnn.py mirrors them) ----
+constexpr int kTN = 128;                  // columns of a tile: pixels jg (forward), reduction columns k (dW)
+constexpr int kTK = 32;                   // reduction step staged through LDS
+constexpr int kTMSmall = 32, kTMMid = 64, kTMLarge = 128;   // the TM instantiations
+constexpr int kAStr = kTK + 1, kBStr = kTN + 1;             // LDS row strides (odd: a column walk touches every bank)
+// dW: a slice is at least kWgradMinSteps steps long, slices stop once tiles x S reaches kWgradTargetGroups workgroups
+constexpr int kWgradMinSteps = 8, kWgradTargetGroups = 512, kWgradMaxSlices = 256;
+
+typedef float dnn_v16f __attribute__((ext_vector_type(16)));
+
+int g_dnn_last_tm = 0, g_dnn_last_slices = 0;
+
+struct ConvArgs {
+    const float *x;   // the gathered operand (N, C, H, W)
+    const float *w;   // forward: the filters (F, C, kh, kw) as Wm; dW: dy (N, F, oh, ow)
+    float *out;
+    int N, C, H, W, F, kh, kw, ph, pw, oh, ow;
+    int K, P, NP;     // C.kh.kw, oh.ow, N.P
+};
+
+// how the 4 waves share a TM x kTN tile: 32 x 32 MFMA blocks, MI x NJ of them per wave
+template <int TM>
+struct Tile {
+    static constexpr int WM = TM >= 128 ? 2 : 1, WN = 4 / WM, MI = TM / (WM * 32), NJ = kTN / (WN * 32);
+};
+
+// the accumulator's row inside a 32 x 32 block: register r of a lane in half kq
+__device__ __forceinline__ int acc_row(int r, int kq) { return (r & 3) + 8 * (r >> 2) + 4 * kq; }
+
+// one staged step: acc += As (TM x kTK) . Bs (kTK x kTN), k ascending
+template <int TM>
+__device__ __forceinline__ void mma_step(const float *As, const float *Bs, dnn_v16f (&acc)[Tile<TM>::MI][Tile<TM>::NJ], int wm, int wn,
+                                         int lane) {
+    using T = Tile<TM>;
+    const int i = lane & 31, kq = lane >> 5;
+#pragma unroll
+    for (int kk = 0; kk < kTK; kk += 2) {
+        float a[T::MI], b[T::NJ];
+#pragma unroll
+        for (int mi = 0; mi < T::MI; ++mi) a[mi] = As[((wm * T::MI + mi) * 32 + i) * kAStr + kk + kq];
+#pragma unroll
+        for (int nj = 0; nj < T::NJ; ++nj) b[nj] = Bs[(kk + kq) * kBStr + (wn * T::NJ + nj) * 32 + i];
+#pragma unroll
+        for (int mi = 0; mi < T::MI; ++mi)
+#pragma unroll
+            for (int nj = 0; nj < T::NJ; ++nj) acc[mi][nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi], b[nj], acc[mi][nj], 0, 0, 0);
+    }
+}
+
+// k = (c.kh + p).kw + q -> the tap's offset inside one image of x and its (p, q); koff = -1 marks the reduction's tail
+__device__ __forceinline__ void decode_tap(const ConvArgs &p, int k, int &koff, int &kp, int &kq) {
+    koff = -1;
+    kp = kq = 0;
+    if (k < p.K) {
+        const int khw = p.kh * p.kw, c = k / khw, r = k - c * khw;
+        kp = r / p.kw;
+        kq = r - kp * p.kw;
+        koff = (c * p.H + kp) * p.W + kq;
+    }
+}
+
+// grid.x = F-tiles x pixel-tiles, F-tiles fastest: neighbouring workgroups gather the same pixels
+template <int TM>
+__global__ __launch_bounds__(256, 2) void dnn_fprop_kernel(const ConvArgs p) {
+    using T = Tile<TM>;
+    __shared__ float As[TM * kAStr];
+    __shared__ float Bs[kTK * kBStr];
+    __shared__ int s_koff[kTK], s_kp[kTK], s_kq[kTK];   // the step's offset table: one decode per k, none per element
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / T::WN, wn = wave % T::WN;
+    const int tiles_f = (p.F + TM - 1) / TM;
+    const int f0 = (int)(blockIdx.x % tiles_f) * TM, j0 = (int)(blockIdx.x / tiles_f) * kTN;
+
+    dnn_v16f acc[T::MI][T::NJ];
+#pragma unroll
+    for (int mi = 0; mi < T::MI; ++mi)
+#pragma unroll
+        for (int nj = 0; nj < T::NJ; ++nj)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mi][nj][r] = 0.0f;
+
+    // a thread gathers ONE pixel for the whole reduction: for a fixed k consecutive pixels of an output row are consecutive addresses
+    const int jl = tid & (kTN - 1), krow0 = tid >> 7;
+    const int jg = j0 + jl;
+    const bool pixel = jg < p.NP;
+    int ih0 = 0, iw0 = 0;
+    long long xo = 0;   // the window's corner in x: outside the array where the padding begins, only ever added to a valid tap
+    if (pixel) {
+        const int n = jg / p.P, pix = jg - n * p.P, oi = pix / p.ow, oj = pix - oi * p.ow;
+        ih0 = oi - p.ph;
+        iw0 = oj - p.pw;
+        xo = (long long)n * p.C * p.H * p.W + (long long)ih0 * p.W + iw0;
+    }
+    const int kc = tid & 31, fr = tid >> 5;
+
+    for (int k0 = 0; k0 < p.K; k0 += kTK) {
+        if (tid < kTK) decode_tap(p, k0 + tid, s_koff[tid], s_kp[tid], s_kq[tid]);
+        __syncthreads();   // also: every wave is done with the previous step's tiles
+#pragma unroll
+        for (int u = 0; u < TM / 8; ++u) {
+            const int f = f0 + fr + 8 * u, k = k0 + kc;
+            As[(fr + 8 * u) * kAStr + kc] = (f < p.F && k < p.K) ? p.w[(size_t)f * p.K + k] : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < kTK / 2; ++u) {
+            const int kr = krow0 + 2 * u, koff = s_koff[kr], ih = ih0 + s_kp[kr], iw = iw0 + s_kq[kr];
+            float v = 0.0f;
+            if (pixel && koff >= 0 && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) v = p.x[xo + koff];
+            Bs[kr * kBStr + jl] = v;
+        }
+        __syncthreads();
+        mma_step<TM>(As, Bs, acc, wm, wn, lane);
+    }
+
+    const int i = lane & 31, kq = lane >> 5;
+#pragma unroll
+    for (int nj = 0; nj < T::NJ; ++nj) {
+        const int col = j0 + (wn * T::NJ + nj) * 32 + i;
+        if (col >= p.NP) continue;
+        const int n = col / p.P, pix = col - n * p.P;
+        float *yb = p.out + ((size_t)n * p.F * p.P + pix);
+#pragma unroll
+        for (int mi = 0; mi < T::MI; ++mi)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int f = f0 + (wm * T::MI + mi) * 32 + acc_row(r, kq);
+                if (f < p.F) yb[(size_t)f * p.P] = acc[mi][nj][r];
+            }
+    }
+}
+
+// w'[c, f, p, q] = w[f, c, kh - 1 - p, kw - 1 - q]
+__global__ __launch_bounds__(256) void dnn_filter_flip_kernel(const float *__restrict__ w, float *__restrict__ wf, int F, int C, int kh, int kw,
+                                                              unsigned n) {
+    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= n) return;
+    const int khw = kh * kw;
+    const int cf = (int)(idx / (unsigned)khw), r = (int)(idx - (unsigned)cf * (unsigned)khw);
+    const int c = cf / F, f = cf - c * F, pp = r / kw, q = r - pp * kw;
+    wf[idx] = w[((size_t)f * C + c) * khw + (size_t)(kh - 1 - pp) * kw + (kw - 1 - q)];
+}
+
+// grid.x = F-tiles x k-tiles, grid.y = slices; a slice reduces steps [slice * steps_per_slice, ...) of kTK pixels jg each and
+// stores its F x K tile at out + slice * F * K
+template <int TM>
+__global__ __launch_bounds__(256, 2) void dnn_wgrad_kernel(const ConvArgs p, int steps_per_slice) {
+    using T = Tile<TM>;
+    __shared__ float As[TM * kAStr];
+    __shared__ float Bs[kTK * kBStr];
+    __shared__ int s_koff[kTN], s_kp[kTN], s_kq[kTN];   // the tile's columns, decoded once
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / T::WN, wn = wave % T::WN;
+    const int tiles_f = (p.F + TM - 1) / TM;
+    const int f0 = (int)(blockIdx.x % tiles_f) * TM, kc0 = (int)(blockIdx.x / tiles_f) * kTN;
+
+    dnn_v16f acc[T::MI][T::NJ];
+#pragma unroll
+    for (int mi = 0; mi < T::MI; ++mi)
+#pragma unroll
+        for (int nj = 0; nj < T::NJ; ++nj)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mi][nj][r] = 0.0f;
+
+    if (tid < kTN) decode_tap(p, kc0 + tid, s_koff[tid], s_kp[tid], s_kq[tid]);
+    const int steps = (p.NP + kTK - 1) / kTK;
+    const int s0 = (int)blockIdx.y * steps_per_slice, s1 = s0 + steps_per_slice < steps ? s0 + steps_per_slice : steps;
+    const int kr = tid & 31, g = tid >> 5;   // a thread stages one pixel of the step: consecutive lanes, consecutive addresses
+
+    for (int s = s0; s < s1; ++s) {
+        const int jg = s * kTK + kr;
+        const bool pixel = jg < p.NP;
+        int n = 0, pix = 0, ih0 = 0, iw0 = 0;
+        if (pixel) {
+            n = jg / p.P;
+            pix = jg - n * p.P;
+            const int oi = pix / p.ow, oj = pix - oi * p.ow;
+            ih0 = oi - p.ph;
+            iw0 = oj - p.pw;
+        }
+        const long long xo = (long long)n * p.C * p.H * p.W + (long long)ih0 * p.W + iw0;
+        const float *db = p.w + ((size_t)n * p.F * p.P + pix);
+        __syncthreads();   // the table (first step); every wave is done with the previous step's tiles
+#pragma unroll
+        for (int u = 0; u < TM / 8; ++u) {
+            const int f = f0 + g + 8 * u;
+            As[(g + 8 * u) * kAStr + kr] = (pixel && f < p.F) ? db[(size_t)f * p.P] : 0.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < kTN / 8; ++u) {
+            const int col = g + 8 * u, koff = s_koff[col], ih = ih0 + s_kp[col], iw = iw0 + s_kq[col];
+            float v = 0.0f;
+            if (pixel && koff >= 0 && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) v = p.x[xo + koff];
+            Bs[kr * kBStr + col] = v;
+        }
+        __syncthreads();
+        mma_step<TM>(As, Bs, acc, wm, wn, lane);
+    }
+
+    float *out = p.out + (size_t)blockIdx.y * p.F * p.K;
+    const int i = lane & 31, kq = lane >> 5;
+#pragma unroll
+    for (int nj = 0; nj < T::NJ; ++nj) {
+        const int k = kc0 + (wn * T::NJ + nj) * 32 + i;
+        if (k >= p.K) continue;
+#pragma unroll
+        for (int mi = 0; mi < T::MI; ++mi)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int f = f0 + (wm * T::MI + mi) * 32 + acc_row(r, kq);
+                if (f < p.F) out[(size_t)f * p.K + k] = acc[mi][nj][r];
+            }
+    }
+}
+
+// dw[e] = part[0][e] + part[1][e] + ... in slice order
+__global__ __launch_bounds__(256) void dnn_wgrad_fold_kernel(const float *__restrict__ part, float *__restrict__ dw, unsigned n, int slices) {
+    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= n) return;
+    float acc = part[idx];
+    for (int s = 1; s < slices; ++s) acc += part[(size_t)s * n + idx];
+    dw[idx] = acc;
+}
+
+int pick_tm(size_t F) { return F <= (size_t)kTMSmall ? kTMSmall : F <= (size_t)kTMMid ? kTMMid : kTMLarge; }
+
+constexpr size_t kLim = (size_t)1 << 31;
+// a * b, saturating at kLim (both factors at most kLim)
+size_t mul_lim(size_t a, size_t b) { return (a >= kLim || b >= kLim || a * b >= kLim) ? kLim : a * b; }
+
+int check_spatial(const char *who, size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw) {
+    if (H < 1 || W < 1 || kh < 1 || kw < 1) return np::fail(NP_ERR_INVALID, "%s: every extent must be at least 1", who);
+    if (H >= kLim || W >= kLim || kh >= kLim || kw >= kLim) return np::fail(NP_ERR_INVALID, "%s: an extent is 2^31 or more", who);
+    if (ph >= kh || pw >= kw) return np::fail(NP_ERR_INVALID, "%s: the padding (%zu, %zu) must be smaller than the window (%zu, %zu)", who, ph, pw, kh, kw);
+    if (kh > H + 2 * ph || kw > W + 2 * pw)
+        return np::fail(NP_ERR_INVALID, "%s: the window (%zu, %zu) is larger than the padded image (%zu, %zu)", who, kh, kw, H + 2 * ph, W + 2 * pw);
+    return NP_OK;
+}
+
+// the whole shape of a layer; fills the kernel's extents (out and the operand pointers are the caller's)
+int check_layer(const char *who, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw, size_t ph, size_t pw, ConvArgs &a) {
+    if (N < 1 || C < 1 || F < 1) return np::fail(NP_ERR_INVALID, "%s: every extent must be at least 1", who);
+    if (int rc = check_spatial(who, H, W, kh, kw, ph, pw)) return rc;
+    const size_t oh = H + 2 * ph - kh + 1, ow = W + 2 * pw - kw + 1;
+    const size_t P = mul_lim(oh, ow), numel_x = mul_lim(mul_lim(N, C), mul_lim(H, W)), numel_w = mul_lim(mul_lim(F, C), mul_lim(kh, kw));
+    const size_t numel_y = mul_lim(mul_lim(N, F), P), NP = mul_lim(N, P), K = mul_lim(C, mul_lim(kh, kw)), Kt = mul_lim(F, mul_lim(kh, kw));
+    if (numel_x >= kLim || numel_w >= kLim || numel_y >= kLim || NP >= kLim || K >= kLim || Kt >= kLim)
+        return np::fail(NP_ERR_INVALID, "%s: an operand, the result, N.P or the reduction length has 2^31 elements or more", who);
+    a.N = (int)N, a.C = (int)C, a.H = (int)H, a.W = (int)W, a.F = (int)F, a.kh = (int)kh, a.kw = (int)kw, a.ph = (int)ph, a.pw = (int)pw;
+    a.oh = (int)oh, a.ow = (int)ow, a.K = (int)K, a.P = (int)P, a.NP = (int)NP;
+    return NP_OK;
+}
+
+int launch_fprop(const ConvArgs &a) {
+    const int tm = pick_tm((size_t)a.F);
+    const size_t tiles = (((size_t)a.F + tm - 1) / tm) * (((size_t)a.NP + kTN - 1) / kTN);
+    if (tiles >= kLim) return np::fail(NP_ERR_INVALID, "np_conv2d: %zu tiles are more than one launch holds", tiles);
+    const dim3 grid((unsigned)tiles), block(256);
+    if (tm == kTMSmall) dnn_fprop_kernel<kTMSmall><<<grid, block, 0, np::stream()>>>(a);
+    else if (tm == kTMMid) dnn_fprop_kernel<kTMMid><<<grid, block, 0, np::stream()>>>(a);
+    else dnn_fprop_kernel<kTMLarge><<<grid, block, 0, np::stream()>>>(a);
+    NP_LAUNCH_CHECK("dnn_fprop_kernel");
+    g_dnn_last_tm = tm;
+    g_dnn_last_slices = 0;
+    return NP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int np_conv2d_shape(size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw, size_t *oh, size_t *ow) {
+    if (!oh || !ow) return np::fail(NP_ERR_INVALID, "np_conv2d_shape: null pointer");
+    if (int rc = check_spatial("np_conv2d_shape", H, W, kh, kw, ph, pw)) return rc;
+    *oh = H + 2 * ph - kh + 1;
+    *ow = W + 2 * pw - kw + 1;
+    return NP_OK;
+}
+
+int np_conv2d_forward(const float *x, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw, size_t ph,
+                      size_t pw, float *y) {
+    // pointers, then the shape, then work: a refused call has touched no device
+    if (!x || !w || !y) return np::fail(NP_ERR_INVALID, "np_conv2d_forward: null pointer");
+    ConvArgs a = {};
+    if (int rc = check_layer("np_conv2d_forward", N, C, H, W, F, kh, kw, ph, pw, a)) return rc;
+    if (int rc = np::ensure_init()) return rc;
+    a.x = x;
+    a.w = w;
+    a.out = y;
+    return launch_fprop(a);
+}
+
+int np_conv2d_backward_data(const float *dy, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
+                            size_t ph, size_t pw, float *dx) {
+    if (!dy || !w || !dx) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_data: null pointer");
+    ConvArgs l = {};
+    if (int rc = check_layer("np_conv2d_backward_data", N, C, H, W, F, kh, kw, ph, pw, l)) return rc;
+    if (int rc = np::ensure_init()) return rc;
+    const size_t numel_w = (size_t)l.F * l.K;
+    np::Scratch flipped;   // released on every path below
+    if (int rc = flipped.alloc(numel_w * sizeof(float))) return rc;
+    dnn_filter_flip_kernel<<<dim3((unsigned)((numel_w + 255) / 256)), dim3(256), 0, np::stream()>>>(w, (float *)flipped.ptr, l.F, l.C, l.kh, l.kw,
+                                                                                                   (unsigned)numel_w);
+    NP_LAUNCH_CHECK("dnn_filter_flip_kernel");
+    // the forward layer of dy: F channels of oh x ow in, C channels out, pad (kh - 1 - ph, kw - 1 - pw); its result is H x W
+    ConvArgs a = {};
+    a.x = dy;
+    a.w = (const float *)flipped.ptr;
+    a.out = dx;
+    a.N = l.N, a.C = l.F, a.H = l.oh, a.W = l.ow, a.F = l.C, a.kh = l.kh, a.kw = l.kw, a.ph = l.kh - 1 - l.ph, a.pw = l.kw - 1 - l.pw;
+    a.oh = l.H, a.ow = l.W, a.K = l.F * l.kh * l.kw, a.P = l.H * l.W, a.NP = l.N * a.P;
+    return launch_fprop(a);
+}
+
+int np_conv2d_backward_filter(const float *x, const float *dy, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
+                              size_t ph, size_t pw, float *dw) {
+    if (!x || !dy || !dw) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_filter: null pointer");
+    ConvArgs a = {};
+    if (int rc = check_layer("np_conv2d_backward_filter", N, C, H, W, F, kh, kw, ph, pw, a)) return rc;
+    if (int rc = np::ensure_init()) return rc;
+    const int tm = pick_tm((size_t)a.F);
+    const size_t tiles = (((size_t)a.F + tm - 1) / tm) * (((size_t)a.K + kTN - 1) / kTN);
+    if (tiles >= kLim) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_filter: %zu tiles are more than one launch holds", tiles);
+    // S from the extents alone: slices of at least kWgradMinSteps steps until tiles x S fills the device
+    const size_t steps = ((size_t)a.NP + kTK - 1) / kTK;
+    size_t want = steps / kWgradMinSteps, fill = (kWgradTargetGroups + tiles - 1) / tiles;
+    if (want > fill) want = fill;
+    if (want > (size_t)kWgradMaxSlices) want = kWgradMaxSlices;
+    if (want < 1) want = 1;
+    const size_t steps_per_slice = (steps + want - 1) / want, slices = (steps + steps_per_slice - 1) / steps_per_slice;
+    const size_t numel_w = (size_t)a.F * a.K;
+    np::Scratch part;   // released on every path below
+    if (slices > 1)
+        if (int rc = part.alloc(slices * numel_w * sizeof(float))) return rc;
+    a.x = x;
+    a.w = dy;
+    a.out = slices > 1 ? (float *)part.ptr : dw;
+    const dim3 grid((unsigned)tiles, (unsigned)slices), block(256);
+    if (tm == kTMSmall) dnn_wgrad_kernel<kTMSmall><<<grid, block, 0, np::stream()>>>(a, (int)steps_per_slice);
+    else if (tm == kTMMid) dnn_wgrad_kernel<kTMMid><<<grid, block, 0, np::stream()>>>(a, (int)steps_per_slice);
+    else dnn_wgrad_kernel<kTMLarge><<<grid, block, 0, np::stream()>>>(a, (int)steps_per_slice);
+    NP_LAUNCH_CHECK("dnn_wgrad_kernel");
+    if (slices > 1) {
+        dnn_wgrad_fold_kernel<<<dim3((unsigned)((numel_w + 255) / 256)), dim3(256), 0, np::stream()>>>((const float *)part.ptr, dw, (unsigned)numel_w,
+                                                                                                      (int)slices);
+        NP_LAUNCH_CHECK("dnn_wgrad_fold_kernel");
+    }
+    g_dnn_last_tm = tm;
+    g_dnn_last_slices = (int)slices;
+    return NP_OK;
+}
+
+int np_debug_dnn_last_path(int *host_tm, int *host_slices) {
+    if (!host_tm || !host_slices) return np::fail(NP_ERR_INVALID, "np_debug_dnn_last_path: null pointer");
+    *host_tm = g_dnn_last_tm;
+    *host_slices = g_dnn_last_slices;
+    return NP_OK;
+}
+
+}  // extern "C"

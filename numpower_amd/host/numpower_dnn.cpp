@@ -1,0 +1,47 @@
+// NDArrayDNN_Conv2D_Forward / _Backward (dnn.c:273-368, dnn.h:7-8) on the device convolution layer (np_conv2d_forward,
+// np_conv2d_backward_data, np_conv2d_backward_filter).
+// The work — argument checks, this project's messages, the result arrays, the np_conv2d_* calls — is ext/hip_dnn.c, the same
+// code a `--dnn` --with-hip tree reaches through the early-outs tools/apply_with_hip.py inserts at the top of the reference's
+// functions; here strided views of the operands are first made contiguous (numpower_host_contiguous).  kernel_size, activation
+// and use_bias are the reference's parameters and are ignored, as the reference ignores the last two on both of its paths.
+// The host library has no CPU convolution: CPU operands get the glue's message.
+// A translation unit of its own: the sanitizer build of numpower_host.cpp (tests/test_host_sanitizers_cpu.py) links
+// against a null device that has no convolution.
+#include "hip_dnn.h"
+#include "numpower_host.h"
+#include "numpower_operand.h"
+
+using numpower_host::Operand;
+
+namespace {
+
+bool on_gpu(NDArray *a) { return NDArray_DEVICE(a) == NDARRAY_DEVICE_GPU; }
+
+}  // namespace
+
+extern "C" {
+
+NDArray *NDArrayDNN_Conv2D_Forward(NDArray *x, NDArray *filters, int *kernel_size, char activation, int use_bias) {
+    (void) kernel_size, (void) activation, (void) use_bias;
+    if (!x || !filters) return nullptr;
+    // CPU operands are handed on as they are: they only ever meet the argument checks and the device messages
+    if (!on_gpu(x) || !on_gpu(filters)) return NPH_Conv2D_Forward(x, filters);
+    Operand cx(x);
+    if (!cx.arr) return nullptr;
+    Operand cf(filters);
+    return cf.arr ? NPH_Conv2D_Forward(cx.arr, cf.arr) : nullptr;
+}
+
+NDArray **NDArrayDNN_Conv2D_Backward(NDArray *input, NDArray *y, NDArray *filters, int kernel_size, char activation, int use_bias) {
+    (void) kernel_size, (void) activation, (void) use_bias;
+    if (!input || !y || !filters) return nullptr;
+    if (!on_gpu(input) || !on_gpu(y) || !on_gpu(filters)) return NPH_Conv2D_Backward(input, y, filters);
+    Operand cx(input);
+    if (!cx.arr) return nullptr;
+    Operand cy(y);
+    if (!cy.arr) return nullptr;
+    Operand cf(filters);
+    return cf.arr ? NPH_Conv2D_Backward(cx.arr, cy.arr, cf.arr) : nullptr;
+}
+
+}  // extern "C"

@@ -153,6 +153,8 @@ def _load_host():
     sig["NDArray_Solve"] = (_P, [_P, _P])
     sig["NDArray_Cholesky"] = (_P, [_P])
     sig["NDArray_Correlate2D"] = (_P, [_P, _P, C.c_int, C.c_int, _P, C.c_int])
+    sig["NDArrayDNN_Conv2D_Forward"] = (_P, [_P, _P, ip, C.c_char, C.c_int])
+    sig["NDArrayDNN_Conv2D_Backward"] = (C.POINTER(_P), [_P, _P, _P, C.c_int, C.c_char, C.c_int])
     sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
     sig["NDArray_Eig"] = (C.POINTER(_P), [_P])
     sig["NDArray_Qr"] = (C.POINTER(_P), [_P])
@@ -847,6 +849,29 @@ class NDArray:
     @staticmethod
     def correlate2d(a, b, mode, boundary, fill_value=0.0):   # numpower.c:4440: scipy.signal.correlate2d
         return NDArray._signal2d(a, b, mode, boundary, fill_value, 0)
+
+    @staticmethod
+    def dnn_conv2d_forward(x, filters):   # numpower.c:4293: NDArrayDNN_Conv2D_Forward(x, filters, NULL, 'r', 1)
+        """y (N, F, H - kh + 1, W - kw + 1) of x (N, C, H, W) and filters (F, C, kh, kw): cross-correlation, stride 1, no padding,
+        no bias, no activation."""
+        h = _load_host()
+        a, _ = NDArray._coerce(x)
+        w, _ = NDArray._coerce(filters)
+        return NDArray._wrap(h.NDArrayDNN_Conv2D_Forward(a._p, w._p, None, b"r", 1))
+
+    @staticmethod
+    def dnn_conv2d_backward(x, y, filters):   # numpower.c:4348: NDArrayDNN_Conv2D_Backward(x, y, filters, 3, 'r', 1) -> RETURN_2NDARRAY
+        """(dW (F, C, kh, kw), dX (N, C, H, W)) for y = the gradient of dnn_conv2d_forward(x, filters), the reference's order."""
+        h = _load_host()
+        a, _ = NDArray._coerce(x)
+        g, _ = NDArray._coerce(y)
+        w, _ = NDArray._coerce(filters)
+        rtns = h.NDArrayDNN_Conv2D_Backward(a._p, g._p, w._p, 3, b"r", 1)
+        if not rtns:
+            _raise_pending(h)
+        out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(2))
+        _libc_free(C.cast(rtns, C.c_void_p))
+        return out
 
     def copy(self):          # PHP_METHOD copy: NDArray_Copy on the array's own device
         return NDArray._wrap(_load_host().NDArray_Copy(self._p, C.cast(self._p, _P).contents.device))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """apply_with_hip.py — turn a NumPower checkout into a `--with-hip` tree (INTEGRATION.md sections 2a and 2b, as code).
 
-    python tools/apply_with_hip.py [--keep-cuda] [--no-signal] [--eig] [--qr] <NumPower checkout> <output directory>
+    python tools/apply_with_hip.py [--keep-cuda] [--no-signal] [--eig] [--qr] [--dnn] <NumPower checkout> <output directory>
 
 Copies the checkout to <output directory>, applies every edit of INTEGRATION.md section 2a by ANCHORED regex and
 copies the glue (ext/*.c, ext/*.h, include/np_hip.h) to <output>/src/hip/.  Every edit names its file, the exact
@@ -595,6 +595,38 @@ QR_EDITS = [
          "    }", after=True, context="NDArray *a = 0;"),   # behind the function's opening line: indented by hand
 ]
 
+# ---- section 2b, dnn_conv2d_forward / dnn_conv2d_backward: without cuDNN (a --with-hip tree never defines HAVE_CUDNN) the reference's
+# NDArrayDNN_Conv2D_Forward / _Backward throw "DNN features for GPU not enabled. ..." for a GPU array; each early-out sits at the top of
+# its function, before the first allocation, and replaces nothing.  Like QR_EDITS a list of its own that is NOT part of EDITS, handed
+# to apply() as `extra`; main() passes it only under --dnn, and only then are ext/hip_dnn.c / hip_dnn.h copied and hip_dnn.c listed in
+# the emitted config.m4, so the tree and the counts of the default command line stay what they were.  Its text runs as a program of
+# its own (dnn_bodies) ----
+DNN_EDITS = [
+    Edit("src/dnn.c", "dnn.c:4: <hip_dnn.h>",
+         r"^(?P<old>#include \"dnn\.h\")$",
+         "#include <hip_dnn.h>", after=True),
+    Edit("src/dnn.c", "dnn.c:275 NDArrayDNN_Conv2D_Forward: GPU early-out",
+         r"^(?P<old>NDArrayDNN_Conv2D_Forward\(NDArray \*x, NDArray \*filters, int \*kernel_size, char activation, int use_bias\)\n\{)"
+         r"(?=\n[ \t]*NDArray \*rtn = NULL;\n[ \t]*if \(NDArray_DEVICE\(x\) == NDARRAY_DEVICE_CPU\) \{)",
+         "    /* numpower_amd 2b: as soon as one operand lives on the GPU the layer runs on the device (np_conv2d_forward, ext/hip_dnn.c; a\n"
+         "     * mixed pair is refused there); CPU operands fall through to the reference's im2col code below, untouched */\n"
+         "    if (NPH_DNN_TAKES(x, filters)) {\n"
+         "        return NPH_Conv2D_Forward(x, filters);\n"
+         "    }", after=True, context="NDArray *x = 0, *filters = 0;"),   # behind the function's opening brace: indented by hand
+    Edit("src/dnn.c", "dnn.c:314 NDArrayDNN_Conv2D_Backward: GPU early-out",
+         r"^(?P<old>NDArrayDNN_Conv2D_Backward\(NDArray \*input, NDArray \*y, NDArray \*filters, int kernel_size, char activation, int use_bias\)\n\{)"
+         r"(?=\n[ \t]*NDArray \*\*rtn = emalloc\(sizeof\(NDArray\*\) \* 2\);)",
+         "    /* numpower_amd 2b: as soon as one operand lives on the GPU both gradients are computed on the device (np_conv2d_backward_filter\n"
+         "     * / _backward_data, ext/hip_dnn.c: {dW, dX}; a mixed triple is refused there) before the reference allocates its vector; CPU\n"
+         "     * operands fall through to the reference's code below, untouched */\n"
+         "    if (NPH_DNN_TAKES3(input, y, filters)) {\n"
+         "        return NPH_Conv2D_Backward(input, y, filters);\n"
+         "    }", after=True, context="NDArray *input = 0, *y = 0, *filters = 0;"),   # behind the function's opening brace: indented by hand
+]
+# what --dnn adds to the glue: copied to src/hip/ and compiled by the emitted config.m4 only then
+DNN_GLUE_FILES = ["ext/hip_dnn.c", "ext/hip_dnn.h"]
+DNN_M4_ANCHOR, DNN_M4_SOURCES = "src/hip/hip_signal.c src/hip/zend_hooks.c", "src/hip/hip_signal.c src/hip/hip_dnn.c src/hip/zend_hooks.c"
+
 CONTEXTS = {
     "ndarray.c:1055-1060 NDArray_ToGPU: H2D copy": "float *tmp_gpu = 0; NDArray *target = 0;",
     "ndarray.c:1090 NDArray_ToCPU: D2H copy": "NDArray *rtn = 0, *target = 0;",
@@ -706,6 +738,7 @@ def snippet_check_source(edits=None) -> str:
     out = ["/* generated by tools/apply_with_hip.py: snippet_check_source() */",
            "#include <stdio.h>", "#include <stddef.h>",
            '#include "np_hip.h"', '#include "numpower_host.h"', '#include "hip_math.h"', '#include "hip_fast.h"', '#include "hip_lazy.h"', '#include "hip_linalg.h"', *(['#include "hip_signal.h"'] if edits is not None else []),
+           *(['#include "hip_dnn.h"'] if edits is DNN_EDITS else []),
            "void zend_throw_error(void *exception_ce, const char *format, ...);   /* Zend/zend_exceptions.h */",
            "typedef struct _zval_struct zval;                                        /* Zend/zend_types.h */",
            "NDArray *ZVAL_TO_NDARRAY(zval *obj);                                     /* numpower.c:89 */",
@@ -909,6 +942,115 @@ def qr_program_source() -> str:
          "    return (NDArray **) reference_body();", "}", ""]
     o.append(_QR_PROGRAM_MAIN)
     return "\n".join(o)
+
+
+def dnn_program_source() -> str:
+    """A C99 PROGRAM around the text DNN_EDITS inserts into dnn.c: NDArrayDNN_Conv2D_Forward and _Backward with the reference's
+    signatures (dnn.h:7-8), the inserted text VERBATIM, then a stand-in for the reference's own code (its im2col path and its
+    cuDNN throw) that only counts how often it is reached.  Built and linked like qr_bodies, against ext/hip_dnn.h.
+
+        dnn_bodies cpu    CPU operands fall through to the stand-in, no device is touched
+        dnn_bodies gpu    GPU operands never fall through: known exact answers with the right shapes (y (N, F, oh, ow), dW in the
+                          filters' shape, dX in the input's; F = shape[0], a 2 x 3 window), every message, no device allocation leaks
+    """
+    _, fwd, bwd = DNN_EDITS
+    o = ["/* generated by tools/apply_with_hip.py: dnn_program_source() — do not edit */",
+         "#include <stdio.h>", "#include <stdlib.h>", "#include <string.h>", "",
+         "#define HAVE_NP_HIP 1", '#include "numpower_host.h"', '#include "hip_dnn.h"', "",
+         "static int g_fell_through;   /* calls that reached the reference's own code (the stand-ins below) */",
+         "static void *reference_body(void) { g_fell_through++; return NULL; }", "",
+         "static NDArray *patched_NDArrayDNN_Conv2D_Forward(NDArray *x, NDArray *filters, int *kernel_size, char activation, int use_bias)",
+         "{", "#ifdef HAVE_NP_HIP", _indent(fwd.new, ""), "#endif",
+         "    (void) kernel_size; (void) activation; (void) use_bias;", "    return (NDArray *) reference_body();", "}", "",
+         "static NDArray **patched_NDArrayDNN_Conv2D_Backward(NDArray *input, NDArray *y, NDArray *filters, int kernel_size, char activation, int use_bias)",
+         "{", "#ifdef HAVE_NP_HIP", _indent(bwd.new, ""), "#endif",
+         "    (void) kernel_size; (void) activation; (void) use_bias;", "    return (NDArray **) reference_body();", "}", ""]
+    o.append(_DNN_PROGRAM_MAIN)
+    return "\n".join(o)
+
+
+_DNN_PROGRAM_MAIN = r"""static int g_failures;
+#define CHECK(cond, ...) do { if (!(cond)) { fprintf(stderr, "dnn_bodies: " __VA_ARGS__); fprintf(stderr, "\n"); g_failures++; } } while (0)
+
+static NDArray *make(const float *v, int d0, int d1, int d2, int d3, int gpu) {
+    int shape[4] = {d0, d1, d2, d3};
+    NDArray *h = NDArray_FromHostBuffer(v, shape, d3 ? 4 : 3);
+    if (!gpu) return h;
+    NDArray *d = NDArray_ToGPU(h);
+    NDArray_FREE(h);
+    return d;
+}
+
+/* true when r has the shape (d0, d1, d2, d3) and exactly the values of want */
+static int is(NDArray *r, int d0, int d1, int d2, int d3, const float *want) {
+    float got[64];
+    const int n = d0 * d1 * d2 * d3;
+    int ok = r && NDArray_NDIM(r) == 4 && NDArray_SHAPE(r)[0] == d0 && NDArray_SHAPE(r)[1] == d1 && NDArray_SHAPE(r)[2] == d2 &&
+             NDArray_SHAPE(r)[3] == d3 && n <= 64;
+    NDArray *h = ok ? NDArray_ToCPU(r) : NULL;
+    ok = ok && h && NDArray_CopyToHostBuffer(h, got) == 0;
+    for (int i = 0; ok && i < n; ++i) ok = got[i] == want[i];
+    if (h) NDArray_FREE(h);
+    return ok;
+}
+
+static int raised(const void *r, const char *message) {
+    return r == NULL && strcmp(numpower_host_last_error(), message) == 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc < 2 || (strcmp(argv[1], "cpu") && strcmp(argv[1], "gpu"))) {
+        fprintf(stderr, "usage: dnn_bodies cpu|gpu\n");
+        return 2;
+    }
+    const int gpu = strcmp(argv[1], "gpu") == 0;
+    /* x (2, 2, 3, 4), filters (3, 2, 2, 3): F = 3 differs from kw = 3's neighbours C = 2 and kh = 2, so a result with the reference's
+     * F = shape[3] or kh = kw = shape[2] cannot have these shapes; dy (2, 3, 2, 2) */
+    const float xv[48] = {3, 1, 1, 3, 1, 2, 2, -2, -3, -1, -2, 3, 3, -3, 0, 2, -3, 2, -3, 0, 2, -1, -1, -2, 2, -2, 3, 0, 0, 0, 1, 0, 0, 3, 2, 2,
+                          1, 1, -1, 3, 0, -2, 2, -2, 3, 1, -3, -3};
+    const float wv[36] = {0, -3, -3, 0, 3, 0, 2, 3, 2, 1, 0, 0, -2, 0, -1, -2, 3, -3, -3, -2, 3, 1, 3, -2, 2, -1, 0, -3, 1, 2, 1, -2, 0, -2, 3, 3};
+    const float dyv[24] = {-2, 0, 3, 2, 1, 1, -3, 2, 0, -3, -2, 0, 2, 0, 1, 3, 1, -1, 1, 1, -3, -3, 1, -1};
+    const long live0 = gpu ? NDArray_LiveDeviceAllocations() : 0;
+    NDArray *x = make(xv, 2, 2, 3, 4, gpu), *w = make(wv, 3, 2, 2, 3, gpu), *dy = make(dyv, 2, 3, 2, 2, gpu);
+    NDArray *x3 = make(xv, 4, 3, 4, 0, gpu), *w_c3 = make(wv, 2, 3, 2, 3, gpu), *w_big = make(wv, 3, 2, 6, 1, gpu), *dy_bad = make(dyv, 2, 3, 4, 1, gpu);
+    NDArray *w_host = make(wv, 3, 2, 2, 3, 0);
+    NDArray *y = patched_NDArrayDNN_Conv2D_Forward(x, w, NULL, 'r', 1);
+    NDArray **g = patched_NDArrayDNN_Conv2D_Backward(x, dy, w, 3, 'r', 1);
+    if (!gpu) {
+        CHECK(!y && !g, "CPU operands were computed on the device");
+        CHECK(g_fell_through == 2, "%d of 2 calls reached the reference's code", g_fell_through);
+    } else {
+        const float y_want[24] = {-6, -6, -19, -12, -3, 11, 2, -15, 20, -23, -13, 10, 0, -3, 7, 2, -28, 23, 24, -12, 7, 1, -1, -30};
+        const float dw_want[36] = {5, 7, 7, -4, -2, 6, -15, 12, -15, 16, -21, -9, 9, -4, -2, 13, 7, 17, 11, -13, 7, -3, -6, -6, -5, -11, -21, -3, -6, 7,
+                                   11, -8, -2, -2, 15, 2};
+        const float dx_want[48] = {-2, -2, 8, -1, 0, -7, -15, -17, 12, -6, 17, -6, -7, -14, 3, 3, 12, 27, -9, -1, 4, -11, 6, -4, -8, -7, -4, 1, 7, 9,
+                                   -27, -13, -5, 8, 10, -5, -2, 10, 15, -3, 9, 0, -9, 2, 0, 12, 1, -5};
+        CHECK(is(y, 2, 3, 2, 2, y_want), "the forward result differs from the exact cross-correlation (2, 3, 2, 2)");
+        CHECK(g && is(g[0], 3, 2, 2, 3, dw_want), "rtn[0] differs from dW in the filters' own shape (3, 2, 2, 3)");
+        CHECK(g && is(g[1], 2, 2, 3, 4, dx_want), "rtn[1] differs from dX in the input's shape (2, 2, 3, 4)");
+        CHECK(raised(patched_NDArrayDNN_Conv2D_Forward(x3, w, NULL, 'r', 1), NPH_DNN_MSG_NDIM), "a 3-d input was not refused");
+        CHECK(raised(patched_NDArrayDNN_Conv2D_Backward(x, x3, w, 3, 'r', 1), NPH_DNN_MSG_NDIM), "a 3-d gradient was not refused");
+        CHECK(raised(patched_NDArrayDNN_Conv2D_Forward(x, w_c3, NULL, 'r', 1), NPH_DNN_MSG_CHANNELS), "filters of 3 channels against 2 were not refused");
+        CHECK(raised(patched_NDArrayDNN_Conv2D_Forward(x, w_big, NULL, 'r', 1), NPH_DNN_MSG_WINDOW), "a 6 x 1 window on a 3 x 4 image was not refused");
+        CHECK(raised(patched_NDArrayDNN_Conv2D_Backward(x, dy_bad, w, 3, 'r', 1), NPH_DNN_MSG_GRADIENT), "a gradient of the wrong shape was not refused");
+        CHECK(raised(patched_NDArrayDNN_Conv2D_Forward(x, w_host, NULL, 'r', 1), NPH_DNN_MSG_DEVICE), "one operand on each device was not refused");
+        CHECK(raised(patched_NDArrayDNN_Conv2D_Backward(x, dy, w_host, 3, 'r', 1), NPH_DNN_MSG_DEVICE), "filters on the CPU were not refused");
+        CHECK(g_fell_through == 0, "%d GPU calls fell through to the reference's code", g_fell_through);
+    }
+    if (g) {
+        NDArray_FREE(g[0]);
+        NDArray_FREE(g[1]);
+        free(g);
+    }
+    if (y) NDArray_FREE(y);
+    NDArray *all[] = {x, w, dy, x3, w_c3, w_big, dy_bad, w_host};
+    for (size_t i = 0; i < sizeof(all) / sizeof(all[0]); ++i)
+        if (all[i]) NDArray_FREE(all[i]);
+    if (gpu) CHECK(NDArray_LiveDeviceAllocations() == live0, "%ld device allocations leaked", NDArray_LiveDeviceAllocations() - live0);
+    printf("dnn_bodies %s: %d calls reached the reference's own code, %d failures\n", argv[1], g_fell_through, g_failures);
+    return g_failures ? 1 : 0;
+}
+"""
 
 
 def signal_program_source() -> str:
@@ -2349,7 +2491,7 @@ class Applied(dict):
 
 
 def apply(checkout: Path, out: Path, keep_cuda: bool = False, extra=()):
-    """-> {edit description: times applied} for EDITS; the edits of `extra` (SIGNAL_EDITS, EIG_EDITS, QR_EDITS) are applied after them, file by file,
+    """-> {edit description: times applied} for EDITS; the edits of `extra` (SIGNAL_EDITS, EIG_EDITS, QR_EDITS, DNN_EDITS) are applied after them, file by file,
     and reported in the result's .extra.  Raises PatchError on any anchor problem or leftover CUDA name."""
     if out.exists():
         raise PatchError("%s exists; give a fresh output directory" % out)
@@ -2371,8 +2513,14 @@ def apply(checkout: Path, out: Path, keep_cuda: bool = False, extra=()):
             (applied if e in EDITS else applied.extra)[e.what] = n
         path.write_text(text)
     (out / "src" / "hip").mkdir(parents=True, exist_ok=True)
-    for g in GLUE_FILES:
+    with_dnn = any(e in DNN_EDITS for e in extra)
+    for g in GLUE_FILES + (DNN_GLUE_FILES if with_dnn else []):
         shutil.copy2(ROOT / g, out / "src" / "hip" / Path(g).name)
+    if with_dnn:   # hip_dnn.c joins the --with-hip sources of the emitted config.m4
+        m4 = (out / "config.m4").read_text()
+        if m4.count(DNN_M4_ANCHOR) != 1:
+            raise PatchError("config.m4: the --with-hip source list was found %d times, not once" % m4.count(DNN_M4_ANCHOR))
+        (out / "config.m4").write_text(m4.replace(DNN_M4_ANCHOR, DNN_M4_SOURCES))
     problems = check_tree(out, raw=not keep_cuda)
     if problems:
         raise PatchError("CUDA / cuBLAS names still %s:\n  " % ("visible to a --with-hip build" if keep_cuda else "in the tree's text") +
@@ -2382,8 +2530,9 @@ def apply(checkout: Path, out: Path, keep_cuda: bool = False, extra=()):
 
 def main(argv):
     keep_cuda = "--keep-cuda" in argv
-    extra = ([] if "--no-signal" in argv else SIGNAL_EDITS) + (EIG_EDITS if "--eig" in argv else []) + (QR_EDITS if "--qr" in argv else [])
-    argv = [a for a in argv if a not in ("--keep-cuda", "--no-signal", "--eig", "--qr")]
+    extra = ([] if "--no-signal" in argv else SIGNAL_EDITS) + (EIG_EDITS if "--eig" in argv else []) + (QR_EDITS if "--qr" in argv else []) + \
+        (DNN_EDITS if "--dnn" in argv else [])
+    argv = [a for a in argv if a not in ("--keep-cuda", "--no-signal", "--eig", "--qr", "--dnn")]
     if len(argv) != 3:
         print(__doc__, file=sys.stderr)
         return 2

@@ -1,0 +1,189 @@
+"""Timing of the device convolution layer (np_dnn.hip): np_conv2d_forward, np_conv2d_backward_data and np_conv2d_backward_filter
+on a short list of layers, after a GEMM warm-up that covers the clock ramp.  Writes profiles/dnn/conv2d_sweep.log (and prints it).
+
+Per layer and operation: ms per call (device events around `reps` calls, the median of the rounds), TFLOP/s (2 M N K of the
+implicit GEMM: forward F x N.P x C.kh.kw, dX C x N.H.W x F.kh.kw, dW F x C.kh.kw x N.P), and np_sgemm on DENSE operands of the same
+(M, N, K) in the same run with the ratio gemm / conv: the ceiling the project's own GEMM sets for those extents.  The 1 x 1 layer
+is a GEMM with no gather: a ratio far below 1 THERE is a tile-loop problem, not a gather problem.
+
+Every layer runs in a child process of its own under its own time limit (--limit seconds); the sweep stops at the first
+layer that fails or runs out of time.  --torch adds, as information, torch.nn.functional.conv2d and its autograd on the device
+where this installation runs them (one more child); if it does not, the log says so in one line.
+
+Usage: python tools/dnn_sweep.py [--layers 0,1,...] [--rounds N] [--limit S] [--torch] [--out FILE]
+       python tools/dnn_sweep.py --profile LAYER     three calls of each operation and nothing else, for a run under the kernel profiler"""
+import argparse
+import statistics
+import subprocess
+import sys
+import time
+from pathlib import Path
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+# name, (N, C, H, W), (F, kh, kw), (ph, pw)
+LAYERS = [("3x3 64->64 at 56^2, batch 32", (32, 64, 56, 56), (64, 3, 3), (1, 1)),
+          ("3x3 128->128 at 28^2, batch 32", (32, 128, 28, 28), (128, 3, 3), (1, 1)),
+          ("1x1 256->64 at 56^2, batch 32", (32, 256, 56, 56), (64, 1, 1), (0, 0)),
+          ("7x7 3->64 at 224^2 pad 3, batch 8", (8, 3, 224, 224), (64, 7, 7), (3, 3)),
+          ("5x5 1->32 at 28^2, batch 512", (512, 1, 28, 28), (32, 5, 5), (0, 0))]
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--layers", default=",".join(str(i) for i in range(len(LAYERS))))
+ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--limit", type=int, default=120, help="seconds each child process may take")
+ap.add_argument("--torch", action="store_true")
+ap.add_argument("--out", default=str(ROOT / "profiles" / "dnn" / "conv2d_sweep.log"))
+ap.add_argument("--profile", type=int, default=None)
+ap.add_argument("--child", default=None, help="internal: 'layer:<i>' or 'torch'")
+args = ap.parse_args()
+
+
+def shapes(i):
+    _, (N, C, H, W), (F, kh, kw), (ph, pw) = LAYERS[i]
+    oh, ow = H + 2 * ph - kh + 1, W + 2 * pw - kw + 1
+    gemms = {"forward": (F, N * oh * ow, C * kh * kw), "dX": (C, N * H * W, F * kh * kw), "dW": (F, C * kh * kw, N * oh * ow)}
+    return (N, C, H, W), (F, C, kh, kw), (N, F, oh, ow), (ph, pw), gemms
+
+
+def run_layer(i, rounds, profile=False):
+    import ctypes as C_
+    import numpy as np
+    from numpower_amd import device as D
+    from numpower_amd._lib import Timer, check, load
+    D.init(0)
+    lib = load()
+    t = Timer()
+    xs, ws, ys, (ph, pw), gemms = shapes(i)
+    rng = np.random.default_rng(i)
+    dev = lambda s: D.DeviceArray.from_host(rng.standard_normal(s).astype(np.float32))
+    x, w, dy = dev(xs), dev(ws), dev(ys)
+    y, dx, dw = D.DeviceArray(ys), D.DeviceArray(xs), D.DeviceArray(ws)
+    dims = (xs[0], xs[1], xs[2], xs[3], ws[0], ws[2], ws[3], ph, pw)
+    ops = {"forward": lambda: check(lib.np_conv2d_forward(x.ptr, w.ptr, *dims, y.ptr)),
+           "dX": lambda: check(lib.np_conv2d_backward_data(dy.ptr, w.ptr, *dims, dx.ptr)),
+           "dW": lambda: check(lib.np_conv2d_backward_filter(x.ptr, dy.ptr, *dims, dw.ptr))}
+    if profile:
+        for _ in range(3):
+            for fn in ops.values():
+                fn()
+        D.sync()
+        return
+    ga = dev((4096, 4096))                      # clock ramp: ~1 s of 4096^3 GEMMs
+    gc = D.DeviceArray((4096, 4096))
+    t0 = time.time()
+    while time.time() - t0 < 1.0:
+        for _ in range(10):
+            check(lib.np_sgemm(4096, 4096, 4096, ga.ptr, ga.ptr, gc.ptr))
+        D.sync()
+
+    def median_ms(fn):
+        fn()
+        D.sync()
+        t0 = time.time()
+        fn()
+        D.sync()
+        reps = max(3, min(200, int(0.1 / max(time.time() - t0, 1e-5))))
+        ms = []
+        for _ in range(rounds):
+            t.start()
+            for _ in range(reps):
+                fn()
+            t.stop()
+            ms.append(t.elapsed_ms() / reps)
+        return statistics.median(ms)
+
+    for name, fn in ops.items():
+        M, N, K = gemms[name]
+        a, b, c = dev((M, K)), dev((K, N)), D.DeviceArray((M, N))
+        conv_ms = median_ms(fn)
+        tm, s = C_.c_int(), C_.c_int()
+        check(lib.np_debug_dnn_last_path(C_.byref(tm), C_.byref(s)))
+        gemm_ms = median_ms(lambda: check(lib.np_sgemm(M, N, K, a.ptr, b.ptr, c.ptr)))
+        flop = 2.0 * M * N * K
+        print("%-34s %-8s %6d %9d %7d %9.4f %8.2f %9.4f %8.2f %7.3f %4d %4d" % (LAYERS[i][0], name, M, N, K, conv_ms, flop / conv_ms * 1e-9, gemm_ms,
+                                                                            flop / gemm_ms * 1e-9, gemm_ms / conv_ms, tm.value, s.value), flush=True)
+        for d in (a, b, c):
+            d.free()
+
+
+def run_torch(layers, rounds):
+    import torch
+    if not torch.cuda.is_available():
+        print("torch.nn.functional.conv2d: this torch sees no device", flush=True)
+        return
+    for i in layers:
+        xs, ws, ys, pad, gemms = shapes(i)
+        x = torch.randn(xs, device="cuda", requires_grad=True)
+        w = torch.randn(ws, device="cuda", requires_grad=True)
+        dy = torch.randn(ys, device="cuda")
+
+        def ms(fn):
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            out = []
+            for _ in range(rounds):
+                t0 = time.time()
+                for _ in range(5):
+                    fn()
+                torch.cuda.synchronize()
+                out.append((time.time() - t0) / 5 * 1e3)
+            return statistics.median(out)
+
+        fwd = ms(lambda: torch.nn.functional.conv2d(x.detach(), w.detach(), padding=pad))
+
+        def both():
+            x.grad = w.grad = None
+            torch.nn.functional.conv2d(x, w, padding=pad).backward(dy)
+
+        print("%-34s torch (information): forward %.4f ms, forward + both gradients %.4f ms" % (LAYERS[i][0], fwd, ms(both)), flush=True)
+
+
+if args.profile is not None:
+    run_layer(args.profile, 1, profile=True)
+    sys.exit(0)
+if args.child:
+    if args.child == "torch":
+        run_torch([int(s) for s in args.layers.split(",")], args.rounds)
+    else:
+        run_layer(int(args.child.split(":")[1]), args.rounds)
+    sys.exit(0)
+
+lines = []
+
+
+def say(line=""):
+    print(line, flush=True)
+    lines.append(line)
+
+
+def child(what):
+    """-> True when the child ended well; its output joins the log either way"""
+    try:
+        proc = subprocess.run([sys.executable, __file__, "--child", what, "--layers", args.layers, "--rounds", str(args.rounds)],
+                              capture_output=True, text=True, timeout=args.limit)
+    except subprocess.TimeoutExpired:
+        say("%s: no result inside %d s" % (what, args.limit))
+        return False
+    for line in proc.stdout.splitlines():
+        say(line)
+    if proc.returncode != 0:
+        say("%s: ended with status %d: %s" % (what, proc.returncode, proc.stderr.strip().splitlines()[-1] if proc.stderr.strip() else ""))
+    return proc.returncode == 0
+
+
+say("np_conv2d_forward / _backward_data / _backward_filter, fp32, median of %d rounds; gemm = np_sgemm on dense operands of the same M, N, K" % args.rounds)
+say("%-34s %-8s %6s %9s %7s %9s %8s %9s %8s %7s %4s %4s" % ("layer", "op", "M", "N", "K", "conv ms", "TFLOP/s", "gemm ms", "TFLOP/s", "gemm/conv", "TM", "S"))
+ok = True
+for i in (int(s) for s in args.layers.split(",")):
+    ok = child("layer:%d" % i)
+    if not ok:
+        break                                   # nothing more is started on a device after a failure
+if ok and args.torch:
+    if not child("torch"):
+        say("torch.nn.functional.conv2d did not run on the device in this installation")
+out = Path(args.out)
+out.parent.mkdir(parents=True, exist_ok=True)
+out.write_text("\n".join(lines) + "\n")
+sys.exit(0 if ok else 1)
