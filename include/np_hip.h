@@ -257,6 +257,16 @@ typedef enum np_reduce_op {
     NP_SUM = 0, NP_PROD = 1, NP_MIN = 2, NP_MAX = 3, NP_MEAN = 4,
     NP_REDUCE_OP_COUNT
 } np_reduce_op;
+/* NP_MIN / NP_MAX and NaN, in np_reduce_all(_dev) and np_reduce_axis: the reference's loops (NDArray_Min / NDArray_Max,
+ * ndarray.c:752-772, 939-959; the axis forms :818-839) start from position 0 of the reduced slice and replace on a strict
+ * compare.  So the result is NaN exactly when position 0 of the slice is NaN; a NaN in any later position never wins; an
+ * all-NaN slice gives NaN.  The kernels combine in a tree from +-inf and put the NaN of position 0 back where the final
+ * value is written (r_first_nan, np_internal.h).  The np_fused_chain_reduce* calls follow the same rule with the chain's
+ * value in position 0.
+ * Sign of a zero extreme: where the extreme of a slice is zero and the slice holds both +0 and -0, the reference returns
+ * whichever comes first; a tree order cannot promise that, and either zero may be returned.  Everything else about
+ * min / max is bit-exact and independent of the launch geometry.
+ * NP_SUM / NP_PROD / NP_MEAN propagate NaN and Inf as IEEE arithmetic does in any order. */
 
 /* Full reduction to one host float.  Replaces cuda_sum_float / cuda_prod_float /
  * cuda_min_float / cuda_max_float (cuda_math.cu:921,934,1032,1016).  Deterministic two-pass

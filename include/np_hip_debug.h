@@ -94,6 +94,9 @@ int np_debug_hw_ids(unsigned *host_out2, size_t workgroups);
 /* tools: the CU count every planner (GEMM tiles / stream-K, streaming grids) assumes from now on; 0 = the device's own.  For a CU-masked
  * library stream (np_set_stream): a product planned for 256 CUs runs a partial extra round of workgroups on 248.  Process-global. */
 int np_debug_set_cus(int cus);
+/* tests: the CU count the planners assume right now (np_debug_set_cus's value, else the current device's own): what a test needs to
+ * work out which kernel a shape is planned onto. */
+int np_debug_cus(int *host_cus);
 /* testing: a one-lane kernel on the library stream raises `bits` in the current device's error word — what a device-side wait
  * that gives up does (1 = a stream-ordering wait of np_comm, 2 = a stream-K finisher).  np_sync / np_memcpy_d2h / host-result
  * calls / np_comm_* calls on this device return NP_ERR_DEVICE from then on, until np_clear_device_error(). */
@@ -125,6 +128,37 @@ int np_debug_conv2d_staged_path(int on);
  * count TM (32, 64 or 128; 0 = none yet) and, for _backward_filter, the number of slices S its reduction was cut into (1: written
  * directly, no fold kernel); 0 slices after the two others.  Plain process globals. */
 int np_debug_dnn_last_path(int *host_tm, int *host_slices);
+/* tests / tools: which kernel families the last np_reduce_axis or np_reduce_all(_dev) call of the process launched, the calls it
+ * makes on its own partials included: the OR of the NP_REDUCE_PATH_ bits below (0 = none yet).  A plain process global, cleared
+ * at the top of those entry points; calls the library makes itself (split-K GEMM folds, chain partials) overwrite it too. */
+#define NP_REDUCE_PATH_ROWS_BLOCK 0x0001u          /* inner == 1: reduce_rows_block, a workgroup per row */
+#define NP_REDUCE_PATH_ROWS_BLOCK_CHUNKED 0x0002u  /* reduce_rows_block over chunks of each row; the partials are reduced again */
+#define NP_REDUCE_PATH_ROWS_STAGED 0x0004u         /* reduce_rows_staged: slabs of short rows through LDS */
+#define NP_REDUCE_PATH_ROWS_GROUP 0x0008u          /* reduce_rows_group<L>: L = 2 .. 32 lanes per row */
+#define NP_REDUCE_PATH_ROWS_WAVE 0x0010u           /* reduce_rows_wave: a wave per row */
+#define NP_REDUCE_PATH_COLS_ONE_PASS 0x0020u       /* inner > 1: reduce_axis_cols writes the result */
+#define NP_REDUCE_PATH_COLS_TWO_PASSES 0x0040u     /* reduce_axis_cols over 2 .. 255 splits of the axis + reduce_axis_cols over the partials */
+#define NP_REDUCE_PATH_COLS_SPLITS_RECURSE 0x0080u /* reduce_axis_cols over >= 256 splits; the partials are reduced again */
+#define NP_REDUCE_PATH_COLS_XCD_RUNS 0x0100u       /* a reduce_axis_cols launch dealt its tiles to the XCDs in runs */
+#define NP_REDUCE_PATH_SMALL_INNER 0x0200u         /* reduce_small_inner (dword walk); the partials are reduced again */
+#define NP_REDUCE_PATH_SMALL_INNER_V4 0x0400u      /* reduce_small_inner_v4 (float4 walk); the partials are reduced again */
+#define NP_REDUCE_PATH_GENERIC 0x0800u             /* reduce_axis_generic, a thread per output */
+#define NP_REDUCE_PATH_GENERIC_CHUNKED 0x1000u     /* reduce_axis_generic over chunks of the axis; the partials are reduced again */
+#define NP_REDUCE_PATH_ALL_ONE_LAUNCH 0x2000u      /* reduce_all_pass1, folded by its last workgroup */
+#define NP_REDUCE_PATH_ALL_TWO_LAUNCHES 0x4000u    /* reduce_all_pass1 + reduce_all_pass2 */
+int np_debug_reduce_last_path(unsigned *host_mask);
+/* the same for the last np_fused_chain_reduce / _reduce_dev / _reduce_axis call: the OR of the NP_CHAIN_PATH_ bits.  Partials
+ * (NP_CHAIN_PATH_SPLIT) and the temporary go through np_reduce_axis, whose own probe then tells how. */
+#define NP_CHAIN_PATH_FLAT 0x0001u         /* full reduction: fused_chain_kernel (the interpreter) */
+#define NP_CHAIN_PATH_STATIC_FLAT 0x0002u  /* full reduction: a compiled chain (np_fused_static.hip) */
+#define NP_CHAIN_PATH_ROWS 0x0004u         /* last axis: fused_chain_rows_kernel */
+#define NP_CHAIN_PATH_ROWS_STAGED 0x0008u  /* last axis: fused_chain_rows_staged_kernel */
+#define NP_CHAIN_PATH_STATIC_ROWS 0x0010u  /* last axis: a compiled chain */
+#define NP_CHAIN_PATH_COLS 0x0020u         /* first axis: fused_chain_cols_kernel */
+#define NP_CHAIN_PATH_STATIC_COLS 0x0040u  /* first axis: a compiled chain */
+#define NP_CHAIN_PATH_SPLIT 0x0080u        /* the axis was cut into chunks: np_reduce_axis folds the partials */
+#define NP_CHAIN_PATH_TEMPORARY 0x0100u    /* the chain was stored to a temporary and np_reduce_axis reduced it */
+int np_debug_chain_reduce_last_path(unsigned *host_mask);
 
 #ifdef __cplusplus
 }

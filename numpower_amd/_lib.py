@@ -93,6 +93,7 @@ PROTOTYPES = {
     "np_comm_set_wait_limit": (C.c_int, [C.c_double]),
     "np_debug_hw_ids": (C.c_int, [C.POINTER(C.c_uint), C.c_size_t]),
     "np_debug_set_cus": (C.c_int, [C.c_int]),
+    "np_debug_cus": (C.c_int, [C.POINTER(C.c_int)]),
     "np_comm_debug_model": (C.c_int, [C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "np_comm_sync_mode": (C.c_int, []),
     "np_comm_piece": (C.c_int, [C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -173,6 +174,8 @@ PROTOTYPES = {
     "np_debug_conv2d_last_path": (C.c_int, [C.POINTER(C.c_int)]),
     "np_debug_conv2d_staged_path": (C.c_int, [C.c_int]),
     "np_debug_dnn_last_path": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "np_debug_reduce_last_path": (C.c_int, [C.POINTER(C.c_uint)]),
+    "np_debug_chain_reduce_last_path": (C.c_int, [C.POINTER(C.c_uint)]),
     "np_clear_device_error": (C.c_int, [C.POINTER(C.c_uint)]),
     "np_debug_clock_mhz": (C.c_int, [C.POINTER(C.c_float)]),
 }

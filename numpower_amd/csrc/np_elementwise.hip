@@ -786,9 +786,14 @@ __device__ __forceinline__ void fused_fetch(float (&dst)[U * G], const float *p,
 
 // VACC: the sink accumulates per register element (rv[u * G + e], for column reductions where every
 // element of a slot belongs to a different result) instead of into the one scalar racc.
+// [nan0_begin, nan0_end): the flat indices that are POSITION 0 of a reduced slice (element 0 of a full reduction, the first
+// element of the row, row 0 of a column reduction).  NP_MIN / NP_MAX follow the reference's loop, which starts from that element
+// (np_hip.h, np_reduce_op): a NaN chain value there becomes the accumulator, and stays — no later compare replaces a NaN.  It is
+// always slot u = 0 of the first trip of the span's first thread (lane 0 / wave 0), the `a` side of every combine up to the
+// writer, so it reaches the output (or partial 0 / chunk 0, where the folds look for it).
 template <int U, int G, bool LIGHT, typename I, bool VACC, bool RAGGED = false, bool KEEP = false>
 __device__ __forceinline__ void fused_span_impl(FusedArgsK f, float *__restrict__ out, I elem0, I nslots, I tid,
-                                                I stride, float &racc, float (&rv)[U * G]) {
+                                                I stride, float &racc, float (&rv)[U * G], I nan0_begin = 0, I nan0_end = 0) {
     constexpr int N = U * G;
     const int sink = f->sink;
     const int n_ops = f->n_ops;
@@ -799,6 +804,8 @@ __device__ __forceinline__ void fused_span_impl(FusedArgsK f, float *__restrict_
     const I ragged_cols = RAGGED ? cols : (I)0;   // float4 slots of a broadcast with cols % 4 != 0 may straddle rows (a kernel variant of its own:
                                                   // with the extra code in the common kernel, aligned exp(X) + col lost 9 %)
     const unsigned div_m = f->div_m, div_s1 = f->div_s1, div_s2 = f->div_s2;
+    // does this thread's first slot (trip 0, u = 0) hold position 0 of a slice?  Decided once: the loop tests one flag
+    bool own0 = sink >= NP_MIN && tid < nslots && elem0 + tid * G >= nan0_begin && elem0 + tid * G < nan0_end;
     for (I base = 0; base < nslots; base += stride * U) {
         I first[U], row[U], col[U];
         bool live[U];
@@ -888,11 +895,17 @@ __device__ __forceinline__ void fused_span_impl(FusedArgsK f, float *__restrict_
                 for (int e = 0; e < N; ++e)
                     if (live[e / G] && acc[e] > rv[e]) rv[e] = acc[e];
             }
+            if (own0) {   // (first trip, slot 0)
+                own0 = false;
+#pragma unroll
+                for (int e = 0; e < G; ++e)
+                    if (first[0] + (I)e < nan0_end && acc[e] != acc[e]) rv[e] = acc[e];
+            }
             continue;
         }
         if (sink >= 0) {
             // reduction at the end of the chain: the value never goes to memory (uniform branch;
-            // same combine rules as np_reduce_all: NaN never replaces in min / max)
+            // same combine rules as np_reduce_all: NaN never replaces in min / max, except the one in position 0 — below)
             if (sink == NP_SUM) {
 #pragma unroll
                 for (int e = 0; e < N; ++e) racc += live[e / G] ? acc[e] : 0.0f;
@@ -907,6 +920,12 @@ __device__ __forceinline__ void fused_span_impl(FusedArgsK f, float *__restrict_
 #pragma unroll
                 for (int e = 0; e < N; ++e)
                     if (live[e / G] && acc[e] > racc) racc = acc[e];
+            }
+            if (own0) {   // (first trip, slot 0)
+                own0 = false;
+#pragma unroll
+                for (int e = 0; e < G; ++e)
+                    if (first[0] + (I)e < nan0_end && acc[e] != acc[e]) racc = acc[e];
             }
             continue;
         }
@@ -924,9 +943,9 @@ __device__ __forceinline__ void fused_span_impl(FusedArgsK f, float *__restrict_
 
 template <int U, int G, bool LIGHT, typename I, bool RAGGED = false, bool KEEP = false>
 __device__ __forceinline__ void fused_span(FusedArgsK f, float *__restrict__ out, I elem0, I nslots, I tid,
-                                           I stride, float &racc) {
+                                           I stride, float &racc, I nan0_begin = 0, I nan0_end = 0) {
     float unused[U * G];
-    fused_span_impl<U, G, LIGHT, I, false, RAGGED, KEEP>(f, out, elem0, nslots, tid, stride, racc, unused);
+    fused_span_impl<U, G, LIGHT, I, false, RAGGED, KEEP>(f, out, elem0, nslots, tid, stride, racc, unused, nan0_begin, nan0_end);
 }
 
 __device__ __forceinline__ float sink_identity(int sink) {
@@ -962,11 +981,11 @@ __global__ __launch_bounds__(256) void fused_chain_rows_kernel(FusedArgs by_valu
     const I out_stride = BLOCK ? (I)gridDim.y : 1, out_off = BLOCK ? (I)blockIdx.y : 0;
     for (I r = first_row; r < rows; r += row_stride) {
         float racc = sink_identity(sink);
-        fused_span<UU, G, LIGHT, I>(f, out, r * cols + slot0 * G, nslots, lane, width, racc);
+        fused_span<UU, G, LIGHT, I>(f, out, r * cols + slot0 * G, nslots, lane, width, racc, r * cols, r * cols + 1);
         if constexpr (G == 4) {   // a row of cols % 4 != 0 floats: its last 1-3 elements, one per lane, behind the float4 slots
             const I tail = cols - (cols / 4) * 4;
             if (tail != 0 && (!BLOCK || blockIdx.y == gridDim.y - 1))
-                fused_span<1, 1, LIGHT, I>(f, out, r * cols + (cols / 4) * 4, tail, lane, width, racc);
+                fused_span<1, 1, LIGHT, I>(f, out, r * cols + (cols / 4) * 4, tail, lane, width, racc, r * cols, r * cols + 1);
         }
         if constexpr (BLOCK) {
 #pragma unroll
@@ -1012,7 +1031,7 @@ __global__ __launch_bounds__(256) void fused_chain_cols_kernel(FusedArgs by_valu
         // thread owns its G columns for the whole chunk, so nothing has to be combined across waves
         const I slot = (I)blockIdx.x * 256 + threadIdx.x;
         if (slot < slots_per_row) {
-            fused_span_impl<CU, G, LIGHT, I, true>(f, out, r0 * cols, (r1 - r0) * slots_per_row, slot, slots_per_row, racc, rv);
+            fused_span_impl<CU, G, LIGHT, I, true>(f, out, r0 * cols, (r1 - r0) * slots_per_row, slot, slots_per_row, racc, rv, (I)0, cols);
 #pragma unroll
             for (int e = 0; e < G; ++e) {
                 float v = rv[e];
@@ -1027,7 +1046,7 @@ __global__ __launch_bounds__(256) void fused_chain_cols_kernel(FusedArgs by_valu
     // slots are v = (wave + 4 i) * slots_per_row + slot
     if (slot < slots_per_row)
         fused_span_impl<CU, G, LIGHT, I, true>(f, out, r0 * cols, (r1 - r0) * slots_per_row, wave * slots_per_row + slot,
-                                              4 * slots_per_row, racc, rv);
+                                              4 * slots_per_row, racc, rv, (I)0, cols);
     // cross-wave combine through LDS, lane fastest: a wave's 64 stores / loads of one element land on 64 different banks
     // (lane-major [lane][e] put lanes l and l + 16 on one bank: 74 % of this kernel's LDS cycles were conflicts)
     __shared__ float part[4][G][64];
@@ -1064,10 +1083,10 @@ __global__ __launch_bounds__(256) void fused_chain_kernel(FusedArgs by_value, fl
     float racc = sink == NP_SUM ? 0.0f : sink == NP_PROD ? 1.0f : sink == NP_MIN ? INFINITY : -INFINITY;
     if constexpr (VEC) {
         const I nvec = n / 4;
-        fused_span<U, 4, LIGHT, I, RAGGED, KEEP>(f, out, (I)0, nvec, tid, stride, racc);
-        fused_span<1, 1, LIGHT, I>(f, out, nvec * 4, n - nvec * 4, tid, stride, racc);   // ragged tail (< 4 elements)
+        fused_span<U, 4, LIGHT, I, RAGGED, KEEP>(f, out, (I)0, nvec, tid, stride, racc, (I)0, (I)1);
+        fused_span<1, 1, LIGHT, I>(f, out, nvec * 4, n - nvec * 4, tid, stride, racc, (I)0, (I)1);   // ragged tail (< 4 elements)
     } else {
-        fused_span<U, 1, LIGHT, I>(f, out, (I)0, n, tid, stride, racc);   // 4-byte aligned views
+        fused_span<U, 1, LIGHT, I>(f, out, (I)0, n, tid, stride, racc, (I)0, (I)1);   // 4-byte aligned views
     }
     if (sink >= 0) {   // one partial per workgroup, folded in a fixed order (deterministic) by the last workgroup or a second launch
         __shared__ float lds4[4];
@@ -1206,7 +1225,7 @@ __global__ __launch_bounds__(256) void fused_chain_rows_staged_kernel(FusedArgs 
             float a = np::dev::r_identity<SINK>();
             for (unsigned c = t; c < len; c += T) a = np::dev::r_combine<SINK>(a, p[c]);
             for (unsigned off = T >> 1; off > 0; off >>= 1) a = np::dev::r_combine<SINK>(a, __shfl_xor(a, (int)off, 64));
-            if (t == 0) out[row0 + r] = mean_div != 0.0f ? __fdiv_rn(a, mean_div) : a;
+            if (t == 0) out[row0 + r] = np::dev::r_first_nan<SINK>(mean_div != 0.0f ? __fdiv_rn(a, mean_div) : a, p);   // (p[0]: the chain value in position 0)
         }
         return;
     }
@@ -1221,7 +1240,7 @@ __global__ __launch_bounds__(256) void fused_chain_rows_staged_kernel(FusedArgs 
         if (c < len) a0 = np::dev::r_combine<SINK>(a0, p[c]);
         float v = np::dev::r_combine<SINK>(a0, a1);
         if (mean_div != 0.0f) v = __fdiv_rn(v, mean_div);
-        out[row0 + r] = v;
+        out[row0 + r] = np::dev::r_first_nan<SINK>(v, p);   // (p[0]: the chain value in position 0)
     }
 }
 
@@ -1246,6 +1265,10 @@ static bool fused_rows_staged_mid_shape(size_t rows, size_t cols) {
     const size_t trips = (slots + 2 * L - 1) / (2 * L);
     return (double)slots / (double)(trips * 2 * L) < 0.9;
 }
+
+// np_debug_chain_reduce_last_path: the NP_CHAIN_PATH_* bits of what the last np_fused_chain_reduce(_dev / _axis) call launched.
+// A plain process global, cleared at the top of those entry points.
+static unsigned g_chain_last_path = 0;
 
 static bool fused_axis_shape_ok(size_t rows, size_t cols, int axis) {
     if (rows * cols >= (size_t(1) << 32)) return false;
@@ -1446,6 +1469,7 @@ static int fused_chain_impl(const float *const *inputs, const int *input_kinds, 
             np::Scratch tmp;
             if (int rc = tmp.alloc(n * sizeof(float))) return rc;
             if (int rc = fused_chain_impl(inputs, input_kinds, n_inputs, ops, n_ops, (float *)tmp.ptr, rows, cols, -1)) return rc;
+            g_chain_last_path |= NP_CHAIN_PATH_TEMPORARY;
             const int rop = mean_div != 0.0f ? NP_MEAN : sink;
             return np_reduce_axis(rop, (const float *)tmp.ptr, rows, cols, 1, out, 0);
         }
@@ -1479,6 +1503,7 @@ static int fused_chain_impl(const float *const *inputs, const int *input_kinds, 
         else NP_FRS(NP_MAX);
 #undef NP_FRS
         NP_LAUNCH_CHECK("fused_chain_rows_staged_kernel");
+        g_chain_last_path |= NP_CHAIN_PATH_ROWS_STAGED;
         return NP_OK;
     }
     if (axis_mode == 1) {
@@ -1522,6 +1547,7 @@ static int fused_chain_impl(const float *const *inputs, const int *input_kinds, 
             while (Lc > 4 && (size_t)Lc >= slots) Lc >>= 1;
             size_t gridc = (rows + 4 * (64 / Lc) - 1) / (4 * (64 / Lc));
             if (gridc > cap) gridc = cap;
+            g_chain_last_path |= NP_CHAIN_PATH_STATIC_ROWS;
             return np::fused_static_rows(sd, dst, rows, cols, Lc, div, (unsigned)gridc);
         }
         const dim3 grid2((unsigned)grid, (unsigned)chunks);
@@ -1531,6 +1557,7 @@ static int fused_chain_impl(const float *const *inputs, const int *input_kinds, 
         else { if (block) NP_FR(4, false, true); else NP_FR(4, false, false); }
 #undef NP_FR
         NP_LAUNCH_CHECK("fused_chain_rows_kernel");
+        g_chain_last_path |= NP_CHAIN_PATH_ROWS | (chunks > 1 ? NP_CHAIN_PATH_SPLIT : 0u);
         if (chunks > 1) {
             if (int rc = np_reduce_axis(sink, dst, rows, chunks, 1, out, 0)) return rc;
             if (mean_div != 0.0f) return np_binary(NP_DIVIDE, out, NP_FULL, &mean_div, NP_HOST_SCALAR, out, 1, rows, 0, 0);
@@ -1565,6 +1592,7 @@ static int fused_chain_impl(const float *const *inputs, const int *input_kinds, 
             if (int rc = np::fused_static_cols(sd, dst, rows, cols, rows_per_chunk, div, (unsigned)col_blocks, (unsigned)chunks,
                                                g_variant == 7004 || g_variant / 1000 == 14 ? 4 : 2))   // (A/B: 7004, 14000 + wg per CU)
                 return rc;
+            g_chain_last_path |= NP_CHAIN_PATH_STATIC_COLS | (chunks > 1 ? NP_CHAIN_PATH_SPLIT : 0u);
             if (chunks > 1) {
                 if (int rc = np_reduce_axis(sink, dst, 1, chunks, cols, out, 0)) return rc;
                 if (mean_div != 0.0f) return np_binary(NP_DIVIDE, out, NP_FULL, &mean_div, NP_HOST_SCALAR, out, 1, cols, 0, 0);
@@ -1588,6 +1616,7 @@ static int fused_chain_impl(const float *const *inputs, const int *input_kinds, 
         }
 #undef NP_FCOL
         NP_LAUNCH_CHECK("fused_chain_cols_kernel");
+        g_chain_last_path |= NP_CHAIN_PATH_COLS | (chunks > 1 ? NP_CHAIN_PATH_SPLIT : 0u);
         if (chunks > 1) {
             if (int rc = np_reduce_axis(sink, dst, 1, chunks, cols, out, 0)) return rc;
             if (mean_div != 0.0f) return np_binary(NP_DIVIDE, out, NP_FULL, &mean_div, NP_HOST_SCALAR, out, 1, cols, 0, 0);
@@ -1597,6 +1626,7 @@ static int fused_chain_impl(const float *const *inputs, const int *input_kinds, 
     if (compiled && np::fused_static_covers(sd, sink, -1)) {
         const unsigned grid = reduce_blocks ? reduce_blocks : grid_for(n / 4 + 1, 2, 0);
         if (int rc = np::fused_static_flat(sd, out, n, sink, grid, f.ticket, f.result)) return rc;
+        if (sink >= 0) g_chain_last_path |= NP_CHAIN_PATH_STATIC_FLAT;
         if (sink >= 0 && !f.ticket) return np::fold_partials(sink, (const float *)partials.ptr, reduce_blocks, result);
         return NP_OK;
     }
@@ -1636,6 +1666,7 @@ static int fused_chain_impl(const float *const *inputs, const int *input_kinds, 
     }
 #undef NP_FC
     NP_LAUNCH_CHECK("fused_chain_kernel");
+    if (sink >= 0) g_chain_last_path |= NP_CHAIN_PATH_FLAT;
     if (sink >= 0 && !f.ticket) return np::fold_partials(sink, (const float *)partials.ptr, reduce_blocks, result);
     return NP_OK;
 }
@@ -1670,6 +1701,7 @@ int np_fused_chain_reduce(const float *const *inputs, const int *input_kinds, in
         return np::fail(NP_ERR_INVALID, "np_fused_chain_reduce: unknown reduction %d", reduce_op);
     if (rows * cols == 0) return np::fail(NP_ERR_INVALID, "np_fused_chain_reduce: empty input");
     if (int rc = np::ensure_init()) return rc;
+    g_chain_last_path = 0;
     np::ResultCall call;
     float *slot = call.slot;
     if (!slot) return NP_ERR_ALLOC;
@@ -1690,6 +1722,7 @@ int np_fused_chain_reduce_dev(const float *const *inputs, const int *input_kinds
         return np::fail(NP_ERR_INVALID, "np_fused_chain_reduce_dev: unknown reduction %d", reduce_op);
     if (rows * cols == 0) return np::fail(NP_ERR_INVALID, "np_fused_chain_reduce_dev: empty input");
     if (int rc = np::ensure_init()) return rc;
+    g_chain_last_path = 0;
     const int sink = reduce_op == NP_MEAN ? NP_SUM : reduce_op;
     if (int rc = fused_chain_impl(inputs, input_kinds, n_inputs, ops, n_ops, dev_out, rows, cols, sink)) return rc;
     if (reduce_op == NP_MEAN) {
@@ -1709,6 +1742,7 @@ int np_fused_chain_reduce_axis(const float *const *inputs, const int *input_kind
         return np::fail(NP_ERR_INVALID, "np_fused_chain_reduce_axis: unknown reduction %d", reduce_op);
     if (rows * cols == 0) return np::fail(NP_ERR_INVALID, "np_fused_chain_reduce_axis: empty input");
     if (int rc = np::ensure_init()) return rc;
+    g_chain_last_path = 0;
     const int sink = reduce_op == NP_MEAN ? NP_SUM : reduce_op;
     const float mean_div = reduce_op == NP_MEAN ? (float)(axis == 1 ? cols : rows) : 0.0f;
     if (fused_axis_shape_ok(rows, cols, axis))
@@ -1718,8 +1752,15 @@ int np_fused_chain_reduce_axis(const float *const *inputs, const int *input_kind
     np::Scratch tmp;
     if (int rc = tmp.alloc(rows * cols * sizeof(float))) return rc;
     if (int rc = fused_chain_impl(inputs, input_kinds, n_inputs, ops, n_ops, (float *)tmp.ptr, rows, cols, -1)) return rc;
+    g_chain_last_path |= NP_CHAIN_PATH_TEMPORARY;
     return axis == 1 ? np_reduce_axis(reduce_op, (const float *)tmp.ptr, rows, cols, 1, out, 0)
                      : np_reduce_axis(reduce_op, (const float *)tmp.ptr, 1, rows, cols, out, 0);
+}
+
+int np_debug_chain_reduce_last_path(unsigned *host_mask) {
+    if (!host_mask) return np::fail(NP_ERR_INVALID, "np_debug_chain_reduce_last_path: null pointer");
+    *host_mask = g_chain_last_path;
+    return NP_OK;
 }
 
 int np_elementwise_set_variant(int variant) {

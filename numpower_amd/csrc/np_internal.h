@@ -154,9 +154,25 @@ template <int OP>
 __device__ __forceinline__ float r_combine(float a, float b) {
     if constexpr (OP == NP_SUM || OP == NP_MEAN) return a + b;
     if constexpr (OP == NP_PROD) return a * b;
-    // same comparison the reference uses (ndarray.c:764, :951): NaN never replaces
+    // same comparison the reference uses (ndarray.c:764, :951): a NaN in `b` never replaces `a`.  The reference starts from
+    // element 0 of the slice, the accumulators here from r_identity: a NaN in position 0, which the reference keeps to the
+    // end, is lost by this comparison and put back by r_first_nan() where the final value is written.
     if constexpr (OP == NP_MIN) return (b < a) ? b : a;
     return (b > a) ? b : a;
+}
+
+// NP_MIN / NP_MAX, at the place that writes a slice's final value: `first` points at position 0 of the reduced slice (nullptr:
+// the value is a partial, or the caller has no rule to apply).  The reference's loop starts from that element and replaces it
+// only on a strict compare, so a NaN there is the result; NaNs in later positions never win (np_hip.h, np_reduce_op).
+template <int OP>
+__device__ __forceinline__ float r_first_nan(float r, const float *first) {
+    if constexpr (OP == NP_MIN || OP == NP_MAX) {
+        if (first) {
+            const float f = *first;
+            if (f != f) r = f;
+        }
+    }
+    return r;
 }
 
 template <int OP>
@@ -215,11 +231,11 @@ __device__ __forceinline__ float block_reduce(float v, float *lds4) {
 // The end of a streaming first pass: `r` is this workgroup's partial (valid in thread 0).  With a ticket, the last
 // workgroup to finish folds all gridDim.x partials — thread t takes partials t, t + blockDim, ... and block_reduce joins
 // them, the order the separate one-workgroup kernel uses, whichever workgroup happens to be last — and writes out[0]
-// (divided by mean_count for NP_MEAN).  Without one (ticket == nullptr) the partial is just stored for that kernel.
+// (divided by mean_count for NP_MEAN; `first`: r_first_nan).  Without one (ticket == nullptr) the partial is just stored for that kernel.
 // All threads of every workgroup call it.
 template <int OP>
 __device__ __forceinline__ void fold_in_last_workgroup(float r, float *partials, unsigned *ticket, float *out,
-                                                       float mean_count, float *lds4) {
+                                                       float mean_count, float *lds4, const float *first = nullptr) {
     if (!ticket) {
         if (threadIdx.x == 0) partials[blockIdx.x] = r;
         return;
@@ -227,7 +243,7 @@ __device__ __forceinline__ void fold_in_last_workgroup(float r, float *partials,
     if (gridDim.x == 1) {
         if (threadIdx.x == 0) {
             if constexpr (OP == NP_MEAN) r = __fdiv_rn(r, mean_count);
-            out[0] = r;
+            out[0] = r_first_nan<OP>(r, first);
         }
         return;
     }
@@ -236,7 +252,7 @@ __device__ __forceinline__ void fold_in_last_workgroup(float r, float *partials,
     // thread t folds partials t, t + blockDim, ... in that order (the order of the one-workgroup second kernel).  The loads
     // are memory-side atomics, a microsecond or two each: eight are issued before the first is used (lanes past the end load
     // nothing and fold the identity, which changes no bit: x + 0, x * 1, min(x, +inf), max(x, -inf))
-    float f = r_identity<OP>();
+    float f = r_identity<OP>(), p0 = 0.0f;
     for (unsigned base = 0; base < gridDim.x; base += 8 * blockDim.x) {
         float v[8];
 #pragma unroll
@@ -244,13 +260,16 @@ __device__ __forceinline__ void fold_in_last_workgroup(float r, float *partials,
             const unsigned i = base + u * blockDim.x + threadIdx.x;
             v[u] = i < gridDim.x ? coherent_load(&partials[i]) : r_identity<OP>();
         }
+        if (base == 0) p0 = v[0];   // thread 0: partial 0
 #pragma unroll
         for (int u = 0; u < 8; ++u) f = r_combine<OP>(f, v[u]);
     }
     f = block_reduce<OP>(f, lds4);
     if (threadIdx.x == 0) {
         if constexpr (OP == NP_MEAN) f = __fdiv_rn(f, mean_count);
-        out[0] = f;
+        // MIN / MAX: a first pass that evaluates its elements itself (the chain kernels) hands the NaN of position 0 over as
+        // partial 0 — workgroup 0 owns position 0, and no other partial is ever NaN; np_reduce.hip's passes give `first`
+        out[0] = r_first_nan<OP>(r_first_nan<OP>(f, first), &p0);
         coherent_store(ticket, 0u);   // clean for the launch that draws this slot next
     }
 }

@@ -33,6 +33,9 @@ int g_small_inner_dword = 0;    // reduce_small_inner: 1 = the dword walk of rou
 int g_arg_xcd_runs_off = 0;     // argreduce_cols_tile on unaligned rows: 1 = the plain workgroup order (np_reduce_set_variant(4200001): A/B)
 int g_arg_cols_wg_per_cu = 0;   // argreduce_cols_tile: workgroups per CU the axis is cut for; 0 = by alignment (np_reduce_set_variant(4000000 + N): A/B)
 constexpr int kStreamWgPerCu = 8;
+// np_debug_reduce_last_path: the NP_REDUCE_PATH_* bits of what the last np_reduce_axis / np_reduce_all(_dev) call launched, its
+// recursion on partials included.  A plain process global, cleared at the top of those entry points.
+unsigned g_last_path = 0;
 inline size_t stream_cap() {
     if (g_wg_per_cu >= 1000) return (size_t)g_wg_per_cu;   // tuning: an exact workgroup count
     return (size_t)np::num_cus() * (size_t)(g_wg_per_cu > 0 ? g_wg_per_cu : kStreamWgPerCu);
@@ -98,19 +101,21 @@ __global__ __launch_bounds__(256) void reduce_all_pass1(const float *__restrict_
         if (t < n) r = r_combine<OP>(r, in[t]);
     }
     r = block_reduce<OP>(r, lds4);
-    fold_in_last_workgroup<OP>(r, partials, ticket, out, mean_count, lds4);   // ticket == nullptr: pass 2 folds
+    fold_in_last_workgroup<OP>(r, partials, ticket, out, mean_count, lds4, n ? in : nullptr);   // ticket == nullptr: pass 2 folds
 }
 
 // pass 2: one workgroup folds the partials; MEAN divides by the element count at the end
-// (`value / numElements`, arithmetics.c:89, numpower.c:2659).
+// (`value / numElements`, arithmetics.c:89, numpower.c:2659).  `first`: position 0 of the input the partials came from, for
+// the NaN rule of NP_MIN / NP_MAX (r_first_nan); nullptr when the caller has none.
 template <int OP>
 __global__ __launch_bounds__(256) void reduce_all_pass2(const float *__restrict__ partials, int np,
-                                                        float *__restrict__ out, float count) {
+                                                        float *__restrict__ out, float count,
+                                                        const float *__restrict__ first = nullptr) {
     __shared__ float lds4[4];
     // thread t folds partials t, t + 256, ... in that order; eight loads are in flight before the first is used (one load -> add
     // round trip per iteration was ~6 us for the 2049 partials of a 10^8-element reduction); lanes past the end fold the identity,
     // which changes no bit (x + 0, x * 1, min(x, +inf), max(x, -inf))
-    float r = r_identity<OP>();
+    float r = r_identity<OP>(), p0 = 0.0f;
     for (int base = 0; base < np; base += 8 * (int)blockDim.x) {
         float v[8];
 #pragma unroll
@@ -118,13 +123,15 @@ __global__ __launch_bounds__(256) void reduce_all_pass2(const float *__restrict_
             const int i = base + u * (int)blockDim.x + (int)threadIdx.x;
             v[u] = i < np ? partials[i] : r_identity<OP>();
         }
+        if (base == 0) p0 = v[0];   // thread 0: partial 0
 #pragma unroll
         for (int u = 0; u < 8; ++u) r = r_combine<OP>(r, v[u]);
     }
     r = block_reduce<OP>(r, lds4);
     if (threadIdx.x == 0) {
         if constexpr (OP == NP_MEAN) r = __fdiv_rn(r, count);
-        out[0] = r;
+        // (a NaN partial 0: the chain kernels' way of handing over the NaN of position 0, fold_in_last_workgroup)
+        out[0] = r_first_nan<OP>(r_first_nan<OP>(r, first), &p0);
     }
 }
 
@@ -879,14 +886,16 @@ __global__ __launch_bounds__(256) void all_pass1(const float *__restrict__ in,
 // keep ROWS_IN_FLIGHT independent loads in flight, and combine through LDS at the end.
 // out_partial[outer][splits][inner]; with splits == 1 this is the final result.
 //
-// FINAL applies the epilogue: MEAN -> divide by axis_len; PROD with the AVX-body quirk ->
+// FINAL applies the epilogue: MIN / MAX -> the NaN rule of position 0 (first / first_axis: the array the caller was given and
+// its axis length; r_first_nan); MEAN -> divide by axis_len; PROD with the AVX-body quirk ->
 // zero results take the sign the reference's repeated Multiply_Float leaves behind
 // (arithmetics.c:403,410-412): -0.0f for inner index < body_end, +0.0f after it.
 template <int OP, bool FINAL, typename I>
 __global__ __launch_bounds__(256) void reduce_axis_cols(const float *__restrict__ in,
                                                         float *__restrict__ out, I axis_len,
                                                         I inner, I splits, float mean_div,
-                                                        int prod_quirk, I body_end, unsigned xcd_runs = 0) {
+                                                        int prod_quirk, I body_end, unsigned xcd_runs = 0,
+                                                        const float *__restrict__ first = nullptr, I first_axis = 0) {
     __shared__ v4f lds[3][64];
     const I inner4 = (inner + 3) / 4;   // column groups per row; the last one may hold fewer than 4 columns
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -971,6 +980,14 @@ __global__ __launch_bounds__(256) void reduce_axis_cols(const float *__restrict_
                         if (acc[k] == 0.0f) acc[k] = (col4 * 4 + k < body_end) ? -0.0f : 0.0f;
                 }
             }
+            if constexpr (OP == NP_MIN || OP == NP_MAX) {
+                if (first) {   // position 0 of each column's slice in the ORIGINAL array (this launch may fold partials)
+                    const float *f0 = first + (size_t)o * first_axis * (size_t)inner + (size_t)col4 * 4;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if ((I)k < valid) acc[k] = r_first_nan<OP>(acc[k], f0 + k);
+                }
+            }
         }
         float *q = out + ((size_t)o * splits + split) * (size_t)inner + (size_t)col4 * 4;
         if (valid == 4) {
@@ -995,7 +1012,8 @@ __global__ __launch_bounds__(256) void reduce_axis_generic(const float *__restri
                                                            float *__restrict__ out, I outer,
                                                            I axis_len, I inner, float mean_div,
                                                            int prod_quirk, I body_end, I chunks,
-                                                           I chunk_len) {
+                                                           I chunk_len, const float *__restrict__ first = nullptr,
+                                                           I first_axis = 0) {
     const I total = outer * chunks * inner;
     const I stride = (I)gridDim.x * blockDim.x;
     for (I idx = (I)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
@@ -1025,6 +1043,7 @@ __global__ __launch_bounds__(256) void reduce_axis_generic(const float *__restri
             if constexpr (OP == NP_PROD) {
                 if (prod_quirk && r == 0.0f) r = (j < body_end) ? -0.0f : 0.0f;
             }
+            r = r_first_nan<OP>(r, first ? first + (size_t)o * first_axis * inner + j : nullptr);
         }
         out[idx] = r;
     }
@@ -1143,7 +1162,8 @@ __global__ __launch_bounds__(256) void reduce_small_inner_v4(const float *__rest
 template <int OP, typename I>
 __global__ __launch_bounds__(256) void reduce_rows_wave(const float *__restrict__ in,
                                                         float *__restrict__ out, I rows, I len,
-                                                        float mean_div, int prod_quirk) {
+                                                        float mean_div, int prod_quirk,
+                                                        const float *__restrict__ first = nullptr, I first_axis = 0) {
     const int lane = threadIdx.x & 63;
     const I row = (I)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
@@ -1172,7 +1192,7 @@ __global__ __launch_bounds__(256) void reduce_rows_wave(const float *__restrict_
         if constexpr (OP == NP_PROD) {
             if (prod_quirk && r == 0.0f) r = 0.0f;
         }
-        out[row] = r;
+        out[row] = r_first_nan<OP>(r, first ? first + (size_t)row * first_axis : nullptr);
     }
 }
 
@@ -1182,7 +1202,8 @@ __global__ __launch_bounds__(256) void reduce_rows_wave(const float *__restrict_
 // neighbouring groups read neighbouring rows) and fold with xor-shuffles.
 template <int OP, int L, typename I>
 __global__ __launch_bounds__(256) void reduce_rows_group(const float *__restrict__ in, float *__restrict__ out,
-                                                         I rows, I len, float mean_div, int prod_quirk) {
+                                                         I rows, I len, float mean_div, int prod_quirk,
+                                                         const float *__restrict__ first = nullptr, I first_axis = 0) {
     const I row = ((I)blockIdx.x * 256 + threadIdx.x) / L;
     const unsigned l = threadIdx.x % L;
     float r = r_identity<OP>();
@@ -1204,7 +1225,7 @@ __global__ __launch_bounds__(256) void reduce_rows_group(const float *__restrict
         if constexpr (OP == NP_PROD) {
             if (prod_quirk && r == 0.0f) r = 0.0f;   // see reduce_rows_wave
         }
-        out[row] = r;
+        out[row] = r_first_nan<OP>(r, first ? first + (size_t)row * first_axis : nullptr);
     }
 }
 
@@ -1217,7 +1238,8 @@ __global__ __launch_bounds__(256) void reduce_rows_group(const float *__restrict
 template <int OP>
 __global__ __launch_bounds__(256) void reduce_rows_staged(const float *__restrict__ in, float *__restrict__ out,
                                                           size_t rows_total, unsigned len, unsigned R, unsigned magic,
-                                                          float mean_div, int prod_quirk) {
+                                                          float mean_div, int prod_quirk,
+                                                          const float *__restrict__ first = nullptr, size_t first_axis = 0) {
     extern __shared__ __attribute__((aligned(16))) float slab[];
     const unsigned pitch = len | 1u;
     const size_t row0 = (size_t)blockIdx.x * R;
@@ -1255,7 +1277,7 @@ __global__ __launch_bounds__(256) void reduce_rows_staged(const float *__restric
         if constexpr (OP == NP_PROD) {
             if (prod_quirk && v == 0.0f) v = 0.0f;   // see reduce_rows_wave
         }
-        out[row0 + r] = v;
+        out[row0 + r] = r_first_nan<OP>(v, first ? first + (row0 + r) * first_axis : nullptr);
     }
 }
 
@@ -1264,7 +1286,8 @@ __global__ __launch_bounds__(256) void reduce_rows_staged(const float *__restric
 template <int OP, typename I>
 __global__ __launch_bounds__(256) void reduce_rows_block(const float *__restrict__ in,
                                                          float *__restrict__ out, I rows, I row_len,
-                                                         float mean_div, I chunk_len, int prod_quirk) {
+                                                         float mean_div, I chunk_len, int prod_quirk,
+                                                         const float *__restrict__ first = nullptr, I first_axis = 0) {
     __shared__ float lds4[4];
     const I row = blockIdx.x, chunk = blockIdx.y;
     const I c0 = chunk * chunk_len;
@@ -1302,7 +1325,7 @@ __global__ __launch_bounds__(256) void reduce_rows_block(const float *__restrict
         if constexpr (OP == NP_PROD) {
             if (prod_quirk && r == 0.0f) r = 0.0f;   // see reduce_rows_wave
         }
-        out[(size_t)row * gridDim.y + chunk] = r;
+        out[(size_t)row * gridDim.y + chunk] = r_first_nan<OP>(r, first ? first + (size_t)row * first_axis : nullptr);   // (chunked launches pass none)
     }
 }
 
@@ -1330,9 +1353,10 @@ int launch_reduce_all(const float *in, size_t n, float *dev_out) {
     reduce_all_pass1<OP, I><<<(unsigned)blocks, 256, 0, s>>>(in, (float *)partials.ptr, (I)n, (I)head, (I)nvec,
                                                            ticket, dev_out, (float)n);
     NP_LAUNCH_CHECK("reduce_all_pass1");
+    g_last_path |= ticket ? NP_REDUCE_PATH_ALL_ONE_LAUNCH : NP_REDUCE_PATH_ALL_TWO_LAUNCHES;
     if (ticket) return NP_OK;
     reduce_all_pass2<OP><<<1, 256, 0, s>>>((const float *)partials.ptr, (int)blocks, dev_out,
-                                           (float)n);
+                                           (float)n, n ? in : nullptr);
     NP_LAUNCH_CHECK("reduce_all_pass2");
     return NP_OK;
 }
@@ -1388,11 +1412,14 @@ size_t choose_splits(size_t outer, size_t axis_len, size_t inner4) {
 }
 
 // mean_div_override != 0: this call folds the partials of an earlier pass — MEAN divides by the
-// original axis length, not by the number of partials.
+// original axis length, not by the number of partials, and the NaN rule of MIN / MAX looks at position 0 of the ORIGINAL
+// array's slices (first0, an array of outer x first_axis0 x inner), which the kernel that writes `out` is handed.
 template <int OP, typename I>
 int launch_reduce_axis(const float *in, size_t outer, size_t axis_len, size_t inner, float *out,
-                       unsigned flags, float mean_div_override = 0.0f) {
+                       unsigned flags, float mean_div_override = 0.0f, const float *first0 = nullptr, size_t first_axis0 = 0) {
     hipStream_t s = np::stream();
+    const float *first = first0 ? first0 : in;
+    const size_t first_axis = first0 ? first_axis0 : axis_len;
     const float mean_div = mean_div_override != 0.0f ? mean_div_override
                                                       : (float)(long)axis_len;   // CreateFromLongScalar, numpower.c:2666
     const int quirk = (OP == NP_PROD && (flags & NP_QUIRK_AVX_BODY) && axis_len > 1) ? 1 : 0;
@@ -1417,8 +1444,9 @@ int launch_reduce_axis(const float *in, size_t outer, size_t axis_len, size_t in
             }
             if (chunks == 1) {
                 reduce_rows_block<OP, I><<<(unsigned)outer, 256, 0, s>>>(in, out, (I)outer, (I)axis_len,
-                                                                      mean_div, (I)axis_len, quirk);
+                                                                      mean_div, (I)axis_len, quirk, first, (I)first_axis);
                 NP_LAUNCH_CHECK("reduce_rows_block");
+                g_last_path |= NP_REDUCE_PATH_ROWS_BLOCK;
                 return NP_OK;
             }
             const size_t chunk_len = ((axis_len + chunks - 1) / chunks + 3) / 4 * 4;
@@ -1428,7 +1456,8 @@ int launch_reduce_axis(const float *in, size_t outer, size_t axis_len, size_t in
             reduce_rows_block<P1, I><<<dim3((unsigned)outer, (unsigned)chunks), 256, 0, s>>>(
                 in, (float *)partials.ptr, (I)outer, (I)axis_len, 1.0f, (I)chunk_len, 0);
             NP_LAUNCH_CHECK("reduce_rows_block(chunks)");
-            return launch_reduce_axis<OP, I>((const float *)partials.ptr, outer, chunks, 1, out, flags, mean_div);
+            g_last_path |= NP_REDUCE_PATH_ROWS_BLOCK_CHUNKED;
+            return launch_reduce_axis<OP, I>((const float *)partials.ptr, outer, chunks, 1, out, flags, mean_div, first, first_axis);
         }
         if (axis_len > 4 && axis_len <= 48 && outer * axis_len >= (size_t(8) << 20) && ((uintptr_t)in & 15u) == 0) {
             // slabs of R rows (a multiple of 256) staged through ~32 KB of LDS: 10^7 x 10 4.5 -> 5.95 TB/s, 5 * 10^6 x 16
@@ -1442,8 +1471,9 @@ int launch_reduce_axis(const float *in, size_t outer, size_t axis_len, size_t in
             if (blocks <= 0x7fffffffu && lds <= 64 * 1024) {
                 const unsigned magic = (unsigned)((0x100000000ull + axis_len - 1) / axis_len);
                 reduce_rows_staged<OP><<<(unsigned)blocks, 256, lds, s>>>(in, out, outer, (unsigned)axis_len, R, magic,
-                                                                       mean_div, quirk);
+                                                                       mean_div, quirk, first, first_axis);
                 NP_LAUNCH_CHECK("reduce_rows_staged");
+                g_last_path |= NP_REDUCE_PATH_ROWS_STAGED;
                 return NP_OK;
             }
         }
@@ -1455,7 +1485,7 @@ int launch_reduce_axis(const float *in, size_t outer, size_t axis_len, size_t in
             const size_t blocks = (outer + rows_per_block - 1) / rows_per_block;
             if (blocks > 0x7fffffffu)
                 return np::fail(NP_ERR_INVALID, "np_reduce_axis: too many rows for row reduce");
-#define NP_RG(L_) reduce_rows_group<OP, L_, I><<<(unsigned)blocks, 256, 0, s>>>(in, out, (I)outer, (I)axis_len, mean_div, quirk)
+#define NP_RG(L_) reduce_rows_group<OP, L_, I><<<(unsigned)blocks, 256, 0, s>>>(in, out, (I)outer, (I)axis_len, mean_div, quirk, first, (I)first_axis)
             switch (L) {
                 case 2: NP_RG(2); break;
                 case 4: NP_RG(4); break;
@@ -1465,6 +1495,7 @@ int launch_reduce_axis(const float *in, size_t outer, size_t axis_len, size_t in
             }
 #undef NP_RG
             NP_LAUNCH_CHECK("reduce_rows_group");
+            g_last_path |= NP_REDUCE_PATH_ROWS_GROUP;
             return NP_OK;
         }
         if (axis_len >= 32) {
@@ -1472,8 +1503,9 @@ int launch_reduce_axis(const float *in, size_t outer, size_t axis_len, size_t in
             if (blocks > 0x7fffffffu)
                 return np::fail(NP_ERR_INVALID, "np_reduce_axis: too many rows for row reduce");
             reduce_rows_wave<OP, I><<<(unsigned)blocks, 256, 0, s>>>(in, out, (I)outer, (I)axis_len,
-                                                                  mean_div, quirk);
+                                                                  mean_div, quirk, first, (I)first_axis);
             NP_LAUNCH_CHECK("reduce_rows_wave");
+            g_last_path |= NP_REDUCE_PATH_ROWS_WAVE;
             return NP_OK;
         }
     } else if ((inner % 4 == 0 || inner >= 4000) && outer <= 65535 &&
@@ -1489,10 +1521,12 @@ int launch_reduce_axis(const float *in, size_t outer, size_t axis_len, size_t in
         // tiles that straddle 128-byte lines: neighbours on one XCD (np_reduce_set_variant(4200001): the launch order, A/B)
         const unsigned xcd_runs = ((inner * sizeof(float)) % 128 != 0 || ((uintptr_t)in & 127u) != 0) && grid.x > 1 &&
                                   (size_t)grid.x * grid.y * grid.z < (size_t(1) << 31) && !g_arg_xcd_runs_off ? 1u : 0u;
+        if (xcd_runs) g_last_path |= NP_REDUCE_PATH_COLS_XCD_RUNS;
         if (splits == 1) {
             reduce_axis_cols<OP, true, I><<<grid, 256, 0, s>>>(in, out, (I)axis_len, (I)inner, (I)1,
-                                                            mean_div, quirk, (I)body_end, xcd_runs);
+                                                            mean_div, quirk, (I)body_end, xcd_runs, first, (I)first_axis);
             NP_LAUNCH_CHECK("reduce_axis_cols");
+            g_last_path |= NP_REDUCE_PATH_COLS_ONE_PASS;
             return NP_OK;
         }
         np::Scratch partials;
@@ -1504,14 +1538,17 @@ int launch_reduce_axis(const float *in, size_t outer, size_t axis_len, size_t in
         // fold them with one workgroup per tile, four rows in flight per wave — 192 dependent iterations, as long as the first
         // pass itself (134 us where the read takes 67).  The partials are again a tall skinny array: reduce THEM in chunks first
         // (one more 4 us launch).  From 256 chunks up; BASELINE config 4 (192 chunks over 16 tiles, a 5 us fold) is not touched.
-        if (splits >= 256)
-            return launch_reduce_axis<OP, I>((const float *)partials.ptr, outer, splits, inner, out, flags, mean_div);
+        if (splits >= 256) {
+            g_last_path |= NP_REDUCE_PATH_COLS_SPLITS_RECURSE;
+            return launch_reduce_axis<OP, I>((const float *)partials.ptr, outer, splits, inner, out, flags, mean_div, first, first_axis);
+        }
+        g_last_path |= NP_REDUCE_PATH_COLS_TWO_PASSES;
         // pass 2: the partials are an outer x splits x inner array; MEAN must divide by the real
         // axis length, not by `splits`.
         const dim3 grid2((unsigned)((inner4 + 63) / 64), 1, (unsigned)outer);
         reduce_axis_cols<OP, true, I><<<grid2, 256, 0, s>>>((const float *)partials.ptr, out,
                                                          (I)splits, (I)inner, (I)1, mean_div,
-                                                         quirk, (I)body_end);
+                                                         quirk, (I)body_end, 0u, first, (I)first_axis);
         NP_LAUNCH_CHECK("reduce_axis_cols(pass 2)");
         return NP_OK;
     } else if (inner <= 128 && axis_len >= 512 && outer <= 65535 && outer * inner < target_wg * 64) {
@@ -1534,7 +1571,8 @@ int launch_reduce_axis(const float *in, size_t outer, size_t axis_len, size_t in
             reduce_small_inner<P1, I><<<dim3((unsigned)blocks, (unsigned)outer), 256, 0, s>>>(
                 in, (float *)partials.ptr, (I)axis_len, (I)inner, (I)rows_per_block);
         NP_LAUNCH_CHECK("reduce_small_inner");
-        return launch_reduce_axis<OP, I>((const float *)partials.ptr, outer, blocks, inner, out, flags, mean_div);
+        g_last_path |= v4 ? NP_REDUCE_PATH_SMALL_INNER_V4 : NP_REDUCE_PATH_SMALL_INNER;
+        return launch_reduce_axis<OP, I>((const float *)partials.ptr, outer, blocks, inner, out, flags, mean_div, first, first_axis);
     }
     // generic fallback (ragged inner, misaligned views, tiny problems): one thread per output and
     // axis chunk; chunk the axis when the outputs alone cannot fill the machine
@@ -1558,8 +1596,9 @@ int launch_reduce_axis(const float *in, size_t outer, size_t axis_len, size_t in
     if (chunks == 1) {
         reduce_axis_generic<OP, I><<<(unsigned)blocks, 256, 0, s>>>(in, out, (I)outer, (I)axis_len,
                                                                  (I)inner, mean_div, quirk,
-                                                                 (I)body_end, (I)1, (I)axis_len);
+                                                                 (I)body_end, (I)1, (I)axis_len, first, (I)first_axis);
         NP_LAUNCH_CHECK("reduce_axis_generic");
+        g_last_path |= NP_REDUCE_PATH_GENERIC;
         return NP_OK;
     }
     np::Scratch partials;
@@ -1568,7 +1607,8 @@ int launch_reduce_axis(const float *in, size_t outer, size_t axis_len, size_t in
                                                              (I)axis_len, (I)inner, 1.0f, 0, (I)0,
                                                              (I)chunks, (I)chunk_len);
     NP_LAUNCH_CHECK("reduce_axis_generic(chunks)");
-    return launch_reduce_axis<OP, I>((const float *)partials.ptr, outer, chunks, inner, out, flags, mean_div);
+    g_last_path |= NP_REDUCE_PATH_GENERIC_CHUNKED;
+    return launch_reduce_axis<OP, I>((const float *)partials.ptr, outer, chunks, inner, out, flags, mean_div, first, first_axis);
 }
 
 template <int OP>
@@ -1590,6 +1630,7 @@ int np_reduce_all_dev(int op, const float *in, size_t n, float *dev_out) {
     if (!dev_out) return np::fail(NP_ERR_INVALID, "np_reduce_all: null output");
     if (n > 0 && !in) return np::fail(NP_ERR_INVALID, "np_reduce_all: null input");
     if (int rc = np::ensure_init()) return rc;
+    g_last_path = 0;
     switch (op) {
         case NP_SUM: return dispatch_reduce_all<NP_SUM>(in, n, dev_out);
         case NP_PROD: return dispatch_reduce_all<NP_PROD>(in, n, dev_out);
@@ -2408,6 +2449,7 @@ int np_reduce_axis(int op, const float *in, size_t outer, size_t axis_len, size_
     if (axis_len == 0) return np::fail(NP_ERR_INVALID, "np_reduce_axis: empty axis");
     if (!in || !out) return np::fail(NP_ERR_INVALID, "np_reduce_axis: null pointer");
     if (int rc = np::ensure_init()) return rc;
+    g_last_path = 0;
     switch (op) {
         case NP_SUM: return dispatch_reduce_axis<NP_SUM>(in, outer, axis_len, inner, out, flags);
         case NP_PROD: return dispatch_reduce_axis<NP_PROD>(in, outer, axis_len, inner, out, flags);
@@ -2415,6 +2457,12 @@ int np_reduce_axis(int op, const float *in, size_t outer, size_t axis_len, size_
         case NP_MAX: return dispatch_reduce_axis<NP_MAX>(in, outer, axis_len, inner, out, flags);
         default: return dispatch_reduce_axis<NP_MEAN>(in, outer, axis_len, inner, out, flags);
     }
+}
+
+int np_debug_reduce_last_path(unsigned *host_mask) {
+    if (!host_mask) return np::fail(NP_ERR_INVALID, "np_debug_reduce_last_path: null pointer");
+    *host_mask = g_last_path;
+    return NP_OK;
 }
 
 }  // extern "C"

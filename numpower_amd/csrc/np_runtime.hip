@@ -502,6 +502,13 @@ int np_debug_set_cus(int cus) {
     return NP_OK;
 }
 
+int np_debug_cus(int *host_cus) {
+    if (!host_cus) return np::fail(NP_ERR_INVALID, "np_debug_cus: null pointer");
+    if (int rc = np::ensure_init()) return rc;
+    *host_cus = np::num_cus();
+    return NP_OK;
+}
+
 int np_debug_hw_ids(unsigned *host_out2, size_t workgroups) {
     if (!host_out2 || workgroups == 0 || workgroups > 65536) return np::fail(NP_ERR_INVALID, "np_debug_hw_ids: bad arguments");
     if (int rc = np::ensure_init()) return rc;
