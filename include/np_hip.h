@@ -76,7 +76,11 @@ const char *np_version(void);
 
 /* Stream plumbing: the library launches on one stream.  By default it owns a non-blocking
  * stream; a caller that already has one (e.g. torch's current stream, passed as the raw
- * hipStream_t) can hand it in.  Pass NULL to go back to the library-owned stream. */
+ * hipStream_t) can hand it in.  Pass NULL to go back to the library-owned stream.
+ * np_get_stream() returns a handle that is ordered behind every library call made BEFORE it.  While the library owns the stream,
+ * large np_sgemm calls may run on a side stream of the library's (np_sgemm_overlap_stats below), and the handle is ordered behind
+ * those only as of the moment it was fetched: a caller that enqueues its own work on it behind LATER library calls fetches it
+ * again after those calls (or installs its own stream with np_set_stream, which turns the side stream off). */
 int np_set_stream(void *hip_stream);
 void *np_get_stream(void);
 
@@ -359,6 +363,15 @@ int np_sgemm_strided_batched(size_t batch, size_t M, size_t N, size_t K,
 int np_sgemm_strided_batched_piece(size_t count, size_t whole, size_t M, size_t N, size_t K,
                                    const float *A, size_t stride_a, const float *B, size_t stride_b,
                                    float *C, size_t stride_c);
+/* Consecutive large np_sgemm calls (one launch of the LDS-DMA kernel each, from 4e9 flop) that do not touch each other's operands
+ * run alternately on the library stream and on a side stream the library owns, so that one launch's workgroups start while
+ * the previous launch is still storing C.  Every other entry point first orders the library stream behind the side stream — as
+ * does np_get_stream, at the moment it is called (see there for a handle that is kept) — and products that share bytes (C of one is an operand or
+ * the C of the next, or the other way round) are never reordered.  Off under a caller's stream (np_set_stream) and inside
+ * np_graph_begin .. np_graph_end; NP_SGEMM_OVERLAP=0 in the environment turns it off when the library is loaded.
+ * out[0]: launches that went to the side stream, out[1]: launches on the library stream next to one on the side stream,
+ * out[2]: launches of that size ordered behind everything (the first of a run, a shared operand, other work in between). */
+int np_sgemm_overlap_stats(unsigned long long out[3]);
 /* y[M] = A[MxN] . x[N]; replaces cblas_sgemv / matrixVectorMultiplyFloatKernel
  * (linalg.c:367-386, cuda_math.cu:228,1417). */
 int np_sgemv(size_t M, size_t N, const float *A, const float *x, float *y);

@@ -72,7 +72,9 @@ int np_comm_debug_loopback(void *dev_scratch, size_t bytes);
  * -24 = that plan wherever one exists, -25 / -26 = its launch tile-major / chunk-major over the XCDs, -(30000 + 1000 * shape + S)
  * forces single products of K >= 512 onto S K-chunks of k-quartered tile `shape` (-30000: off), -(40 + q), q = 0 .. 59: a thin
  * K-chunk launch (17 .. 2047 rows, N <= 64, K >= 16384) of fewer than q / 4 workgroups per CU goes to the planner instead
- * (0 = never, as before round 5; default 59).  All of them are process-wide setters for A/B measurements and tests: results stay within the same bounds. */
+ * (0 = never, as before round 5; default 59); -27 / -28 = consecutive independent large products on the library stream alone /
+ * alternating with the side stream (np_sgemm_overlap_stats, np_hip.h; default), -29 = products of any size qualify for that
+ * (tests), -30 = from 4e9 flop again.  All of them are process-wide setters for A/B measurements and tests: results stay within the same bounds. */
 int np_runtime_set_variant(int variant);   /* how host-result calls wait: 0 = hipStreamSynchronize, 1 = spin on a stream-written flag, 2 = spin on the result itself (default) */
 int np_sgemm_set_variant(int variant);
 /* debug: the planner's choice for one dense, aligned M x N x K product on a device of `cus` CUs (0 = the current device; any

@@ -9,13 +9,40 @@
 
 #include "np_hip.h"
 #include "np_hip_debug.h"
+#include "np_sgemm_lane.h"
 
 namespace np {
 
 // Records msg as the calling thread's last error and returns code.
 int fail(int code, const char *fmt, ...);
-// Library stream (never the null stream unless the caller installed it).
+// Library stream (never the null stream unless the caller installed it).  JOINS first: if the side lane (below) holds work
+// the stream has not been ordered behind yet, the stream is made to wait for it (a device-side wait; the host does not
+// block), so whatever the caller enqueues sees every product the library was given before.
 hipStream_t stream();
+// The same stream without the join: for the one launch that is meant to run next to the lane's work (LaneLaunch) and nothing else.
+hipStream_t stream_nojoin();
+// The side lane: one extra stream per device on which every other large independent np_sgemm launch runs, so that its
+// workgroups fill the CUs while the launch before it is still draining C (np_sgemm_lane.h has the protocol and the decision;
+// np_runtime.hip the streams and events).  begin() picks the stream for a GEMM that touches `cur`'s ranges and does `flop`
+// work, and enqueues what orders it; the object holds the lane until it dies, when it records the lane's event if the launch
+// went there.  Never visible outside np_sgemm: whoever fetches np::stream() is behind the lane.
+// The object holds a non-recursive mutex that np::stream() takes as well: while one is alive, launch on its `stream` and do NOT
+// call np::stream() (NP_LAUNCH_CHECK does not).
+struct LaneLaunch {
+    hipStream_t stream = nullptr;
+    int begin(const lane::Gemm &cur, double flop);
+    ~LaneLaunch();
+    LaneLaunch() = default;
+    LaneLaunch(const LaneLaunch &) = delete;
+    LaneLaunch &operator=(const LaneLaunch &) = delete;
+
+  private:
+    void *dev_ = nullptr;
+    bool side_ = false;
+};
+// np_sgemm_set_variant(-27 .. -30): 0 = overlap off, 1 = on (default), 2 = every launch qualifies by size (tests), 3 = the default size again
+void lane_set_knob(int what);
+void lane_stats(unsigned long long out[3]);
 // Makes sure np_init ran (lazily initialises device 0).
 int ensure_init();
 // Device properties cached at init.

@@ -8,11 +8,15 @@
 //   * allocations come from a caching pool, so the one-result-buffer-per-op pattern of the
 //     reference's L2 (arithmetics.c:211-231) costs a free-list pop instead of hipMalloc;
 //   * everything is ordered on one library stream and asynchronous; the only blocking calls
-//     are np_sync, np_memcpy_d2h, np_read_float and the timers.
+//     are np_sync, np_memcpy_d2h, np_read_float and the timers.  (One exception nobody can see: every
+//     other large independent np_sgemm launch runs on a side lane, and np::stream() orders the library
+//     stream behind it before anything else is enqueued — "the side lane" below.)
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <chrono>
 #include <map>
 #include <mutex>
@@ -41,6 +45,18 @@ struct DeviceState {
     unsigned *tickets = nullptr;                         // ring of zeroed device counters (np::next_ticket)
     unsigned ticket_seq = 0;
     unsigned *streamk_flags = nullptr;                   // np_sgemm.hip's stream-K flags (np::streamk_flags), zero between launches
+    // The side lane of the large independent GEMMs (np_internal.h LaneLaunch, np_sgemm_lane.h).  The stream and the three
+    // events, which time nothing, are created on first use and live as long as own_stream (the life of the process).
+    // cur_stream is read by joined_locked() and stream_nojoin() only: everything else takes it through the join.
+    std::mutex lane_mu;                                  // everything below, and the order of what goes to the two streams
+    hipStream_t lane = nullptr;
+    hipEvent_t lane_done = nullptr;                      // recorded on the lane behind its latest GEMM
+    hipEvent_t main_mark = nullptr;                      // recorded on cur_stream in front of the latest GEMM launched there
+    hipEvent_t lane_mark = nullptr;                      // recorded on the lane in front of its latest GEMM
+    bool lane_pending = false;                           // the lane holds work cur_stream has not been made to wait for
+    unsigned long long main_seq = 0;                     // how often cur_stream has been handed out (joined_locked)
+    np::lane::Gemm prev = {};                            // the latest GEMM that passed the gate ...
+    bool prev_valid = false, prev_on_side = false;       // ... if any, and where it went
 };
 
 struct Runtime {
@@ -67,6 +83,58 @@ struct Runtime {
 Runtime &rt() {
     static Runtime r;
     return r;
+}
+
+// ---- the side lane ----
+constexpr double kLaneMinFlop = 4e9;   // the size from which np_sgemm.hip's dma_takes hands any single product to the LDS-DMA kernel
+// process-wide, read and written from any thread and under any device's lane_mu: atomics
+std::atomic<bool> g_lane_on{[] {
+    const char *e = getenv("NP_SGEMM_OVERLAP");   // NP_SGEMM_OVERLAP=0: off from load (np_sgemm_set_variant(-27) at any time)
+    return !(e && e[0] == '0' && e[1] == 0);
+}()};
+std::atomic<double> g_lane_min_flop{kLaneMinFlop};
+std::atomic<unsigned long long> g_lane_stats[3];   // launches to the lane, to main next to the lane, to main joined (gate passed)
+
+// The join: d.cur_stream, ordered behind whatever the lane holds.  Caller holds d.lane_mu.
+hipStream_t joined_locked(DeviceState &d) {
+    if (d.lane_pending) {
+        // a device-side wait; should the runtime refuse it, the host waits for the lane instead: slower, never wrong
+        if (hipStreamWaitEvent(d.cur_stream, d.lane_done, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(d.lane);
+        }
+        d.lane_pending = false;
+    }
+    ++d.main_seq;
+    return d.cur_stream;
+}
+
+hipStream_t joined(DeviceState &d) {
+    std::lock_guard<std::mutex> lk(d.lane_mu);
+    return joined_locked(d);
+}
+
+int lane_create_locked(DeviceState &d) {
+    if (d.lane) return NP_OK;
+    hipStream_t s = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&e0, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&e1, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&e2, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (e2) (void)hipEventDestroy(e2);
+        if (e1) (void)hipEventDestroy(e1);
+        if (e0) (void)hipEventDestroy(e0);
+        if (s) (void)hipStreamDestroy(s);
+        return np::fail(NP_ERR_DEVICE, "side lane of np_sgemm: %s", hipGetErrorString(e));
+    }
+    d.lane_done = e0;
+    d.main_mark = e1;
+    d.lane_mark = e2;
+    d.lane = s;
+    return NP_OK;
 }
 
 constexpr size_t kAskDriverFrom = size_t(64) << 20;     // np_malloc: requests from 64 MiB on look at the device's free memory first
@@ -124,7 +192,77 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-hipStream_t stream() { return rt().cur().cur_stream; }
+hipStream_t stream() { return joined(rt().cur()); }
+hipStream_t stream_nojoin() { return rt().cur().cur_stream; }
+
+// Where the GEMM goes and what orders it (np_sgemm_lane.h).  The lane stays locked until the object dies, so that no other
+// thread's np::stream() can slip between the launch and the event that lets a join wait for it.
+int LaneLaunch::begin(const lane::Gemm &cur, double flop) {
+    DeviceState &d = rt().cur();
+    d.lane_mu.lock();
+    dev_ = &d;
+    unsigned flags = 0;
+    if (stream_nojoin() == d.own_stream) flags |= lane::kOwnStream;
+    if (g_lane_on.load(std::memory_order_relaxed)) flags |= lane::kKnobOn;
+    if (flop >= g_lane_min_flop.load(std::memory_order_relaxed)) flags |= lane::kBigEnough;
+    if (d.prev_valid) flags |= lane::kPrevValid;
+    if (d.prev_on_side) flags |= lane::kPrevOnSide;
+    if ((flags & lane::kGate) == (lane::kGate & ~lane::kNotCapturing)) {   // (asked only of launches that pass the rest of the gate)
+        hipStreamCaptureStatus st = hipStreamCaptureStatusActive;
+        if (hipStreamIsCapturing(stream_nojoin(), &st) == hipSuccess) {
+            if (st == hipStreamCaptureStatusNone) flags |= lane::kNotCapturing;
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+    const bool gate = (flags & lane::kGate) == lane::kGate;
+    if (gate)
+        if (int rc = lane_create_locked(d)) return rc;
+    const lane::Where where = lane::lane_decide(d.prev, cur, d.main_seq, flags);
+    // The two streams are ordered SYMMETRICALLY: a launch on either waits for the mark recorded on the other in front of the launch
+    // before it — behind everything the other stream was given except that one launch, the only one it was compared with.
+    if (where == lane::SIDE) {
+        NP_HIP_CHECK(hipStreamWaitEvent(d.lane, d.main_mark, 0));
+        NP_HIP_CHECK(hipEventRecord(d.lane_mark, d.lane));
+        stream = d.lane;
+        side_ = true;
+        d.lane_pending = true;
+    } else {
+        stream = where == lane::MAIN_JOINED ? joined_locked(d) : stream_nojoin();
+        if (where == lane::MAIN_BEHIND_PREV) NP_HIP_CHECK(hipStreamWaitEvent(stream, d.lane_mark, 0));
+        if (gate) NP_HIP_CHECK(hipEventRecord(d.main_mark, stream));
+    }
+    d.prev_valid = gate;
+    if (gate) {
+        d.prev = cur;
+        d.prev.seq = d.main_seq;
+        d.prev_on_side = side_;
+        g_lane_stats[where == lane::SIDE ? 0 : where == lane::MAIN_BEHIND_PREV ? 1 : 2].fetch_add(1, std::memory_order_relaxed);
+    }
+    return NP_OK;
+}
+
+LaneLaunch::~LaneLaunch() {
+    if (!dev_) return;
+    DeviceState &d = *(DeviceState *)dev_;
+    if (side_ && hipEventRecord(d.lane_done, d.lane) != hipSuccess) {
+        // without the event no join could wait for this launch: drain the lane here and now instead
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(d.lane);
+        d.lane_pending = false;
+        d.prev_valid = false;
+    }
+    d.lane_mu.unlock();
+}
+
+void lane_set_knob(int what) {
+    if (what <= 1) g_lane_on.store(what == 1, std::memory_order_relaxed);
+    else g_lane_min_flop.store(what == 2 ? 0.0 : kLaneMinFlop, std::memory_order_relaxed);
+}
+
+void lane_stats(unsigned long long out[3]) {
+    for (int i = 0; i < 3; ++i) out[i] = g_lane_stats[i].load(std::memory_order_relaxed);
+}
 int g_cus_override = 0;   // np_debug_set_cus: what the planners take for the CU count (a CU-masked library stream reaches fewer)
 int num_cus() { return g_cus_override > 0 ? g_cus_override : rt().cur().cus; }
 
@@ -323,7 +461,7 @@ int result_wait() {
     } else if (r.wait_mode == 1 && r.slots) {
         volatile uint32_t *flag = (volatile uint32_t *)(r.slots + 63);
         const uint32_t want = ++r.wait_seq;
-        const hipError_t e = hipStreamWriteValue32(r.cur().cur_stream, (void *)flag, want, 0);
+        const hipError_t e = hipStreamWriteValue32(np::stream(), (void *)flag, want, 0);
         if (e == hipSuccess) {
             for (unsigned spins = 0;; ++spins) {
                 if (*flag == want) return NP_OK;
@@ -335,7 +473,7 @@ int result_wait() {
             r.wait_mode = 0;   // not supported here: never try again
         }
     }
-    NP_HIP_CHECK(hipStreamSynchronize(r.cur().cur_stream));
+    NP_HIP_CHECK(hipStreamSynchronize(np::stream()));
     return NP_OK;
 }
 
@@ -405,7 +543,7 @@ int np_runtime_set_variant(int variant) {
 
 int np_sync(void) {
     if (int rc = np::ensure_init()) return rc;
-    NP_HIP_CHECK(hipStreamSynchronize(rt().cur().cur_stream));
+    NP_HIP_CHECK(hipStreamSynchronize(np::stream()));   // (joined: the lane's work is behind this wait too)
     return np::check_device_error("np_sync");
 }
 
@@ -524,17 +662,19 @@ int np_debug_hw_ids(unsigned *host_out2, size_t workgroups) {
 int np_set_stream(void *hip_stream) {
     if (int rc = np::ensure_init()) return rc;
     DeviceState &d = rt().cur();
+    std::lock_guard<std::mutex> lk(d.lane_mu);
     hipStream_t next = hip_stream ? (hipStream_t)hip_stream : d.own_stream;
-    if (next == d.cur_stream) return NP_OK;   // per-chunk callers (parallel.hip_compute) must not block here
-    // drain the stream we are leaving so pool reuse stays ordered
-    NP_HIP_CHECK(hipStreamSynchronize(d.cur_stream));
+    if (next == np::stream_nojoin()) return NP_OK;   // per-chunk callers (parallel.hip_compute) must not block here
+    // drain the stream we are leaving (and, through the join, the lane) so pool reuse stays ordered
+    NP_HIP_CHECK(hipStreamSynchronize(joined_locked(d)));
     d.cur_stream = next;
+    ++d.main_seq;
     return NP_OK;
 }
 
 void *np_get_stream(void) {
     if (np::ensure_init()) return nullptr;
-    return (void *)rt().cur().cur_stream;
+    return (void *)np::stream();   // joined: the caller's own work on it is behind the lane's
 }
 
 /* ---- timers ---- */
@@ -550,12 +690,12 @@ int np_timer_create(void **timer) {
 }
 int np_timer_start(void *timer) {
     if (!timer) return np::fail(NP_ERR_INVALID, "np_timer_start: null timer");
-    NP_HIP_CHECK(hipEventRecord(((Timer *)timer)->start, rt().cur().cur_stream));
+    NP_HIP_CHECK(hipEventRecord(((Timer *)timer)->start, np::stream()));
     return NP_OK;
 }
 int np_timer_stop(void *timer) {
     if (!timer) return np::fail(NP_ERR_INVALID, "np_timer_stop: null timer");
-    NP_HIP_CHECK(hipEventRecord(((Timer *)timer)->stop, rt().cur().cur_stream));
+    NP_HIP_CHECK(hipEventRecord(((Timer *)timer)->stop, np::stream()));
     return NP_OK;
 }
 int np_timer_elapsed_ms(void *timer, float *host_ms) {
@@ -584,7 +724,7 @@ int np_timer_destroy(void *timer) {
 // captured).
 int np_graph_begin(void) {
     if (int rc = np::ensure_init()) return rc;
-    NP_HIP_CHECK(hipStreamBeginCapture(rt().cur().cur_stream, hipStreamCaptureModeThreadLocal));
+    NP_HIP_CHECK(hipStreamBeginCapture(np::stream(), hipStreamCaptureModeThreadLocal));
     return NP_OK;
 }
 
@@ -592,7 +732,7 @@ int np_graph_end(void **graph_exec) {
     if (!graph_exec) return np::fail(NP_ERR_INVALID, "np_graph_end: null output");
     *graph_exec = nullptr;
     hipGraph_t graph = nullptr;
-    NP_HIP_CHECK(hipStreamEndCapture(rt().cur().cur_stream, &graph));
+    NP_HIP_CHECK(hipStreamEndCapture(np::stream(), &graph));
     hipGraphExec_t exec = nullptr;
     hipError_t e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
@@ -603,7 +743,7 @@ int np_graph_end(void **graph_exec) {
 
 int np_graph_launch(void *graph_exec) {
     if (!graph_exec) return np::fail(NP_ERR_INVALID, "np_graph_launch: null graph");
-    NP_HIP_CHECK(hipGraphLaunch((hipGraphExec_t)graph_exec, rt().cur().cur_stream));
+    NP_HIP_CHECK(hipGraphLaunch((hipGraphExec_t)graph_exec, np::stream()));
     return NP_OK;
 }
 
@@ -642,7 +782,7 @@ int np_malloc(void **dev_ptr, size_t bytes) {
             size_t free_b = 0, total_b = 0;
             if (cached && hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b < sz + pad + kDriverHeadroom) {
                 for (DeviceState &o : r.dev)
-                    if (o.inited) NP_HIP_CHECK(hipStreamSynchronize(o.cur_stream));
+                    if (o.inited) NP_HIP_CHECK(hipStreamSynchronize(joined(o)));
                 trim_locked(r);
             }
         }
@@ -651,7 +791,7 @@ int np_malloc(void **dev_ptr, size_t bytes) {
             (void)hipGetLastError();
             // give cached blocks back to the driver and retry once
             for (DeviceState &o : r.dev)
-                if (o.inited) NP_HIP_CHECK(hipStreamSynchronize(o.cur_stream));
+                if (o.inited) NP_HIP_CHECK(hipStreamSynchronize(joined(o)));
             trim_locked(r);
             e = hipMalloc(&p, sz + pad);
             if (e != hipSuccess) {
@@ -694,7 +834,7 @@ int np_pool_trim(size_t *host_bytes) {
     Runtime &r = rt();
     std::lock_guard<std::mutex> lk(r.mu);
     for (DeviceState &o : r.dev)
-        if (o.inited) NP_HIP_CHECK(hipStreamSynchronize(o.cur_stream));
+        if (o.inited) NP_HIP_CHECK(hipStreamSynchronize(joined(o)));
     size_t released = trim_locked(r);
     if (host_bytes) *host_bytes = released;
     return NP_OK;

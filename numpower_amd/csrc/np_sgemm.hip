@@ -2426,7 +2426,9 @@ constexpr unsigned kDmasBM[6] = {128, 128, 64, 128, 128, 64}, kDmasBN[6] = {128,
 int launch_dmas(int shape, GemmArgs g, unsigned batch, unsigned S);
 int launch_kq(int shape, GemmArgs g, unsigned batch, bool vec);
 
-int launch_cfg(int cfg, GemmArgs g, unsigned batch, bool vec) {
+// `whole`: the launch is a whole product (no split-K part, no leading block of one): with batch == 1 and no progress request
+// such a launch of the LDS-DMA kernel may run next to the one before it (np::LaneLaunch)
+int launch_cfg(int cfg, GemmArgs g, unsigned batch, bool vec, bool whole = false) {
     if (cfg >= kFirstKqCfg) {
         const int rc = launch_kq(cfg - kFirstKqCfg, g, batch, vec);
         if (rc != 1) return rc;
@@ -2447,17 +2449,35 @@ int launch_cfg(int cfg, GemmArgs g, unsigned batch, bool vec) {
         if (g_variant == 0 && g.tiles_m >= 8) g.swizzle = 4;
         const bool edge = g.M % 256 || g.N % 128 || g.n_store;
         const bool ktail = g.K % 16 || g.K_last % 16 || g.N % 4;   // N % 4: B's last row needs the tail tile's fix-up
+        // Independent large products alternate between the library stream and the runtime's side lane: all 512 workgroups of
+        // a 4096^3 launch are one resident round and reach their stores together, so C drains with every matrix pipe idle, and
+        // the next launch's prologue follows; on two streams the next launch's workgroups take the slots as they come free.
+        // (`lane` keeps the runtime's lane mutex from begin() until it dies: nothing between here and the end of this block may call
+        // np::stream() — it takes the same mutex — so the launch uses `s` and only `s`)
+        np::LaneLaunch lane;
+        hipStream_t s;
+        if (whole && batch == 1 && !g.progress) {
+            np::lane::Gemm cur;
+            cur.a = np::lane::range_of(g.A, g.M, g.lda, g.K);
+            cur.b = np::lane::range_of(g.B, g.K, g.ldb, g.N);
+            cur.c = np::lane::range_of(g.C, g.M, g.ldc, g.n_store ? g.n_store : g.N);
+            cur.seq = 0;
+            if (int rc = lane.begin(cur, 2.0 * (double)g.M * (double)g.N * (double)g.K)) return rc;
+            s = lane.stream;
+        } else {
+            s = np::stream();
+        }
         if (edge && ktail)
-            sgemm_dma_kernel<true, true><<<grid, 256, 0, np::stream()>>>(g);
+            sgemm_dma_kernel<true, true><<<grid, 256, 0, s>>>(g);
         else if (edge)
-            sgemm_dma_kernel<true, false><<<grid, 256, 0, np::stream()>>>(g);
+            sgemm_dma_kernel<true, false><<<grid, 256, 0, s>>>(g);
         else if (ktail)
-            sgemm_dma_kernel<false, true><<<grid, 256, 0, np::stream()>>>(g);
+            sgemm_dma_kernel<false, true><<<grid, 256, 0, s>>>(g);
         else if (g_prio_period && g.K >= g_prio_min_k) {
             g.prio_period = g_prio_period;
-            sgemm_dma_kernel<false, false, true><<<grid, 256, 0, np::stream()>>>(g);
+            sgemm_dma_kernel<false, false, true><<<grid, 256, 0, s>>>(g);
         } else
-            sgemm_dma_kernel<false, false><<<grid, 256, 0, np::stream()>>>(g);
+            sgemm_dma_kernel<false, false><<<grid, 256, 0, s>>>(g);
         NP_LAUNCH_CHECK("sgemm_dma_kernel");
         note_progress_launch(g);
         return NP_OK;
@@ -2945,7 +2965,7 @@ int launch_plan(const Plan &p, GemmArgs g, size_t batch, bool vec) {
         const int rc = launch_dmas(p.cfg - kFirstMidCfg, g, (unsigned)batch, p.S);
         if (rc != 1) return rc;
     }
-    if (p.tail_rows == 0) return launch_cfg(p.cfg, g, (unsigned)batch, vec);
+    if (p.tail_rows == 0) return launch_cfg(p.cfg, g, (unsigned)batch, vec, true);
     const TileCfg &T = kCfg[p.cfg];
     const size_t tm = (M + T.bm - 1) / T.bm;
     const size_t m1 = (tm - p.tail_rows) * T.bm, m2 = M - m1;
@@ -3027,7 +3047,7 @@ int launch_sgemm_ld(size_t batch, size_t M, size_t N, size_t K, const float *A, 
         case 5: return launch_sgemm_pipe<128, 128, 0>(g, (unsigned)batch, vec);
         case 6: return launch_sgemm_pipe<128, 128, 1>(g, (unsigned)batch, vec);
         case 7:
-            if (N >= 4 && K >= 4 && (vec || g_dma_any_alignment)) return launch_cfg(0, g, (unsigned)batch, vec);   // any size: tests
+            if (N >= 4 && K >= 4 && (vec || g_dma_any_alignment)) return launch_cfg(0, g, (unsigned)batch, vec, true);   // any size: tests
             return launch_sgemm_pipe<128, 128, 1>(g, (unsigned)batch, vec);
         default: break;
     }
@@ -3452,6 +3472,10 @@ int np_sgemm_set_variant(int variant) {
         return NP_OK;
     }
     if (variant < 0) {   // -1: whole-K plans only, -2: default planner, -3: default + forced operand padding, -4 / -5: stream-K always / never
+        if (variant <= -27 && variant >= -30) {   // -27 / -28: independent large products on one stream / alternating with the side lane (default); -29: products of any size qualify (tests), -30: from 4e9 flop again
+            np::lane_set_knob(-27 - variant);
+            return NP_OK;
+        }
         if (variant == -16 || variant == -17) {
             g_mid_swizzle = variant == -17;
             return NP_OK;
@@ -3507,6 +3531,13 @@ int np_sgemm_set_variant(int variant) {
         return np::fail(NP_ERR_INVALID, "np_sgemm_set_variant: ablation variants exist only in tuning builds (-DNP_TUNING)");
 #endif
     g_variant = variant;
+    return NP_OK;
+}
+
+int np_sgemm_overlap_stats(unsigned long long out[3]) {
+    if (!out) return np::fail(NP_ERR_INVALID, "np_sgemm_overlap_stats: null output");
+    if (int rc = np::ensure_init()) return rc;
+    np::lane_stats(out);
     return NP_OK;
 }
 
