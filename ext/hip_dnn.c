@@ -28,9 +28,12 @@
 
 /* the layer's extents, read once the shapes have been checked */
 typedef struct { size_t N, C, H, W, F, kh, kw; } nph_layer;
+/* stride, padding and dilation of an Ex call, as given */
+typedef struct { int sh, sw, ph, pw, dh, dw; } nph_geometry;
 
-/* the checks both directions share; y == NULL: forward.  0 after a raised error */
-static int layer_of(NDArray *x, NDArray *y, NDArray *filters, nph_layer *l) {
+/* the checks both directions share; y == NULL: forward; g == NULL: stride 1, no padding, dilation 1 and the messages of the
+ * reference-signature calls.  0 after a raised error */
+static int layer_of(NDArray *x, NDArray *y, NDArray *filters, const nph_geometry *g, nph_layer *l) {
     if (NDArray_NDIM(x) != 4 || NDArray_NDIM(filters) != 4 || (y != NULL && NDArray_NDIM(y) != 4)) {
         np_ext_throw(NPH_DNN_MSG_NDIM);
         return 0;
@@ -40,14 +43,36 @@ static int layer_of(NDArray *x, NDArray *y, NDArray *filters, nph_layer *l) {
         np_ext_throw(NPH_DNN_MSG_CHANNELS);
         return 0;
     }
-    if (fs[2] > xs[2] || fs[3] > xs[3]) {
+    if (g == NULL && (fs[2] > xs[2] || fs[3] > xs[3])) {
         np_ext_throw(NPH_DNN_MSG_WINDOW);
         return 0;
     }
+    /* the forward result's extents, in 64 bits: a dilation times a window may not fit an int */
+    long long oh = (long long) xs[2] - fs[2] + 1, ow = (long long) xs[3] - fs[3] + 1;
+    if (g != NULL) {
+        if (g->sh < 1 || g->sw < 1) {
+            np_ext_throw(NPH_DNN_MSG_STRIDE);
+            return 0;
+        }
+        if (g->dh < 1 || g->dw < 1) {
+            np_ext_throw(NPH_DNN_MSG_DILATION);
+            return 0;
+        }
+        const long long keh = (long long) g->dh * (fs[2] - 1) + 1, kew = (long long) g->dw * (fs[3] - 1) + 1;
+        if (fs[2] >= 1 && fs[3] >= 1 && (g->ph < 0 || g->pw < 0 || g->ph >= keh || g->pw >= kew)) {
+            np_ext_throw(NPH_DNN_MSG_PADDING);
+            return 0;
+        }
+        if (keh > xs[2] + 2LL * g->ph || kew > xs[3] + 2LL * g->pw) {
+            np_ext_throw(NPH_DNN_MSG_EFFECTIVE);
+            return 0;
+        }
+        oh = (xs[2] + 2LL * g->ph - keh) / g->sh + 1, ow = (xs[3] + 2LL * g->pw - kew) / g->sw + 1;
+    }
     if (y != NULL) {
         const int *ys = NDArray_SHAPE(y);
-        if (ys[0] != xs[0] || ys[1] != fs[0] || ys[2] != xs[2] - fs[2] + 1 || ys[3] != xs[3] - fs[3] + 1) {
-            np_ext_throw(NPH_DNN_MSG_GRADIENT);
+        if (ys[0] != xs[0] || ys[1] != fs[0] || ys[2] != oh || ys[3] != ow) {
+            np_ext_throw(g == NULL ? NPH_DNN_MSG_GRADIENT : NPH_DNN_MSG_STRIDED_GRADIENT);
             return 0;
         }
     }
@@ -76,7 +101,7 @@ static NDArray *empty4_on_gpu(size_t d0, size_t d1, size_t d2, size_t d3) {
 
 NDArray *NPH_Conv2D_Forward(NDArray *x, NDArray *filters) {
     nph_layer l;
-    if (x == NULL || filters == NULL || !layer_of(x, NULL, filters, &l)) return NULL;
+    if (x == NULL || filters == NULL || !layer_of(x, NULL, filters, NULL, &l)) return NULL;
     size_t oh = 0, ow = 0;
     if (np_conv2d_shape(l.H, l.W, l.kh, l.kw, 0, 0, &oh, &ow) != NP_OK || l.N < 1 || l.C < 1 || l.F < 1) {
         if (l.N < 1 || l.C < 1 || l.F < 1) np_ext_throw("dnn_conv2d: an operand has no elements");
@@ -95,7 +120,7 @@ NDArray *NPH_Conv2D_Forward(NDArray *x, NDArray *filters) {
 
 NDArray **NPH_Conv2D_Backward(NDArray *x, NDArray *y, NDArray *filters) {
     nph_layer l;
-    if (x == NULL || y == NULL || filters == NULL || !layer_of(x, y, filters, &l)) return NULL;
+    if (x == NULL || y == NULL || filters == NULL || !layer_of(x, y, filters, NULL, &l)) return NULL;
     if (NDArray_NUMELEMENTS(x) < 1 || NDArray_NUMELEMENTS(filters) < 1) {
         np_ext_throw("dnn_conv2d: an operand has no elements");
         return NULL;
@@ -106,6 +131,68 @@ NDArray **NPH_Conv2D_Backward(NDArray *x, NDArray *y, NDArray *filters) {
     int ok = dw != NULL && dx != NULL && rtns != NULL;
     if (ok && (np_conv2d_backward_filter(NDArray_FDATA(x), NDArray_FDATA(y), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, 0, 0, NDArray_FDATA(dw)) != NP_OK ||
                np_conv2d_backward_data(NDArray_FDATA(y), NDArray_FDATA(filters), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, 0, 0, NDArray_FDATA(dx)) != NP_OK)) {
+        np_ext_throw_last();
+        ok = 0;
+    }
+    if (!ok) {
+        if (dw != NULL) NDArray_FREE(dw);
+        if (dx != NULL) NDArray_FREE(dx);
+        if (rtns != NULL) NPH_RELEASE(rtns);
+        return NULL;
+    }
+    rtns[0] = dw;
+    rtns[1] = dx;
+    return rtns;
+}
+
+/* NULL: the default */
+static nph_geometry geometry_of(const int stride[2], const int padding[2], const int dilation[2]) {
+    nph_geometry g = {1, 1, 0, 0, 1, 1};
+    if (stride != NULL) g.sh = stride[0], g.sw = stride[1];
+    if (padding != NULL) g.ph = padding[0], g.pw = padding[1];
+    if (dilation != NULL) g.dh = dilation[0], g.dw = dilation[1];
+    return g;
+}
+
+NDArray *NPH_Conv2D_ForwardEx(NDArray *x, NDArray *filters, const int stride[2], const int padding[2], const int dilation[2]) {
+    nph_layer l;
+    const nph_geometry g = geometry_of(stride, padding, dilation);
+    if (x == NULL || filters == NULL || !layer_of(x, NULL, filters, &g, &l)) return NULL;
+    size_t oh = 0, ow = 0;
+    if (l.N < 1 || l.C < 1 || l.F < 1) {
+        np_ext_throw("dnn_conv2d: an operand has no elements");
+        return NULL;
+    }
+    if (np_conv2d_shape_ex(l.H, l.W, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw, (size_t) g.sh, (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, &oh, &ow) != NP_OK) {
+        np_ext_throw_last();
+        return NULL;
+    }
+    NDArray *rtn = empty4_on_gpu(l.N, l.F, oh, ow);
+    if (rtn == NULL) return NULL;
+    if (np_conv2d_forward_ex(NDArray_FDATA(x), NDArray_FDATA(filters), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw, (size_t) g.sh,
+                             (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, NDArray_FDATA(rtn)) != NP_OK) {
+        np_ext_throw_last();
+        NDArray_FREE(rtn);
+        return NULL;
+    }
+    return rtn;
+}
+
+NDArray **NPH_Conv2D_BackwardEx(NDArray *x, NDArray *y, NDArray *filters, const int stride[2], const int padding[2], const int dilation[2]) {
+    nph_layer l;
+    const nph_geometry g = geometry_of(stride, padding, dilation);
+    if (x == NULL || y == NULL || filters == NULL || !layer_of(x, y, filters, &g, &l)) return NULL;
+    if (NDArray_NUMELEMENTS(x) < 1 || NDArray_NUMELEMENTS(filters) < 1) {
+        np_ext_throw("dnn_conv2d: an operand has no elements");
+        return NULL;
+    }
+    NDArray *dw = empty4_on_gpu(l.F, l.C, l.kh, l.kw), *dx = empty4_on_gpu(l.N, l.C, l.H, l.W);
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 2);
+    int ok = dw != NULL && dx != NULL && rtns != NULL;
+    if (ok && (np_conv2d_backward_filter_ex(NDArray_FDATA(x), NDArray_FDATA(y), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw,
+                                            (size_t) g.sh, (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, NDArray_FDATA(dw)) != NP_OK ||
+               np_conv2d_backward_data_ex(NDArray_FDATA(y), NDArray_FDATA(filters), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw,
+                                          (size_t) g.sh, (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, NDArray_FDATA(dx)) != NP_OK)) {
         np_ext_throw_last();
         ok = 0;
     }

@@ -57,6 +57,23 @@ struct NDArray *NPH_Conv2D_Forward(struct NDArray *x, struct NDArray *filters);
  * libnumpower_host.so. */
 struct NDArray **NPH_Conv2D_Backward(struct NDArray *x, struct NDArray *y, struct NDArray *filters);
 
+/* ---- with a stride, a padding and a dilation (np_conv2d_*_ex of include/np_hip.h; DESIGN.md §3.14 "the general gather") ----
+ * The reference's layer names strides, padding and dilation_rate (dnn.c:196-200) and then hard-wires stride 1, no padding; its
+ * two functions above have no argument for them.  These two are what a binding with such arguments calls: each of stride,
+ * padding, dilation is (rows, columns), NULL meaning (1, 1), (0, 0), (1, 1).  The effective window is dilation . (k - 1) + 1;
+ * y (N, F, oh, ow) with oh = floor((H + 2 ph - keh) / sh) + 1.  The messages above, with these four in place of
+ * NPH_DNN_MSG_WINDOW and NPH_DNN_MSG_GRADIENT, checked in this order after the channels: */
+#define NPH_DNN_MSG_STRIDE "dnn_conv2d: the stride must be at least 1 along both axes"
+#define NPH_DNN_MSG_DILATION "dnn_conv2d: the dilation must be at least 1 along both axes"
+#define NPH_DNN_MSG_PADDING "dnn_conv2d: the padding must be at least 0 and smaller than the effective window, dilation . (k - 1) + 1"
+#define NPH_DNN_MSG_EFFECTIVE "dnn_conv2d: the effective window, dilation . (k - 1) + 1, must not be larger than the padded input (H + 2 ph, W + 2 pw)"
+#define NPH_DNN_MSG_STRIDED_GRADIENT "dnn_conv2d_backward: the gradient must have the shape of the forward result (N, F, (H + 2 ph - keh) / sh + 1, (W + 2 pw - kew) / sw + 1)"
+
+struct NDArray *NPH_Conv2D_ForwardEx(struct NDArray *x, struct NDArray *filters, const int stride[2], const int padding[2], const int dilation[2]);
+/* {dW (F, C, kh, kw), dX (N, C, H, W)} as NPH_Conv2D_Backward; rows and columns of x that no window reads get dX = +0 */
+struct NDArray **NPH_Conv2D_BackwardEx(struct NDArray *x, struct NDArray *y, struct NDArray *filters, const int stride[2], const int padding[2],
+                                       const int dilation[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -598,6 +598,35 @@ int np_conv2d_backward_data(const float *dy, const float *w, size_t N, size_t C,
 int np_conv2d_backward_filter(const float *x, const float *dy, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
                               size_t ph, size_t pw, float *dw);
 
+/* ---- convolution layers with a stride and a dilation (np_dnn.hip; DESIGN.md "dnn_conv2d") ------------
+ * The calls above with a window stride (sh, sw) >= 1 and a tap dilation (dh, dw) >= 1, inserted after (ph, pw).  The effective
+ * window is keh = dh (kh - 1) + 1, kew = dw (kw - 1) + 1, and 0 <= ph < keh, 0 <= pw < kew.
+ *   oh = floor((H + 2 ph - keh) / sh) + 1, ow = floor((W + 2 pw - kew) / sw) + 1
+ *   y[n,f,i,j]  = sum_{c,p,q} w[f,c,p,q] . x~[n,c,i.sh+p.dh-ph,j.sw+q.dw-pw]
+ *   dW[f,c,p,q] = sum_{n,i,j} dy[n,f,i,j] . x~[n,c,i.sh+p.dh-ph,j.sw+q.dw-pw]
+ *   dX[n,c,u,v] = sum_{f,p,q} dy~[n,f,(u+ph-p.dh)/sh,(v+pw-q.dw)/sw] . w[f,c,p,q]   a quotient that is no integer in range: a stored zero
+ * One gather serves all three: position t = i.s - pad + p.d on the grid of the gathered operand dilated by l reads in[t / l]
+ * when t >= 0, t mod l == 0 and t / l < extent, else a STORED zero.  Forward and dW gather x with l = 1; dX is the forward
+ * kernel over dy with the filters flipped and transposed, stride 1, the layer's tap dilation, pad (keh - 1 - ph, kew - 1 - pw),
+ * input dilation (sh, sw) and output (H, W).  The dilated input spends sh.sw times the useful multiply-adds on stored zeros.
+ * Rows and columns of x that no window reads (the remainder of the floor) get dX = +0.0f for finite filters, and a NaN there
+ * in x reaches nothing.
+ * The reduction orders are the ones stated above and do not depend on the stride or the dilation: a strided y is bit for bit
+ * the subsample of the unit-stride y, a dilated y the unit y of the zero-stuffed filter (finite data), a strided dX the unit dX
+ * of the zero-stuffed dy where (H + 2 ph - keh) mod sh == 0 and likewise for W.  With (sh, sw, dh, dw) = (1, 1, 1, 1) the calls
+ * launch the same kernels as the calls above and return the same bits.
+ * Convention as above.  NP_ERR_INVALID before any device work: a null pointer; an extent, stride or dilation of zero;
+ * ph >= keh or pw >= kew; keh > H + 2 ph or kew > W + 2 pw; H + 2 ph, W + 2 pw, keh, kew, a stride, any of numel(x), numel(w),
+ * numel(y), N.oh.ow, C.kh.kw or F.kh.kw at 2^31 or more. */
+int np_conv2d_shape_ex(size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw,
+                       size_t *oh, size_t *ow);
+int np_conv2d_forward_ex(const float *x, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
+                         size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, float *y);
+int np_conv2d_backward_data_ex(const float *dy, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
+                               size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, float *dx);
+int np_conv2d_backward_filter_ex(const float *x, const float *dy, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
+                                 size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, float *dw_out);
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

@@ -130,6 +130,9 @@ int np_debug_conv2d_staged_path(int on);
  * count TM (32, 64 or 128; 0 = none yet) and, for _backward_filter, the number of slices S its reduction was cut into (1: written
  * directly, no fold kernel); 0 slices after the two others.  Plain process globals. */
 int np_debug_dnn_last_path(int *host_tm, int *host_slices);
+/* tests / tools: the form of the gather that call compiled to: 0 unit (stride 1, dilation 1), 1 strided / dilated window,
+ * 2 dilated input (the data gradient of a strided layer). */
+int np_debug_dnn_last_form(int *host_form);
 /* tests / tools: which kernel families the last np_reduce_axis or np_reduce_all(_dev) call of the process launched, the calls it
  * makes on its own partials included: the OR of the NP_REDUCE_PATH_ bits below (0 = none yet).  A plain process global, cleared
  * at the top of those entry points; calls the library makes itself (split-K GEMM folds, chain partials) overwrite it too. */

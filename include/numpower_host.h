@@ -387,6 +387,13 @@ NDArray *NDArray_Correlate2D(NDArray *a, NDArray *b, int mode, int boundary, NDA
  * library has no CPU convolution. */
 NDArray *NDArrayDNN_Conv2D_Forward(NDArray *x, NDArray *filters, int *kernel_size, char activation, int use_bias);
 NDArray **NDArrayDNN_Conv2D_Backward(NDArray *input, NDArray *y, NDArray *filters, int kernel_size, char activation, int use_bias);
+/* The same layer with a window stride, a zero padding and a tap dilation, each (rows, columns), NULL meaning (1, 1), (0, 0),
+ * (1, 1): y (N, F, oh, ow), oh = floor((H + 2 ph - keh) / sh) + 1 with the effective window keh = dh (kh - 1) + 1.  The reference
+ * has no such functions (its layer names the three and hard-wires stride 1, no padding: dnn.c:196-200).  Views are made
+ * contiguous; NPH_Conv2D_ForwardEx / _BackwardEx over np_conv2d_*_ex do the work.  Errors as above, with NPH_DNN_MSG_STRIDE,
+ * _DILATION, _PADDING, _EFFECTIVE and _STRIDED_GRADIENT in place of the window and gradient messages. */
+NDArray *NDArrayDNN_Conv2D_ForwardEx(NDArray *x, NDArray *filters, const int *stride, const int *padding, const int *dilation);
+NDArray **NDArrayDNN_Conv2D_BackwardEx(NDArray *input, NDArray *y, NDArray *filters, const int *stride, const int *padding, const int *dilation);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,8 @@
 // Convolution layers for GPU arrays: np_conv2d_forward, np_conv2d_backward_data, np_conv2d_backward_filter.
 //
-// x (N, C, H, W), w (F, C, kh, kw), y (N, F, oh, ow), row-major fp32; cross-correlation, stride 1, dilation 1, zero padding (ph, pw).
+// and their _ex forms with a window stride (sh, sw) and a tap dilation (dh, dw).
+//
+// x (N, C, H, W), w (F, C, kh, kw), y (N, F, oh, ow), row-major fp32; cross-correlation, zero padding (ph, pw).
 // Everything is an implicit GEMM on v_mfma_f32_32x32x2_f32; no im2col matrix is ever written.
 //
 //   forward   Y (F x N.P) = Wm (F x K) . Col (K x N.P),  K = C.kh.kw with k = (c.kh + p).kw + q — the filters' own memory, so
@@ -13,6 +15,15 @@
 //             long: it is cut into S slices of whole kTK-steps, each slice's tile goes to pool scratch and dnn_wgrad_fold_kernel
 //             adds the slices in slice order (S == 1 writes dW directly).  No float atomics.
 //
+// The general gather.  A kernel is compiled in three FORMs of one gather: position t = i.s - pad + p.d on the grid of the
+// gathered operand dilated by l reads in[t / l] when t >= 0, t mod l == 0 and t / l < extent, and a stored zero otherwise.
+//   0  unit: s = d = l = 1, the text above and the code it always was
+//   1  window stride s and tap dilation d, l = 1: the forward pass and dW of a strided / dilated layer, dX of a dilated one
+//   2  input dilation l with s = 1: dX of a strided layer is the forward pass over dy dilated by (sh, sw), taps dilated by
+//      (dh, dw), pad (keh - 1 - ph, kew - 1 - pw), out (H, W).  It spends sh.sw times the useful MACs on stored zeros.
+// No form divides per gathered element: the pixel is decoded once (form 2: into quotient and residue mod l), the step's tap
+// table holds p.d and q.d (form 2: their quotients and residues), and a residue sum is 0, l (carry one) or no multiple of l.
+//
 // Tiles: a workgroup of 4 waves computes TM x kTN outputs through LDS in reduction steps of kTK; TM is 32, 64 or 128 and is the
 // smallest that covers F (beyond 128: 128), so a layer with few filters does not burn a 128-row tile.  Out-of-range taps, the
 // reduction's tail and the tile edges are zero-filled on BOTH operands: nothing outside the receptive field reaches an output.
@@ -23,6 +34,8 @@
 // at any batch size and position.  For dW the chain runs over jg inside a slice and the slices are then added in order; S is a
 // function of the extents alone.  Results are bit-identical from run to run.
 #include <limits.h>
+
+#include <type_traits>
 
 #include "np_internal.h"
 
@@ -38,15 +51,26 @@ constexpr int kWgradMinSteps = 8, kWgradTargetGroups = 512, kWgradMaxSlices = 25
 
 typedef float dnn_v16f __attribute__((ext_vector_type(16)));
 
-int g_dnn_last_tm = 0, g_dnn_last_slices = 0;
+int g_dnn_last_tm = 0, g_dnn_last_slices = 0, g_dnn_last_form = 0;
 
-struct ConvArgs {
+// what the unit form reads: its kernel arguments, and with them its instruction stream, are what they were before the general gather
+struct ConvCore {
     const float *x;   // the gathered operand (N, C, H, W)
     const float *w;   // forward: the filters (F, C, kh, kw) as Wm; dW: dy (N, F, oh, ow)
     float *out;
     int N, C, H, W, F, kh, kw, ph, pw, oh, ow;
     int K, P, NP;     // C.kh.kw, oh.ow, N.P
 };
+
+struct ConvArgs : ConvCore {
+    int sh, sw, dh, dw, lh, lw;   // window stride, tap dilation, input dilation (H, W are the extents BEFORE that dilation)
+};
+
+// a kernel's argument: forms 1 and 2 read the whole of ConvArgs
+template <int FORM>
+using KernelArgs = std::conditional_t<FORM == 0, ConvCore, ConvArgs>;
+
+int form_of(const ConvArgs &a) { return (a.lh != 1 || a.lw != 1) ? 2 : (a.sh != 1 || a.sw != 1 || a.dh != 1 || a.dw != 1) ? 1 : 0; }
 
 // how the 4 waves share a TM x kTN tile: 32 x 32 MFMA blocks, MI x NJ of them per wave
 template <int TM>
@@ -77,25 +101,69 @@ __device__ __forceinline__ void mma_step(const float *As, const float *Bs, dnn_v
     }
 }
 
-// k = (c.kh + p).kw + q -> the tap's offset inside one image of x and its (p, q); koff = -1 marks the reduction's tail
-__device__ __forceinline__ void decode_tap(const ConvArgs &p, int k, int &koff, int &kp, int &kq) {
+// k = (c.kh + p).kw + q -> the tap's offset inside one image of x and its (p.dh, q.dw); koff = -1 marks the reduction's tail.
+// Form 2: (kp, kq) are the quotients of p.dh, q.dw by the input dilation and (rp, rq) the residues, koff is built from the quotients.
+template <int FORM>
+__device__ __forceinline__ void decode_tap(const KernelArgs<FORM> &p, int k, int &koff, int &kp, int &kq, int &rp, int &rq) {
     koff = -1;
-    kp = kq = 0;
+    kp = kq = rp = rq = 0;
     if (k < p.K) {
         const int khw = p.kh * p.kw, c = k / khw, r = k - c * khw;
         kp = r / p.kw;
         kq = r - kp * p.kw;
+        if constexpr (FORM != 0) kp *= p.dh, kq *= p.dw;
+        if constexpr (FORM == 2) {
+            rp = kp % p.lh, kp /= p.lh;
+            rq = kq % p.lw, kq /= p.lw;
+        }
         koff = (c * p.H + kp) * p.W + kq;
     }
 }
 
+// where the window of output pixel (oi, oj) begins: (ih0, iw0) on the operand's grid; form 2: floor quotient and residue of that
+// position on the dilated grid
+struct Corner {
+    int ih0, iw0, rh0, rw0;
+};
+
+template <int FORM>
+__device__ __forceinline__ Corner corner_of(const KernelArgs<FORM> &p, int oi, int oj) {
+    Corner c = {oi - p.ph, oj - p.pw, 0, 0};
+    if constexpr (FORM == 1) c.ih0 = oi * p.sh - p.ph, c.iw0 = oj * p.sw - p.pw;
+    if constexpr (FORM == 2) {
+        const int th = c.ih0, tw = c.iw0;   // >= -(keh - 1), -(kew - 1)
+        c.ih0 = th / p.lh, c.rh0 = th - c.ih0 * p.lh;
+        if (c.rh0 < 0) c.rh0 += p.lh, --c.ih0;
+        c.iw0 = tw / p.lw, c.rw0 = tw - c.iw0 * p.lw;
+        if (c.rw0 < 0) c.rw0 += p.lw, --c.iw0;
+    }
+    return c;
+}
+
+// one element of Col: x at the corner xo (+ (ih0, iw0)) plus the tap, or a stored zero
+template <int FORM>
+__device__ __forceinline__ float gather(const KernelArgs<FORM> &p, bool pixel, long long xo, const Corner &c, int koff, int kp, int kq, int rp, int rq) {
+    int ih = c.ih0 + kp, iw = c.iw0 + kq;
+    if constexpr (FORM == 2) {
+        // residue sums lie in [0, 2l - 2]: 0 and l are the multiples of l, l carries one into the quotient
+        const int rh = c.rh0 + rp, rw = c.rw0 + rq;
+        const bool ch = rh == p.lh, cw = rw == p.lw;
+        if ((rh != 0 && !ch) || (rw != 0 && !cw)) return 0.0f;
+        if (ch) ++ih, xo += p.W;
+        if (cw) ++iw, ++xo;
+    }
+    if (pixel && koff >= 0 && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) return p.x[xo + koff];
+    return 0.0f;
+}
+
 // grid.x = F-tiles x pixel-tiles, F-tiles fastest: neighbouring workgroups gather the same pixels
-template <int TM>
-__global__ __launch_bounds__(256, 2) void dnn_fprop_kernel(const ConvArgs p) {
+template <int TM, int FORM>
+__global__ __launch_bounds__(256, 2) void dnn_fprop_kernel(const KernelArgs<FORM> p) {
     using T = Tile<TM>;
     __shared__ float As[TM * kAStr];
     __shared__ float Bs[kTK * kBStr];
     __shared__ int s_koff[kTK], s_kp[kTK], s_kq[kTK];   // the step's offset table: one decode per k, none per element
+    __shared__ int s_rp[FORM == 2 ? kTK : 1], s_rq[FORM == 2 ? kTK : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / T::WN, wn = wave % T::WN;
     const int tiles_f = (p.F + TM - 1) / TM;
     const int f0 = (int)(blockIdx.x % tiles_f) * TM, j0 = (int)(blockIdx.x / tiles_f) * kTN;
@@ -112,18 +180,21 @@ __global__ __launch_bounds__(256, 2) void dnn_fprop_kernel(const ConvArgs p) {
     const int jl = tid & (kTN - 1), krow0 = tid >> 7;
     const int jg = j0 + jl;
     const bool pixel = jg < p.NP;
-    int ih0 = 0, iw0 = 0;
+    Corner cr = {0, 0, 0, 0};
     long long xo = 0;   // the window's corner in x: outside the array where the padding begins, only ever added to a valid tap
     if (pixel) {
         const int n = jg / p.P, pix = jg - n * p.P, oi = pix / p.ow, oj = pix - oi * p.ow;
-        ih0 = oi - p.ph;
-        iw0 = oj - p.pw;
-        xo = (long long)n * p.C * p.H * p.W + (long long)ih0 * p.W + iw0;
+        cr = corner_of<FORM>(p, oi, oj);
+        xo = (long long)n * p.C * p.H * p.W + (long long)cr.ih0 * p.W + cr.iw0;
     }
     const int kc = tid & 31, fr = tid >> 5;
 
     for (int k0 = 0; k0 < p.K; k0 += kTK) {
-        if (tid < kTK) decode_tap(p, k0 + tid, s_koff[tid], s_kp[tid], s_kq[tid]);
+        if (tid < kTK) {
+            int rp, rq;
+            decode_tap<FORM>(p, k0 + tid, s_koff[tid], s_kp[tid], s_kq[tid], rp, rq);
+            if constexpr (FORM == 2) s_rp[tid] = rp, s_rq[tid] = rq;
+        }
         __syncthreads();   // also: every wave is done with the previous step's tiles
 #pragma unroll
         for (int u = 0; u < TM / 8; ++u) {
@@ -132,10 +203,8 @@ __global__ __launch_bounds__(256, 2) void dnn_fprop_kernel(const ConvArgs p) {
         }
 #pragma unroll
         for (int u = 0; u < kTK / 2; ++u) {
-            const int kr = krow0 + 2 * u, koff = s_koff[kr], ih = ih0 + s_kp[kr], iw = iw0 + s_kq[kr];
-            float v = 0.0f;
-            if (pixel && koff >= 0 && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) v = p.x[xo + koff];
-            Bs[kr * kBStr + jl] = v;
+            const int kr = krow0 + 2 * u;
+            Bs[kr * kBStr + jl] = gather<FORM>(p, pixel, xo, cr, s_koff[kr], s_kp[kr], s_kq[kr], FORM == 2 ? s_rp[kr] : 0, FORM == 2 ? s_rq[kr] : 0);
         }
         __syncthreads();
         mma_step<TM>(As, Bs, acc, wm, wn, lane);
@@ -171,8 +240,9 @@ __global__ __launch_bounds__(256) void dnn_filter_flip_kernel(const float *__res
 
 // grid.x = F-tiles x k-tiles, grid.y = slices; a slice reduces steps [slice * steps_per_slice, ...) of kTK pixels jg each and
 // stores its F x K tile at out + slice * F * K
-template <int TM>
-__global__ __launch_bounds__(256, 2) void dnn_wgrad_kernel(const ConvArgs p, int steps_per_slice) {
+template <int TM, int FORM>
+__global__ __launch_bounds__(256, 2) void dnn_wgrad_kernel(const KernelArgs<FORM> p, int steps_per_slice) {
+    static_assert(FORM != 2, "the filter gradient gathers x itself: no input dilation");
     using T = Tile<TM>;
     __shared__ float As[TM * kAStr];
     __shared__ float Bs[kTK * kBStr];
@@ -189,7 +259,10 @@ __global__ __launch_bounds__(256, 2) void dnn_wgrad_kernel(const ConvArgs p, int
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[mi][nj][r] = 0.0f;
 
-    if (tid < kTN) decode_tap(p, kc0 + tid, s_koff[tid], s_kp[tid], s_kq[tid]);
+    if (tid < kTN) {
+        int rp, rq;
+        decode_tap<FORM>(p, kc0 + tid, s_koff[tid], s_kp[tid], s_kq[tid], rp, rq);
+    }
     const int steps = (p.NP + kTK - 1) / kTK;
     const int s0 = (int)blockIdx.y * steps_per_slice, s1 = s0 + steps_per_slice < steps ? s0 + steps_per_slice : steps;
     const int kr = tid & 31, g = tid >> 5;   // a thread stages one pixel of the step: consecutive lanes, consecutive addresses
@@ -197,15 +270,15 @@ __global__ __launch_bounds__(256, 2) void dnn_wgrad_kernel(const ConvArgs p, int
     for (int s = s0; s < s1; ++s) {
         const int jg = s * kTK + kr;
         const bool pixel = jg < p.NP;
-        int n = 0, pix = 0, ih0 = 0, iw0 = 0;
+        int n = 0, pix = 0;
+        Corner cr = {0, 0, 0, 0};
         if (pixel) {
             n = jg / p.P;
             pix = jg - n * p.P;
             const int oi = pix / p.ow, oj = pix - oi * p.ow;
-            ih0 = oi - p.ph;
-            iw0 = oj - p.pw;
+            cr = corner_of<FORM>(p, oi, oj);
         }
-        const long long xo = (long long)n * p.C * p.H * p.W + (long long)ih0 * p.W + iw0;
+        const long long xo = (long long)n * p.C * p.H * p.W + (long long)cr.ih0 * p.W + cr.iw0;
         const float *db = p.w + ((size_t)n * p.F * p.P + pix);
         __syncthreads();   // the table (first step); every wave is done with the previous step's tiles
 #pragma unroll
@@ -215,10 +288,8 @@ __global__ __launch_bounds__(256, 2) void dnn_wgrad_kernel(const ConvArgs p, int
         }
 #pragma unroll
         for (int u = 0; u < kTN / 8; ++u) {
-            const int col = g + 8 * u, koff = s_koff[col], ih = ih0 + s_kp[col], iw = iw0 + s_kq[col];
-            float v = 0.0f;
-            if (pixel && koff >= 0 && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W) v = p.x[xo + koff];
-            Bs[kr * kBStr + col] = v;
+            const int col = g + 8 * u;
+            Bs[kr * kBStr + col] = gather<FORM>(p, pixel, xo, cr, s_koff[col], s_kp[col], s_kq[col], 0, 0);
         }
         __syncthreads();
         mma_step<TM>(As, Bs, acc, wm, wn, lane);
@@ -249,6 +320,13 @@ __global__ __launch_bounds__(256) void dnn_wgrad_fold_kernel(const float *__rest
     dw[idx] = acc;
 }
 
+template <int FORM>
+void launch_fprop_form(int tm, dim3 grid, dim3 block, const ConvArgs &a) {
+    if (tm == kTMSmall) dnn_fprop_kernel<kTMSmall, FORM><<<grid, block, 0, np::stream()>>>(a);
+    else if (tm == kTMMid) dnn_fprop_kernel<kTMMid, FORM><<<grid, block, 0, np::stream()>>>(a);
+    else dnn_fprop_kernel<kTMLarge, FORM><<<grid, block, 0, np::stream()>>>(a);
+}
+
 int pick_tm(size_t F) { return F <= (size_t)kTMSmall ? kTMSmall : F <= (size_t)kTMMid ? kTMMid : kTMLarge; }
 
 constexpr size_t kLim = (size_t)1 << 31;
@@ -275,6 +353,75 @@ int check_layer(const char *who, size_t N, size_t C, size_t H, size_t W, size_t 
         return np::fail(NP_ERR_INVALID, "%s: an operand, the result, N.P or the reduction length has 2^31 elements or more", who);
     a.N = (int)N, a.C = (int)C, a.H = (int)H, a.W = (int)W, a.F = (int)F, a.kh = (int)kh, a.kw = (int)kw, a.ph = (int)ph, a.pw = (int)pw;
     a.oh = (int)oh, a.ow = (int)ow, a.K = (int)K, a.P = (int)P, a.NP = (int)NP;
+    a.sh = a.sw = a.dh = a.dw = a.lh = a.lw = 1;
+    return NP_OK;
+}
+
+// the _ex shape: stride (sh, sw), dilation (dh, dw); -> the effective window and the output extents
+int check_spatial_ex(const char *who, size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw,
+                     size_t &keh, size_t &kew, size_t &oh, size_t &ow) {
+    if (H < 1 || W < 1 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1)
+        return np::fail(NP_ERR_INVALID, "%s: every extent, stride and dilation must be at least 1", who);
+    keh = mul_lim(dh, kh - 1) + 1, kew = mul_lim(dw, kw - 1) + 1;
+    if (H >= kLim || W >= kLim || kh >= kLim || kw >= kLim || sh >= kLim || sw >= kLim || keh >= kLim || kew >= kLim)
+        return np::fail(NP_ERR_INVALID, "%s: an extent, a stride or an effective window is 2^31 or more", who);
+    if (ph >= keh || pw >= kew)
+        return np::fail(NP_ERR_INVALID, "%s: the padding (%zu, %zu) must be smaller than the effective window (%zu, %zu)", who, ph, pw, keh, kew);
+    if (keh > H + 2 * ph || kew > W + 2 * pw)
+        return np::fail(NP_ERR_INVALID, "%s: the effective window (%zu, %zu) is larger than the padded image (%zu, %zu)", who, keh, kew, H + 2 * ph,
+                        W + 2 * pw);
+    if (H + 2 * ph >= kLim || W + 2 * pw >= kLim) return np::fail(NP_ERR_INVALID, "%s: a padded extent is 2^31 or more", who);
+    oh = (H + 2 * ph - keh) / sh + 1;
+    ow = (W + 2 * pw - kew) / sw + 1;
+    return NP_OK;
+}
+
+int check_layer_ex(const char *who, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw, size_t ph, size_t pw, size_t sh,
+                   size_t sw, size_t dh, size_t dw, ConvArgs &a) {
+    if (N < 1 || C < 1 || F < 1) return np::fail(NP_ERR_INVALID, "%s: every extent, stride and dilation must be at least 1", who);
+    size_t keh, kew, oh, ow;
+    if (int rc = check_spatial_ex(who, H, W, kh, kw, ph, pw, sh, sw, dh, dw, keh, kew, oh, ow)) return rc;
+    const size_t P = mul_lim(oh, ow), numel_x = mul_lim(mul_lim(N, C), mul_lim(H, W)), numel_w = mul_lim(mul_lim(F, C), mul_lim(kh, kw));
+    const size_t numel_y = mul_lim(mul_lim(N, F), P), NP = mul_lim(N, P), K = mul_lim(C, mul_lim(kh, kw)), Kt = mul_lim(F, mul_lim(kh, kw));
+    if (numel_x >= kLim || numel_w >= kLim || numel_y >= kLim || NP >= kLim || K >= kLim || Kt >= kLim)
+        return np::fail(NP_ERR_INVALID, "%s: an operand, the result, N.P or the reduction length has 2^31 elements or more", who);
+    a.N = (int)N, a.C = (int)C, a.H = (int)H, a.W = (int)W, a.F = (int)F, a.kh = (int)kh, a.kw = (int)kw, a.ph = (int)ph, a.pw = (int)pw;
+    a.oh = (int)oh, a.ow = (int)ow, a.K = (int)K, a.P = (int)P, a.NP = (int)NP;
+    a.sh = (int)sh, a.sw = (int)sw, a.dh = (int)dh, a.dw = (int)dw, a.lh = a.lw = 1;
+    return NP_OK;
+}
+
+// the data gradient of layer l as a forward layer over dy: F channels of oh x ow in, dilated by the stride; C channels of H x W
+// out; taps dilated as the layer's, pad (keh - 1 - ph, kew - 1 - pw), stride 1
+ConvArgs dgrad_layer(const ConvArgs &l, const float *dy, const float *flipped, float *dx) {
+    ConvArgs a = {};
+    a.x = dy;
+    a.w = flipped;
+    a.out = dx;
+    a.N = l.N, a.C = l.F, a.H = l.oh, a.W = l.ow, a.F = l.C, a.kh = l.kh, a.kw = l.kw;
+    a.ph = l.dh * (l.kh - 1) - l.ph, a.pw = l.dw * (l.kw - 1) - l.pw;
+    a.oh = l.H, a.ow = l.W, a.K = l.F * l.kh * l.kw, a.P = l.H * l.W, a.NP = l.N * a.P;
+    a.sh = a.sw = 1, a.dh = l.dh, a.dw = l.dw, a.lh = l.sh, a.lw = l.sw;
+    return a;
+}
+
+// dW's launch shape, from the extents alone: slices of at least kWgradMinSteps steps until tiles x S fills the device
+struct WgradPlan {
+    int tm;
+    size_t tiles, steps_per_slice, slices;
+};
+
+int plan_wgrad(const char *who, const ConvArgs &a, WgradPlan &pl) {
+    pl.tm = pick_tm((size_t)a.F);
+    pl.tiles = (((size_t)a.F + pl.tm - 1) / pl.tm) * (((size_t)a.K + kTN - 1) / kTN);
+    if (pl.tiles >= kLim) return np::fail(NP_ERR_INVALID, "%s: %zu tiles are more than one launch holds", who, pl.tiles);
+    const size_t steps = ((size_t)a.NP + kTK - 1) / kTK;
+    size_t want = steps / kWgradMinSteps, fill = (kWgradTargetGroups + pl.tiles - 1) / pl.tiles;
+    if (want > fill) want = fill;
+    if (want > (size_t)kWgradMaxSlices) want = kWgradMaxSlices;
+    if (want < 1) want = 1;
+    pl.steps_per_slice = (steps + want - 1) / want;
+    pl.slices = (steps + pl.steps_per_slice - 1) / pl.steps_per_slice;
     return NP_OK;
 }
 
@@ -283,12 +430,49 @@ int launch_fprop(const ConvArgs &a) {
     const size_t tiles = (((size_t)a.F + tm - 1) / tm) * (((size_t)a.NP + kTN - 1) / kTN);
     if (tiles >= kLim) return np::fail(NP_ERR_INVALID, "np_conv2d: %zu tiles are more than one launch holds", tiles);
     const dim3 grid((unsigned)tiles), block(256);
-    if (tm == kTMSmall) dnn_fprop_kernel<kTMSmall><<<grid, block, 0, np::stream()>>>(a);
-    else if (tm == kTMMid) dnn_fprop_kernel<kTMMid><<<grid, block, 0, np::stream()>>>(a);
-    else dnn_fprop_kernel<kTMLarge><<<grid, block, 0, np::stream()>>>(a);
+    const int form = form_of(a);
+    if (form == 0) launch_fprop_form<0>(tm, grid, block, a);
+    else if (form == 1) launch_fprop_form<1>(tm, grid, block, a);
+    else launch_fprop_form<2>(tm, grid, block, a);
     NP_LAUNCH_CHECK("dnn_fprop_kernel");
     g_dnn_last_tm = tm;
     g_dnn_last_slices = 0;
+    g_dnn_last_form = form;
+    return NP_OK;
+}
+
+template <int FORM>
+void launch_wgrad_form(int tm, dim3 grid, dim3 block, const ConvArgs &a, int steps_per_slice) {
+    if (tm == kTMSmall) dnn_wgrad_kernel<kTMSmall, FORM><<<grid, block, 0, np::stream()>>>(a, steps_per_slice);
+    else if (tm == kTMMid) dnn_wgrad_kernel<kTMMid, FORM><<<grid, block, 0, np::stream()>>>(a, steps_per_slice);
+    else dnn_wgrad_kernel<kTMLarge, FORM><<<grid, block, 0, np::stream()>>>(a, steps_per_slice);
+}
+
+// a.out is dw (one slice) or the slices' scratch `part`, which is then folded into dw
+int launch_wgrad(const ConvArgs &a, const WgradPlan &pl, const float *part, float *dw) {
+    const dim3 grid((unsigned)pl.tiles, (unsigned)pl.slices), block(256);
+    const int form = form_of(a);
+    if (form == 0) launch_wgrad_form<0>(pl.tm, grid, block, a, (int)pl.steps_per_slice);
+    else launch_wgrad_form<1>(pl.tm, grid, block, a, (int)pl.steps_per_slice);
+    NP_LAUNCH_CHECK("dnn_wgrad_kernel");
+    if (pl.slices > 1) {
+        const size_t numel_w = (size_t)a.F * a.K;
+        dnn_wgrad_fold_kernel<<<dim3((unsigned)((numel_w + 255) / 256)), dim3(256), 0, np::stream()>>>(part, dw, (unsigned)numel_w, (int)pl.slices);
+        NP_LAUNCH_CHECK("dnn_wgrad_fold_kernel");
+    }
+    g_dnn_last_tm = pl.tm;
+    g_dnn_last_slices = (int)pl.slices;
+    g_dnn_last_form = form;
+    return NP_OK;
+}
+
+// w' of layer l into pool scratch
+int flip_filters(const ConvArgs &l, const float *w, np::Scratch &flipped) {
+    const size_t numel_w = (size_t)l.F * l.K;
+    if (int rc = flipped.alloc(numel_w * sizeof(float))) return rc;
+    dnn_filter_flip_kernel<<<dim3((unsigned)((numel_w + 255) / 256)), dim3(256), 0, np::stream()>>>(w, (float *)flipped.ptr, l.F, l.C, l.kh, l.kw,
+                                                                                                   (unsigned)numel_w);
+    NP_LAUNCH_CHECK("dnn_filter_flip_kernel");
     return NP_OK;
 }
 
@@ -323,20 +507,9 @@ int np_conv2d_backward_data(const float *dy, const float *w, size_t N, size_t C,
     ConvArgs l = {};
     if (int rc = check_layer("np_conv2d_backward_data", N, C, H, W, F, kh, kw, ph, pw, l)) return rc;
     if (int rc = np::ensure_init()) return rc;
-    const size_t numel_w = (size_t)l.F * l.K;
     np::Scratch flipped;   // released on every path below
-    if (int rc = flipped.alloc(numel_w * sizeof(float))) return rc;
-    dnn_filter_flip_kernel<<<dim3((unsigned)((numel_w + 255) / 256)), dim3(256), 0, np::stream()>>>(w, (float *)flipped.ptr, l.F, l.C, l.kh, l.kw,
-                                                                                                   (unsigned)numel_w);
-    NP_LAUNCH_CHECK("dnn_filter_flip_kernel");
-    // the forward layer of dy: F channels of oh x ow in, C channels out, pad (kh - 1 - ph, kw - 1 - pw); its result is H x W
-    ConvArgs a = {};
-    a.x = dy;
-    a.w = (const float *)flipped.ptr;
-    a.out = dx;
-    a.N = l.N, a.C = l.F, a.H = l.oh, a.W = l.ow, a.F = l.C, a.kh = l.kh, a.kw = l.kw, a.ph = l.kh - 1 - l.ph, a.pw = l.kw - 1 - l.pw;
-    a.oh = l.H, a.ow = l.W, a.K = l.F * l.kh * l.kw, a.P = l.H * l.W, a.NP = l.N * a.P;
-    return launch_fprop(a);
+    if (int rc = flip_filters(l, w, flipped)) return rc;
+    return launch_fprop(dgrad_layer(l, dy, (const float *)flipped.ptr, dx));
 }
 
 int np_conv2d_backward_filter(const float *x, const float *dy, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
@@ -345,36 +518,15 @@ int np_conv2d_backward_filter(const float *x, const float *dy, size_t N, size_t 
     ConvArgs a = {};
     if (int rc = check_layer("np_conv2d_backward_filter", N, C, H, W, F, kh, kw, ph, pw, a)) return rc;
     if (int rc = np::ensure_init()) return rc;
-    const int tm = pick_tm((size_t)a.F);
-    const size_t tiles = (((size_t)a.F + tm - 1) / tm) * (((size_t)a.K + kTN - 1) / kTN);
-    if (tiles >= kLim) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_filter: %zu tiles are more than one launch holds", tiles);
-    // S from the extents alone: slices of at least kWgradMinSteps steps until tiles x S fills the device
-    const size_t steps = ((size_t)a.NP + kTK - 1) / kTK;
-    size_t want = steps / kWgradMinSteps, fill = (kWgradTargetGroups + tiles - 1) / tiles;
-    if (want > fill) want = fill;
-    if (want > (size_t)kWgradMaxSlices) want = kWgradMaxSlices;
-    if (want < 1) want = 1;
-    const size_t steps_per_slice = (steps + want - 1) / want, slices = (steps + steps_per_slice - 1) / steps_per_slice;
-    const size_t numel_w = (size_t)a.F * a.K;
+    WgradPlan pl;
+    if (int rc = plan_wgrad("np_conv2d_backward_filter", a, pl)) return rc;
     np::Scratch part;   // released on every path below
-    if (slices > 1)
-        if (int rc = part.alloc(slices * numel_w * sizeof(float))) return rc;
+    if (pl.slices > 1)
+        if (int rc = part.alloc(pl.slices * (size_t)a.F * a.K * sizeof(float))) return rc;
     a.x = x;
     a.w = dy;
-    a.out = slices > 1 ? (float *)part.ptr : dw;
-    const dim3 grid((unsigned)tiles, (unsigned)slices), block(256);
-    if (tm == kTMSmall) dnn_wgrad_kernel<kTMSmall><<<grid, block, 0, np::stream()>>>(a, (int)steps_per_slice);
-    else if (tm == kTMMid) dnn_wgrad_kernel<kTMMid><<<grid, block, 0, np::stream()>>>(a, (int)steps_per_slice);
-    else dnn_wgrad_kernel<kTMLarge><<<grid, block, 0, np::stream()>>>(a, (int)steps_per_slice);
-    NP_LAUNCH_CHECK("dnn_wgrad_kernel");
-    if (slices > 1) {
-        dnn_wgrad_fold_kernel<<<dim3((unsigned)((numel_w + 255) / 256)), dim3(256), 0, np::stream()>>>((const float *)part.ptr, dw, (unsigned)numel_w,
-                                                                                                      (int)slices);
-        NP_LAUNCH_CHECK("dnn_wgrad_fold_kernel");
-    }
-    g_dnn_last_tm = tm;
-    g_dnn_last_slices = (int)slices;
-    return NP_OK;
+    a.out = pl.slices > 1 ? (float *)part.ptr : dw;
+    return launch_wgrad(a, pl, (const float *)part.ptr, dw);
 }
 
 int np_debug_dnn_last_path(int *host_tm, int *host_slices) {
@@ -382,6 +534,62 @@ int np_debug_dnn_last_path(int *host_tm, int *host_slices) {
     *host_tm = g_dnn_last_tm;
     *host_slices = g_dnn_last_slices;
     return NP_OK;
+}
+
+int np_debug_dnn_last_form(int *host_form) {
+    if (!host_form) return np::fail(NP_ERR_INVALID, "np_debug_dnn_last_form: null pointer");
+    *host_form = g_dnn_last_form;
+    return NP_OK;
+}
+
+int np_conv2d_shape_ex(size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, size_t *oh,
+                       size_t *ow) {
+    if (!oh || !ow) return np::fail(NP_ERR_INVALID, "np_conv2d_shape_ex: null pointer");
+    size_t keh, kew, h, w;
+    if (int rc = check_spatial_ex("np_conv2d_shape_ex", H, W, kh, kw, ph, pw, sh, sw, dh, dw, keh, kew, h, w)) return rc;
+    *oh = h;
+    *ow = w;
+    return NP_OK;
+}
+
+int np_conv2d_forward_ex(const float *x, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw, size_t ph,
+                         size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, float *y) {
+    if (!x || !w || !y) return np::fail(NP_ERR_INVALID, "np_conv2d_forward_ex: null pointer");
+    ConvArgs a = {};
+    if (int rc = check_layer_ex("np_conv2d_forward_ex", N, C, H, W, F, kh, kw, ph, pw, sh, sw, dh, dw, a)) return rc;
+    if (int rc = np::ensure_init()) return rc;
+    a.x = x;
+    a.w = w;
+    a.out = y;
+    return launch_fprop(a);
+}
+
+int np_conv2d_backward_data_ex(const float *dy, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
+                               size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, float *dx) {
+    if (!dy || !w || !dx) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_data_ex: null pointer");
+    ConvArgs l = {};
+    if (int rc = check_layer_ex("np_conv2d_backward_data_ex", N, C, H, W, F, kh, kw, ph, pw, sh, sw, dh, dw, l)) return rc;
+    if (int rc = np::ensure_init()) return rc;
+    np::Scratch flipped;   // released on every path below
+    if (int rc = flip_filters(l, w, flipped)) return rc;
+    return launch_fprop(dgrad_layer(l, dy, (const float *)flipped.ptr, dx));
+}
+
+int np_conv2d_backward_filter_ex(const float *x, const float *dy, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
+                                 size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, float *dw_out) {
+    if (!x || !dy || !dw_out) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_filter_ex: null pointer");
+    ConvArgs a = {};
+    if (int rc = check_layer_ex("np_conv2d_backward_filter_ex", N, C, H, W, F, kh, kw, ph, pw, sh, sw, dh, dw, a)) return rc;
+    if (int rc = np::ensure_init()) return rc;
+    WgradPlan pl;
+    if (int rc = plan_wgrad("np_conv2d_backward_filter_ex", a, pl)) return rc;
+    np::Scratch part;   // released on every path below
+    if (pl.slices > 1)
+        if (int rc = part.alloc(pl.slices * (size_t)a.F * a.K * sizeof(float))) return rc;
+    a.x = x;
+    a.w = dy;
+    a.out = pl.slices > 1 ? (float *)part.ptr : dw_out;
+    return launch_wgrad(a, pl, (const float *)part.ptr, dw_out);
 }
 
 }  // extern "C"

@@ -44,4 +44,26 @@ NDArray **NDArrayDNN_Conv2D_Backward(NDArray *input, NDArray *y, NDArray *filter
     return cf.arr ? NPH_Conv2D_Backward(cx.arr, cy.arr, cf.arr) : nullptr;
 }
 
+// The same layer with a stride, a padding and a dilation ((rows, columns) each, nullptr: 1, 0, 1): what the reference's layer
+// signature names (dnn.c:196-200) and its functions cannot express.
+NDArray *NDArrayDNN_Conv2D_ForwardEx(NDArray *x, NDArray *filters, const int *stride, const int *padding, const int *dilation) {
+    if (!x || !filters) return nullptr;
+    if (!on_gpu(x) || !on_gpu(filters)) return NPH_Conv2D_ForwardEx(x, filters, stride, padding, dilation);
+    Operand cx(x);
+    if (!cx.arr) return nullptr;
+    Operand cf(filters);
+    return cf.arr ? NPH_Conv2D_ForwardEx(cx.arr, cf.arr, stride, padding, dilation) : nullptr;
+}
+
+NDArray **NDArrayDNN_Conv2D_BackwardEx(NDArray *input, NDArray *y, NDArray *filters, const int *stride, const int *padding, const int *dilation) {
+    if (!input || !y || !filters) return nullptr;
+    if (!on_gpu(input) || !on_gpu(y) || !on_gpu(filters)) return NPH_Conv2D_BackwardEx(input, y, filters, stride, padding, dilation);
+    Operand cx(input);
+    if (!cx.arr) return nullptr;
+    Operand cy(y);
+    if (!cy.arr) return nullptr;
+    Operand cf(filters);
+    return cf.arr ? NPH_Conv2D_BackwardEx(cx.arr, cy.arr, cf.arr, stride, padding, dilation) : nullptr;
+}
+
 }  // extern "C"

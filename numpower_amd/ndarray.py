@@ -155,6 +155,8 @@ def _load_host():
     sig["NDArray_Correlate2D"] = (_P, [_P, _P, C.c_int, C.c_int, _P, C.c_int])
     sig["NDArrayDNN_Conv2D_Forward"] = (_P, [_P, _P, ip, C.c_char, C.c_int])
     sig["NDArrayDNN_Conv2D_Backward"] = (C.POINTER(_P), [_P, _P, _P, C.c_int, C.c_char, C.c_int])
+    sig["NDArrayDNN_Conv2D_ForwardEx"] = (_P, [_P, _P, ip, ip, ip])
+    sig["NDArrayDNN_Conv2D_BackwardEx"] = (C.POINTER(_P), [_P, _P, _P, ip, ip, ip])
     sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
     sig["NDArray_Eig"] = (C.POINTER(_P), [_P])
     sig["NDArray_Qr"] = (C.POINTER(_P), [_P])
@@ -851,22 +853,62 @@ class NDArray:
         return NDArray._signal2d(a, b, mode, boundary, fill_value, 0)
 
     @staticmethod
-    def dnn_conv2d_forward(x, filters):   # numpower.c:4293: NDArrayDNN_Conv2D_Forward(x, filters, NULL, 'r', 1)
-        """y (N, F, H - kh + 1, W - kw + 1) of x (N, C, H, W) and filters (F, C, kh, kw): cross-correlation, stride 1, no padding,
-        no bias, no activation."""
-        h = _load_host()
-        a, _ = NDArray._coerce(x)
-        w, _ = NDArray._coerce(filters)
-        return NDArray._wrap(h.NDArrayDNN_Conv2D_Forward(a._p, w._p, None, b"r", 1))
+    def _dnn_geometry(filters, stride, padding, dilation):
+        """-> None for the defaults (the reference-signature host functions), else three C int pairs (stride, padding, dilation)"""
+        def pair(v, what):
+            if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
+                return int(v), int(v)
+            if isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(e, (int, np.integer)) and not isinstance(e, bool) for e in v):
+                return int(v[0]), int(v[1])
+            raise Error("dnn_conv2d: %s must be an int or a pair of ints" % what)
+
+        s, d = pair(stride, "stride"), pair(dilation, "dilation")
+        if isinstance(padding, str):
+            if padding not in ("valid", "same"):
+                raise Error("dnn_conv2d: padding must be an int, a pair of ints, 'valid' or 'same'")
+            if padding == "valid":
+                p = (0, 0)
+            else:
+                shape = tuple(np.shape(filters)) if not isinstance(filters, NDArray) else tuple(filters.shape())
+                if len(shape) != 4:
+                    raise Error("dnn_conv2d: padding 'same' needs 4-dimensional filters (F, C, kh, kw)")
+                ke = tuple(d[i] * (shape[2 + i] - 1) + 1 for i in range(2))
+                if s != (1, 1) or min(d) < 1 or ke[0] % 2 == 0 or ke[1] % 2 == 0:
+                    raise Error("dnn_conv2d: padding 'same' needs stride 1 and an odd effective window, dilation . (k - 1) + 1, along both axes")
+                p = ((ke[0] - 1) // 2, (ke[1] - 1) // 2)
+        else:
+            p = pair(padding, "padding")
+        if (s, p, d) == ((1, 1), (0, 0), (1, 1)):
+            return None
+        return tuple((C.c_int * 2)(*v) for v in (s, p, d))
 
     @staticmethod
-    def dnn_conv2d_backward(x, y, filters):   # numpower.c:4348: NDArrayDNN_Conv2D_Backward(x, y, filters, 3, 'r', 1) -> RETURN_2NDARRAY
-        """(dW (F, C, kh, kw), dX (N, C, H, W)) for y = the gradient of dnn_conv2d_forward(x, filters), the reference's order."""
+    def dnn_conv2d_forward(x, filters, stride=1, padding=0, dilation=1):   # numpower.c:4293: NDArrayDNN_Conv2D_Forward(x, filters, NULL, 'r', 1)
+        """y (N, F, oh, ow) of x (N, C, H, W) and filters (F, C, kh, kw): cross-correlation, no bias, no activation (DESIGN.md
+        §3.14).  stride, padding and dilation take an int or a (rows, columns) pair; padding also 'valid' (0) and 'same'
+        ((keh - 1) / 2 of the effective window keh = dilation . (kh - 1) + 1, for stride 1 and odd keh, kew).
+        oh = floor((H + 2 ph - keh) / sh) + 1.  With the defaults: the reference's call, y (N, F, H - kh + 1, W - kw + 1)."""
         h = _load_host()
+        geometry = NDArray._dnn_geometry(filters, stride, padding, dilation)
+        a, _ = NDArray._coerce(x)
+        w, _ = NDArray._coerce(filters)
+        if geometry is None:
+            return NDArray._wrap(h.NDArrayDNN_Conv2D_Forward(a._p, w._p, None, b"r", 1))
+        return NDArray._wrap(h.NDArrayDNN_Conv2D_ForwardEx(a._p, w._p, *geometry))
+
+    @staticmethod
+    def dnn_conv2d_backward(x, y, filters, stride=1, padding=0, dilation=1):   # numpower.c:4348: NDArrayDNN_Conv2D_Backward(x, y, filters, 3, 'r', 1) -> RETURN_2NDARRAY
+        """(dW (F, C, kh, kw), dX (N, C, H, W)) for y = the gradient of dnn_conv2d_forward(x, filters, stride, padding, dilation),
+        the reference's order.  Rows and columns of x that no window reads get dX = 0."""
+        h = _load_host()
+        geometry = NDArray._dnn_geometry(filters, stride, padding, dilation)
         a, _ = NDArray._coerce(x)
         g, _ = NDArray._coerce(y)
         w, _ = NDArray._coerce(filters)
-        rtns = h.NDArrayDNN_Conv2D_Backward(a._p, g._p, w._p, 3, b"r", 1)
+        if geometry is None:
+            rtns = h.NDArrayDNN_Conv2D_Backward(a._p, g._p, w._p, 3, b"r", 1)
+        else:
+            rtns = h.NDArrayDNN_Conv2D_BackwardEx(a._p, g._p, w._p, *geometry)
         if not rtns:
             _raise_pending(h)
         out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(2))

@@ -6,6 +6,11 @@ implicit GEMM: forward F x N.P x C.kh.kw, dX C x N.H.W x F.kh.kw, dW F x C.kh.kw
 (M, N, K) in the same run with the ratio gemm / conv: the ceiling the project's own GEMM sets for those extents.  The 1 x 1 layer
 is a GEMM with no gather: a ratio far below 1 THERE is a tile-loop problem, not a gather problem.
 
+Layers with a stride or a dilation (a fifth entry (sh, sw, dh, dw)) go through the _ex entry points; the others through the
+calls they always went through.  Their TFLOP/s count the USEFUL 2 M N K: dX of a strided layer is counted as C x N.P x F.kh.kw,
+the multiply-adds that meet a gradient, while the dilated-input kernel computes C x N.H.W x F.kh.kw, about sh.sw times as many,
+over stored zeros; the last column is the form of the gather (np_debug_dnn_last_form).
+
 Every layer runs in a child process of its own under its own time limit (--limit seconds); the sweep stops at the first
 layer that fails or runs out of time.  --torch adds, as information, torch.nn.functional.conv2d and its autograd on the device
 where this installation runs them (one more child); if it does not, the log says so in one line.
@@ -26,7 +31,12 @@ LAYERS = [("3x3 64->64 at 56^2, batch 32", (32, 64, 56, 56), (64, 3, 3), (1, 1))
           ("3x3 128->128 at 28^2, batch 32", (32, 128, 28, 28), (128, 3, 3), (1, 1)),
           ("1x1 256->64 at 56^2, batch 32", (32, 256, 56, 56), (64, 1, 1), (0, 0)),
           ("7x7 3->64 at 224^2 pad 3, batch 8", (8, 3, 224, 224), (64, 7, 7), (3, 3)),
-          ("5x5 1->32 at 28^2, batch 512", (512, 1, 28, 28), (32, 5, 5), (0, 0))]
+          ("5x5 1->32 at 28^2, batch 512", (512, 1, 28, 28), (32, 5, 5), (0, 0)),
+          # name, (N, C, H, W), (F, kh, kw), (ph, pw), (sh, sw, dh, dw)
+          ("3x3/2 64->128 at 56^2 pad 1, batch 32", (32, 64, 56, 56), (128, 3, 3), (1, 1), (2, 2, 1, 1)),
+          ("7x7/2 3->64 at 224^2 pad 3, batch 8", (8, 3, 224, 224), (64, 7, 7), (3, 3), (2, 2, 1, 1)),
+          ("1x1/2 256->512 at 56^2, batch 32", (32, 256, 56, 56), (512, 1, 1), (0, 0), (2, 2, 1, 1)),
+          ("3x3 dil 2 128->128 at 28^2 pad 2, batch 32", (32, 128, 28, 28), (128, 3, 3), (2, 2), (1, 1, 2, 2))]
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--layers", default=",".join(str(i) for i in range(len(LAYERS))))
@@ -40,10 +50,16 @@ args = ap.parse_args()
 
 
 def shapes(i):
-    _, (N, C, H, W), (F, kh, kw), (ph, pw) = LAYERS[i]
-    oh, ow = H + 2 * ph - kh + 1, W + 2 * pw - kw + 1
-    gemms = {"forward": (F, N * oh * ow, C * kh * kw), "dX": (C, N * H * W, F * kh * kw), "dW": (F, C * kh * kw, N * oh * ow)}
+    _, (N, C, H, W), (F, kh, kw), (ph, pw) = LAYERS[i][:4]
+    sh, sw, dh, dw = geometry(i)
+    oh, ow = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    useful_dx = N * H * W if (sh, sw) == (1, 1) else N * oh * ow      # the pixels whose products meet a gradient
+    gemms = {"forward": (F, N * oh * ow, C * kh * kw), "dX": (C, useful_dx, F * kh * kw), "dW": (F, C * kh * kw, N * oh * ow)}
     return (N, C, H, W), (F, C, kh, kw), (N, F, oh, ow), (ph, pw), gemms
+
+
+def geometry(i):
+    return LAYERS[i][4] if len(LAYERS[i]) > 4 else (1, 1, 1, 1)
 
 
 def run_layer(i, rounds, profile=False):
@@ -63,6 +79,11 @@ def run_layer(i, rounds, profile=False):
     ops = {"forward": lambda: check(lib.np_conv2d_forward(x.ptr, w.ptr, *dims, y.ptr)),
            "dX": lambda: check(lib.np_conv2d_backward_data(dy.ptr, w.ptr, *dims, dx.ptr)),
            "dW": lambda: check(lib.np_conv2d_backward_filter(x.ptr, dy.ptr, *dims, dw.ptr))}
+    if len(LAYERS[i]) > 4:
+        dims += geometry(i)
+        ops = {"forward": lambda: check(lib.np_conv2d_forward_ex(x.ptr, w.ptr, *dims, y.ptr)),
+               "dX": lambda: check(lib.np_conv2d_backward_data_ex(dy.ptr, w.ptr, *dims, dx.ptr)),
+               "dW": lambda: check(lib.np_conv2d_backward_filter_ex(x.ptr, dy.ptr, *dims, dw.ptr))}
     if profile:
         for _ in range(3):
             for fn in ops.values():
@@ -97,12 +118,14 @@ def run_layer(i, rounds, profile=False):
         M, N, K = gemms[name]
         a, b, c = dev((M, K)), dev((K, N)), D.DeviceArray((M, N))
         conv_ms = median_ms(fn)
-        tm, s = C_.c_int(), C_.c_int()
+        tm, s, form = C_.c_int(), C_.c_int(), C_.c_int()
         check(lib.np_debug_dnn_last_path(C_.byref(tm), C_.byref(s)))
+        check(lib.np_debug_dnn_last_form(C_.byref(form)))
         gemm_ms = median_ms(lambda: check(lib.np_sgemm(M, N, K, a.ptr, b.ptr, c.ptr)))
         flop = 2.0 * M * N * K
-        print("%-34s %-8s %6d %9d %7d %9.4f %8.2f %9.4f %8.2f %7.3f %4d %4d" % (LAYERS[i][0], name, M, N, K, conv_ms, flop / conv_ms * 1e-9, gemm_ms,
-                                                                            flop / gemm_ms * 1e-9, gemm_ms / conv_ms, tm.value, s.value), flush=True)
+        print("%-42s %-8s %6d %9d %7d %9.4f %8.2f %9.4f %8.2f %7.3f %4d %4d %4d" % (LAYERS[i][0], name, M, N, K, conv_ms, flop / conv_ms * 1e-9, gemm_ms,
+                                                                                flop / gemm_ms * 1e-9, gemm_ms / conv_ms, tm.value, s.value, form.value),
+              flush=True)
         for d in (a, b, c):
             d.free()
 
@@ -131,13 +154,14 @@ def run_torch(layers, rounds):
                 out.append((time.time() - t0) / 5 * 1e3)
             return statistics.median(out)
 
-        fwd = ms(lambda: torch.nn.functional.conv2d(x.detach(), w.detach(), padding=pad))
+        sh, sw, dh, dw = geometry(i)
+        fwd = ms(lambda: torch.nn.functional.conv2d(x.detach(), w.detach(), padding=pad, stride=(sh, sw), dilation=(dh, dw)))
 
         def both():
             x.grad = w.grad = None
-            torch.nn.functional.conv2d(x, w, padding=pad).backward(dy)
+            torch.nn.functional.conv2d(x, w, padding=pad, stride=(sh, sw), dilation=(dh, dw)).backward(dy)
 
-        print("%-34s torch (information): forward %.4f ms, forward + both gradients %.4f ms" % (LAYERS[i][0], fwd, ms(both)), flush=True)
+        print("%-42s torch (information): forward %.4f ms, forward + both gradients %.4f ms" % (LAYERS[i][0], fwd, ms(both)), flush=True)
 
 
 if args.profile is not None:
@@ -174,7 +198,8 @@ def child(what):
 
 
 say("np_conv2d_forward / _backward_data / _backward_filter, fp32, median of %d rounds; gemm = np_sgemm on dense operands of the same M, N, K" % args.rounds)
-say("%-34s %-8s %6s %9s %7s %9s %8s %9s %8s %7s %4s %4s" % ("layer", "op", "M", "N", "K", "conv ms", "TFLOP/s", "gemm ms", "TFLOP/s", "gemm/conv", "TM", "S"))
+say("%-42s %-8s %6s %9s %7s %9s %8s %9s %8s %7s %4s %4s %4s" % ("layer", "op", "M", "N", "K", "conv ms", "TFLOP/s", "gemm ms", "TFLOP/s", "gemm/conv", "TM", "S",
+                                                                  "form"))
 ok = True
 for i in (int(s) for s in args.layers.split(",")):
     ok = child("layer:%d" % i)
