@@ -110,7 +110,20 @@ inline size_t capped_grid(size_t wanted, size_t cap) {
     if (wanted <= cap) return wanted < 1 ? 1 : wanted;
     return cap | 1;
 }
-// One-block fold of per-workgroup partials into one device float (np_reduce.hip); op = NP_SUM / PROD / MIN / MAX.
+// Workgroups per CU of the streaming reductions' first pass (np_reduce.hip, np_stats.hip; np_reduce_set_variant; tools/reduce_cap_ab.py).
+// One partial per workgroup, so more workgroups = more partials for the one-block second pass to fold.
+extern int g_wg_per_cu;   // 0 = the default below
+constexpr int kStreamWgPerCu = 8;
+inline size_t stream_cap() {
+    if (g_wg_per_cu >= 1000) return (size_t)g_wg_per_cu;   // tuning: an exact workgroup count
+    return (size_t)num_cus() * (size_t)(g_wg_per_cu > 0 ? g_wg_per_cu : kStreamWgPerCu);
+}
+// Further knobs of np_reduce_set_variant (np_reduce.hip) that np_argreduce.hip reads
+extern int g_xcd_runs_off;         // reduce_axis_cols / argreduce_cols_tile on unaligned rows: 1 = the plain workgroup order (4200001: A/B)
+extern int g_arg_flat_wg_per_cu;   // the flat walks for a few columns: workgroups per CU, 0 = by shape (4100000 + N: A/B)
+extern int g_arg_cols_wg_per_cu;   // argreduce_cols_tile: workgroups per CU the axis is cut for; 0 = by alignment (4000000 + N: A/B)
+// One-block fold of per-workgroup partials into one device float (np_reduce.hip; the second pass of np_stats.hip and of the
+// fused chains too); op = NP_SUM / PROD / MIN / MAX.
 int fold_partials(int op, const float *partials, size_t n, float *dev_out);
 // Batched GEMM in one launch with per-piece progress counters (np_sgemm.hip; used by np_comm.hip's overlapped pipeline).
 int sgemm_batched_with_progress(size_t batch, size_t M, size_t N, size_t K, const float *A, size_t stride_a, const float *B,
@@ -165,7 +178,7 @@ bool comm_transfers_stuck(int device, double grace_s);
 
 }  // namespace np
 
-// ---- device-side reduction helpers shared by np_reduce.hip and the fused chain kernel ----
+// ---- device-side reduction helpers shared by np_reduce.hip, np_stats.hip and the fused chain kernel ----
 namespace np {
 namespace dev {
 

@@ -412,6 +412,10 @@ int check_device_error(const char *who) {
 
 size_t g_small_reduce_blocks = 128;   // np_internal.h
 size_t g_fold_in_kernel_max = 256;
+int g_wg_per_cu = 0;
+int g_xcd_runs_off = 0;
+int g_arg_flat_wg_per_cu = 0;
+int g_arg_cols_wg_per_cu = 0;
 unsigned *next_ticket() { return next_tickets(1); }
 
 // `count` consecutive tickets (count <= kTicketRing / 4): a run that would cross the end of the ring starts over at slot 0

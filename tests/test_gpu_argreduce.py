@@ -88,7 +88,8 @@ def test_argmax_1e8(hip):
                                         ((2000, 1003), 0), ((5, 40_000, 7), 1), ((70_000, 1), 0), ((2, 3, 50_000), 2)])
 def test_argreduce_few_outputs_long_axis(shape, axis, hip, oracle):
     """Shapes where one thread per output would idle the chip: the axis is cut into chunks whose
-    (value, index) partials are folded (argreduce_chunks_kernel / vectorised argreduce_rows_kernel).
+    (value, index) partials are folded (the flat walks for a few columns, argreduce_cols_tile for (2000, 1003), the
+    vectorised argreduce_rows_kernel; argreduce_chunks_kernel is met by test_argreduce_streaming_forms).
     First-occurrence ties and the NaN rules must survive the chunk boundaries."""
     from numpower_amd.ndarray import NDArray
     x = synth.uniform(shape, 51, -1.0, 1.0)
@@ -129,6 +130,8 @@ def test_argreduce_short_rows(cols, hip, oracle):
     ((200_003, 3), 0), ((100_001, 7), 0), ((33_000, 63), 0), ((2, 50_001, 5), 1),                   # a few columns, flat float4 walk
     ((50_001, 8), 0), ((30_001, 100), 0), ((7, 3001, 100), 1), ((9001, 256), 0), ((300, 77, 12), 1),  # whole float4 column groups
     ((2000, 1003), 0), ((4096, 1024), 0), ((1500, 9973), 0), ((4000, 20, 201), 1), ((3, 700, 260), 1), ((5, 17, 193), 1),  # wide inner
+    # axis in chunks, one thread per (output, chunk)
+    ((2000, 101), 0), ((4000, 67), 0), ((3, 129, 130), 1),
 ])
 def test_argreduce_streaming_forms(shape, axis, hip, oracle):
     """Every streaming form of round 5 (per-component accumulators, strict compares inside a lane, the general tie / NaN

@@ -81,7 +81,7 @@ def _moments(hip, x, offset=0):
 @pytest.mark.parametrize("n", [5, 300, 4099, 65536, 1_000_003, 10_000_000])
 def test_variance_of_a_large_mean_and_a_small_spread(n, hip, oracle):
     """1e4 + U[0,1): the case a one-pass sum x^2 - (sum x)^2 / n form loses every digit on, and a Chan merge with means
-    stored as single floats loses 6e-5 on at a few hundred elements (np_reduce.hip: anchor + offset).  Bar: 1e-5 of the
+    stored as single floats loses 6e-5 on at a few hundred elements (np_stats.hip: anchor + offset).  Bar: 1e-5 of the
     fp64 variance; next to it the oracle (the reference's own two passes, statistics.c:117-130), which is held to what its
     sequential fp32 sum allows — the GPU result must be at least as close to fp64 as the oracle is, up to the bar."""
     x = (np.float32(1e4) + synth.uniform((n,), 77, 0.0, 1.0)).astype(np.float32)
