@@ -74,9 +74,19 @@ int np_comm_debug_loopback(void *dev_scratch, size_t bytes);
  * K-chunk launch (17 .. 2047 rows, N <= 64, K >= 16384) of fewer than q / 4 workgroups per CU goes to the planner instead
  * (0 = never, as before round 5; default 59); -27 / -28 = consecutive independent large products on the library stream alone /
  * alternating with the side stream (np_sgemm_overlap_stats, np_hip.h; default), -29 = products of any size qualify for that
- * (tests), -30 = from 4e9 flop again.  All of them are process-wide setters for A/B measurements and tests: results stay within the same bounds. */
+ * (tests), -30 = from 4e9 flop again; -31 / -32 = the K loop of the 256 x 128 LDS-DMA kernels (sgemm_dma_kernel, sgemm_streamk_kernel)
+ * with flat per-lane source pointers everywhere / with buffer-addressed sources and three K-tiles per trip wherever the launch is
+ * eligible (no K % 16 / N % 4 tail, A and B 16-byte aligned, lda and ldb multiples of 4 below 2^22), -33 = the default: the second
+ * form for the eligible whole-tile launches with full tiles and K >= 2048 (the instantiation measured faster beyond its noise,
+ * profiles/kloop/), the first for the rest — same bits either way, np_sgemm_debug_kloop_stats counts which loop each launch ran.  All of them are process-wide setters for A/B measurements and tests: results stay within the same bounds. */
 int np_runtime_set_variant(int variant);   /* how host-result calls wait: 0 = hipStreamSynchronize, 1 = spin on a stream-written flag, 2 = spin on the result itself (default) */
 int np_sgemm_set_variant(int variant);
+/* tests / tools: out[0] = launches of sgemm_dma_kernel / sgemm_streamk_kernel that ran the buffer-addressed K loop (-32) so far,
+ * out[1] = those that ran the flat-addressed one (-31, or a launch that is not eligible) */
+int np_sgemm_debug_kloop_stats(unsigned long long out[2]);
+/* tests: C (M x N, rows ldc floats apart) = A (M x K, rows lda apart) . B (K x N, rows ldb apart) — one np_sgemm on windows of larger
+ * buffers, the form the factorizations use internally; nothing outside the windows is read into C or written */
+int np_sgemm_debug_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, const float *B, size_t ldb, float *C, size_t ldc);
 /* debug: the planner's choice for one dense, aligned M x N x K product on a device of `cus` CUs (0 = the current device; any
  * other value needs no device: the planner is host arithmetic).  out[11]: cfg, tail_rows, S, modelled us of the tiled plan;
  * stream-K taken (0/1), its modelled us; cfg, S, us of the best mid-size-tile plan; cfg, us of the best plan without them

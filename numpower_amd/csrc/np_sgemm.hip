@@ -514,10 +514,29 @@ __global__ __launch_bounds__(256, 2) void sgemm_pipe_kernel(GemmArgs g) {
 // function so that two kernels share it: sgemm_dma_kernel (one whole tile per workgroup) and sgemm_streamk_kernel
 // (a workgroup walks a contiguous range of (tile, k) iterations, i.e. a few SEGMENTS of tiles).  `K` is this
 // segment's inner length: a K tail (K % 16) exists only in the segment that holds the tile's last k.
+//
+// BUF = the K loop with scalar addressing.  The steady-state iteration of the flat-addressed loop (BUF = false) issues, per
+// wave and K-tile, 64 MFMAs, 16 LDS reads, 6 global_load_lds_dwordx4 and 14 VALU instructions, none of which the result
+// needs: eight (v_lshl_add_u32, v_lshl_or_b32, v_add_u32 0xc000 ...) rebuild the four fragment read addresses from the
+// run-time buffer index `cur`, six (v_lshl_add_u64 v[a:a+1], v[a:a+1], 0, 64) bump the per-lane 64-bit DMA source pointers,
+// each directly behind the global_load_lds that still has to read that register pair.  All lanes walk the same matrix at
+// loop-invariant per-lane offsets; only a uniform base moves.  The FLAT builtin does not select a scalar base on this
+// toolchain — __builtin_amdgcn_global_load_lds(uniform_base + voff32, ...) still compiles to v_lshl_add_u64 + global_load_lds
+// v[..], off — so do not retry that form; the BUFFER form does: __builtin_amdgcn_make_buffer_rsrc on a uniform pointer that
+// advances by scalar adds, __builtin_amdgcn_raw_ptr_buffer_load_lds with a loop-invariant voffset.  With the loop unrolled over
+// the three LDS buffers (a trip = three K-tiles, `cur` a compile-time value) every fragment read is an immediate offset from one
+// of three per-lane bases and every m0 a precomputed SGPR: the trip is 192 MFMA, 48 DS, 18 buffer_load ... lds and no VALU at
+// all (tools/gemm_kloop_isa.py, profiles/kloop/kloop_isa.log; 200 VGPRs, no scratch).  The order inside a tile is unchanged
+// (fragments of k-group 1 behind the first 8 MFMAs, vmcnt(0) + barrier behind 33, six DMA pieces, eight reads, one per MFMA
+// gap) and so is every element's accumulation order: same bits (tests/test_gpu_sgemm_kloop.py).  Measured at 4096^3
+// (profiles/kloop/): SQ_INSTS_VALU 41.63 M -> 34.29 M per launch, MFMA busy 0.950 -> 0.992 of CU-busy cycles, 933.6 -> 902.4 us
+// per product, 147.2 -> 151.9 TFLOP/s in bench.py.  What the trips leave over (1 .. 4 K-tiles) runs on a run-time buffer index:
+// peeled per buffer, the accumulators travel through alternative paths and the kernel spills (256 VGPRs + 972 B of scratch).
+// Which launches take it: kloop_takes() on the host.
 constexpr int kDmaBM = 256, kDmaBN = 128, kDmaBK = 16, kDmaTM = 4, kDmaTN = 2;
 typedef v16f DmaAcc[kDmaTM][kDmaTN];
 
-template <bool EDGE, bool KTAIL, bool PRIO>
+template <bool EDGE, bool KTAIL, bool PRIO, bool BUF = false>
 __device__ __forceinline__ void dma_gemm_segment(const GemmArgs &g, const float *A, const float *B, const unsigned m0,
                                                  const unsigned n0, const unsigned K, DmaAcc &acc, float **lds_out = nullptr) {
     constexpr int BM = kDmaBM, BN = kDmaBN, BK = kDmaBK;
@@ -660,6 +679,149 @@ __device__ __forceinline__ void dma_gemm_segment(const GemmArgs &g, const float 
     };
 
     Frag f0, f1;
+    using T = std::true_type;
+    using F = std::false_type;
+    if constexpr (BUF) {
+        // ---- the K loop with scalar addressing (see the comment above this function) ----
+        static_assert(!KTAIL, "the buffer-addressed K loop has no tail tile");
+        // DMA sources: one buffer resource per operand, its base the tile's first row (A) / column (B) at the current k,
+        // advanced by scalar adds; the per-lane byte offsets never change.  The host guarantees lda, ldb < 2^22, so
+        // 255 rows of A (15 of B) plus a row's 64 (512) bytes stay below 2^32; num_records = 2^32 - 1: the range check
+        // never fires, clamped rows / columns stay the mechanism for edges.
+        const float *a_base = A + (size_t)m0 * g.lda;
+        const float *b_base = B + n0;
+        unsigned a_vo[4], b_vo[2];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const unsigned r = (wave * 4 + c) * 16 + (lane >> 2);
+            const unsigned q = (lane & 3) ^ ((r >> 2) & 3);
+            unsigned row = r;
+            if (EDGE && m0 + r >= g.M) row = g.M - 1 - m0;
+            a_vo[c] = (row * g.lda + q * 4) * 4u;
+        }
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const unsigned krow = (wave * 2 + c) * 2 + (lane >> 5);
+            unsigned col = (lane & 31) * 4;
+            if (EDGE && n0 + col >= g.N) col = 0;   // wholly outside (N % 4 == 0 here): the tile's first columns, valid memory
+            b_vo[c] = (krow * g.ldb + col) * 4u;
+        }
+        const size_t b_step_buf = (size_t)BK * g.ldb;
+        auto dma_buf = [&](auto buf_c) {   // buf_c: an integral_constant in the trips, a run-time index in the peeled tiles
+            const unsigned buf = buf_c;
+            const auto ra = __builtin_amdgcn_make_buffer_rsrc((void *)a_base, 0, -1, 0x00020000);
+            const auto rb = __builtin_amdgcn_make_buffer_rsrc((void *)b_base, 0, -1, 0x00020000);
+            float *as = As + buf * A_SZ + wave * 1024;
+            float *bs = Bs + buf * B_SZ + wave * 512;
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (__attribute__((address_space(3))) void *)(as + c * 256), 16, (int)a_vo[c], 0, 0, 0);
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (__attribute__((address_space(3))) void *)(bs + c * 256), 16, (int)b_vo[c], 0, 0, 0);
+            a_base += BK;
+            b_base += b_step_buf;
+        };
+        // fragment reads: in the trips the buffer is a compile-time value, so every read is an immediate offset from one of
+        // three per-lane bases (A k-group 0, A k-group 1, B: the B buffers end at 72 KiB, past what a DS offset reaches from As)
+        const float *const a_rd0 = As + a_off0, *const a_rd1 = As + a_off1, *const b_rd = Bs + b_off;
+        auto read_buf = [&](Frag &f, auto buf_c, auto kg_c) {
+            const unsigned buf = buf_c;
+            constexpr unsigned kg = decltype(kg_c)::value;
+            const float *as = (kg ? a_rd1 : a_rd0) + buf * A_SZ;
+            const float *bs = b_rd + buf * B_SZ + kg * 8 * BN;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) f.a4[i] = *(const v4f *)(as + i * 32 * BK);
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) f.bv[s][j] = bs[s * BN + j * 32];
+        };
+        using I0 = std::integral_constant<unsigned, 0>;
+        using I1 = std::integral_constant<unsigned, 1>;
+        using I2 = std::integral_constant<unsigned, 2>;
+        // One K-tile on buffer `cur`: the order inside is k_tile's below, statement for statement.
+        auto k_tile_buf = [&](auto cur_c, auto dma_c, auto next_c) {
+            constexpr bool DMA = decltype(dma_c)::value, NEXT = decltype(next_c)::value;
+            const unsigned cur = cur_c, nxt = (cur == 2) ? 0 : cur + 1, nn = (nxt == 2) ? 0 : nxt + 1;
+            read_buf(f1, cur, I1{});
+            mfma_group(f0);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            }
+            __builtin_amdgcn_sched_group_barrier(0x008, 24, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (NEXT) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+            }
+            if constexpr (DMA) dma_buf(nn);
+            if constexpr (NEXT) read_buf(f0, nxt, I0{});
+            mfma_group(f1);
+            if constexpr (DMA) {
+#pragma unroll
+                for (int q = 0; q < 6; ++q) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                }
+            }
+            if constexpr (NEXT) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                }
+            }
+            __builtin_amdgcn_sched_group_barrier(0x008, 32, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        dma_buf(I0{});
+        if (nk > 1) dma_buf(I1{});
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        read_buf(f0, I0{}, I0{});
+        // A trip is three K-tiles on buffers 0, 1, 2, each with a DMA (tile + 2) and a successor: it needs five tiles
+        // ahead of it.  What the trips leave, 1 .. 4 tiles starting on buffer 0 again, runs behind them on a run-time buffer
+        // index like the flat loop's tiles (peeled per buffer, the 128 accumulators travel through alternative paths and spill)
+        unsigned trips = nk >= 5 ? (nk - 2) / 3 : 0;
+        unsigned rest = nk - 3 * trips;
+        auto trip = [&]() {
+            k_tile_buf(I0{}, T{}, T{});
+            k_tile_buf(I1{}, T{}, T{});
+            k_tile_buf(I2{}, T{}, T{});
+        };
+        if constexpr (PRIO) {
+            // g.prio_period K-tiles per phase, rounded to whole trips (16 -> 5 trips = 15 K-tiles)
+            unsigned phase = (unsigned)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (3 << 11)) & 1u;
+            const unsigned per = g.prio_period >= 2 ? (g.prio_period + 1) / 3 : 1;
+            while (trips) {
+                if (phase)
+                    __builtin_amdgcn_s_setprio(1);
+                else
+                    __builtin_amdgcn_s_setprio(0);
+                unsigned n = trips < per ? trips : per;
+                trips -= n;
+                for (; n; --n) trip();
+                phase ^= 1u;
+            }
+            __builtin_amdgcn_s_setprio(0);
+        } else {
+            for (; trips; --trips) trip();
+        }
+        unsigned cur = 0;
+        for (; rest > 2; --rest) {
+            k_tile_buf(cur, T{}, T{});
+            cur = (cur == 2) ? 0 : cur + 1;
+        }
+        if (rest > 1) {
+            k_tile_buf(cur, F{}, T{});
+            cur = (cur == 2) ? 0 : cur + 1;
+        }
+        k_tile_buf(cur, F{}, F{});
+        return;
+    }
     dma_tile(0, has_tail && nk == 1);
     if (nk > 1) dma_tile(1, has_tail && nk == 2);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -718,8 +880,6 @@ __device__ __forceinline__ void dma_gemm_segment(const GemmArgs &g, const float 
         __builtin_amdgcn_sched_barrier(0);
         cur = nxt;
     };
-    using T = std::true_type;
-    using F = std::false_type;
     // (a compile-time "tail DMA" variant of k_tile, peeled into its own iteration, pushed the kernel
     // to 256 VGPRs + 600 B/lane of scratch and 4096^3 from 144 to 130 TFLOP/s: the flag stays uniform
     // run-time state)
@@ -773,7 +933,7 @@ __device__ __forceinline__ void dma_store_tile(const GemmArgs &g, float *C, unsi
             }
 }
 
-template <bool EDGE, bool KTAIL, bool PRIO = false>
+template <bool EDGE, bool KTAIL, bool PRIO = false, bool BUF = false>
 __global__ __launch_bounds__(256, 2) void sgemm_dma_kernel(GemmArgs g) {
     if (g.K_last && blockIdx.z + 1 == gridDim.z) g.K = g.K_last;   // uniform: split-K remainder chunk
     unsigned tile_m, tile_n;
@@ -785,7 +945,7 @@ __global__ __launch_bounds__(256, 2) void sgemm_dma_kernel(GemmArgs g) {
     const float *B = g.B + (size_t)blockIdx.z * g.stride_b;
     float *C = g.C + (size_t)blockIdx.z * g.stride_c;
     DmaAcc acc;
-    dma_gemm_segment<EDGE, KTAIL, PRIO>(g, A, B, m0, n0, g.K, acc);
+    dma_gemm_segment<EDGE, KTAIL, PRIO, BUF>(g, A, B, m0, n0, g.K, acc);
     if (g.progress)
         dma_store_tile<EDGE, true>(g, C, m0, n0, acc);
     else
@@ -818,7 +978,7 @@ struct StreamKArgs {
     unsigned *error_word;   // np::device_error_word(): a finisher whose poll budget runs out ORs kErrStreamK in (reported at np_sync)
 };
 
-template <bool EDGE, bool KTAIL, bool PRIO = false>
+template <bool EDGE, bool KTAIL, bool PRIO = false, bool BUF = false>
 __global__ __launch_bounds__(256, 2) void sgemm_streamk_kernel(GemmArgs g, StreamKArgs sk) {
     const unsigned long long G = gridDim.x, w = blockIdx.x;
     const unsigned long long it0 = sk.iters_total * w / G, it1 = sk.iters_total * (w + 1) / G;
@@ -835,7 +995,7 @@ __global__ __launch_bounds__(256, 2) void sgemm_streamk_kernel(GemmArgs g, Strea
         first = false;
         DmaAcc acc;
         float *lds = nullptr;
-        dma_gemm_segment<EDGE, KTAIL, PRIO>(g, g.A + (size_t)kb * kDmaBK, g.B + (size_t)kb * kDmaBK * g.ldb, m0, n0, K, acc, &lds);
+        dma_gemm_segment<EDGE, KTAIL, PRIO, BUF>(g, g.A + (size_t)kb * kDmaBK, g.B + (size_t)kb * kDmaBK * g.ldb, m0, n0, K, acc, &lds);
         const unsigned long long next_it = it1 < tile_end ? it1 : tile_end;
         unsigned row0, col0;
         dma_acc_coords(row0, col0);
@@ -2298,10 +2458,33 @@ unsigned g_prio_period = 16;
 // with the other's MFMAs.  Same box, alternation on -> off (profiles/r05/gemm_thin_k_ab.log): 4096 x 4096 x 128 94.6 -> 108.9 TFLOP/s,
 // x 256 119.5 -> 124.9, 8192 x 8192 x 256 124.8 -> 133.5, K = 512 equal, K = 1024 139.5 -> 141.7, 4096^3 144.9 -> 145.3 (noise).
 // np_sgemm_set_variant(-(100 + p)) with p != 16 applies period p at every K (A/B); p = 16 restores this default.
+// The buffer-addressed K loop (dma_gemm_segment<.., BUF>) flips between its three-tile trips: its period is p rounded to whole
+// trips, (p + 1) / 3 of them and at least one (16 -> 5 trips = 15 K-tiles; 2 ... 64 are within 0.3 % of each other).
 unsigned g_prio_min_k = 2048;
 unsigned long long *g_probe = nullptr;
 
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
+// Which K loop sgemm_dma_kernel / sgemm_streamk_kernel run (dma_gemm_segment<.., BUF>).  A launch is ELIGIBLE for the
+// buffer-addressed loop, three K-tiles per trip, when it has no K / N tail instantiation, A and B (and the batch strides) are
+// 16-byte aligned and lda, ldb are multiples of 4 below 2^22 floats (every per-lane byte offset then fits the 32-bit voffset).
+// np_sgemm_set_variant(-31) = 0: the flat-addressed loop everywhere; (-32) = 2: the buffer-addressed loop wherever eligible;
+// (-33) = 1, the default: the buffer-addressed loop for the eligible launches of the instantiation that met the bar for a new
+// default in the in-process A/B (profiles/kloop/: the gain above the flat loop's own range in every round) — the whole-tile
+// kernel with priority alternation, full tiles, K >= 2048: the headline's 4096^3, 7 rounds of 7 with the side lane on and
+// off.  Stream-K (2560^3, 3584^3: 0.975, 0.968 of the flat loop's time, 6 and 5 rounds of 7), the whole-tile kernel below
+// K = 2048 (4096 x 4096 x 1024: 0.961, 1 of 7: its 4-step blocks range by more than the gain) and the ragged instantiations
+// (4000 x 4000 x 4096: 1.006) did not meet it and stay on the flat loop.
+// g_kloop_count: launches of the two kernels that took the buffer-addressed loop / the flat one (np_sgemm_debug_kloop_stats).
+int g_kloop = 1;
+unsigned long long g_kloop_count[2] = {0, 0};
+inline bool kloop_takes(const GemmArgs &g, unsigned batch, bool ktail, bool in_default_set) {
+    const bool buf = (g_kloop == 2 || (g_kloop == 1 && in_default_set)) && !ktail && aligned16(g.A) && aligned16(g.B) &&
+                     g.lda % 4 == 0 && g.ldb % 4 == 0 && g.lda < (1u << 22) && g.ldb < (1u << 22) &&
+                     (batch == 1 || (g.stride_a % 4 == 0 && g.stride_b % 4 == 0));
+    __atomic_fetch_add(&g_kloop_count[buf ? 0 : 1], 1ull, __ATOMIC_RELAXED);
+    return buf;
+}
 
 // What np::sgemm_batched_with_progress asks of the ONE launch it makes (host-side plumbing).  Per host thread: an np_sgemm
 // on another thread while the communicator's thread is inside np_sgemm_strided_batched_allgather must not pick up that
@@ -2467,16 +2650,25 @@ int launch_cfg(int cfg, GemmArgs g, unsigned batch, bool vec, bool whole = false
         } else {
             s = np::stream();
         }
+        const bool buf = kloop_takes(g, batch, ktail, !edge && !ktail && g_prio_period && g.K >= g_prio_min_k);
         if (edge && ktail)
             sgemm_dma_kernel<true, true><<<grid, 256, 0, s>>>(g);
-        else if (edge)
-            sgemm_dma_kernel<true, false><<<grid, 256, 0, s>>>(g);
-        else if (ktail)
+        else if (edge) {
+            if (buf)
+                sgemm_dma_kernel<true, false, false, true><<<grid, 256, 0, s>>>(g);
+            else
+                sgemm_dma_kernel<true, false><<<grid, 256, 0, s>>>(g);
+        } else if (ktail)
             sgemm_dma_kernel<false, true><<<grid, 256, 0, s>>>(g);
         else if (g_prio_period && g.K >= g_prio_min_k) {
             g.prio_period = g_prio_period;
-            sgemm_dma_kernel<false, false, true><<<grid, 256, 0, s>>>(g);
-        } else
+            if (buf)
+                sgemm_dma_kernel<false, false, true, true><<<grid, 256, 0, s>>>(g);
+            else
+                sgemm_dma_kernel<false, false, true><<<grid, 256, 0, s>>>(g);
+        } else if (buf)
+            sgemm_dma_kernel<false, false, false, true><<<grid, 256, 0, s>>>(g);
+        else
             sgemm_dma_kernel<false, false><<<grid, 256, 0, s>>>(g);
         NP_LAUNCH_CHECK("sgemm_dma_kernel");
         note_progress_launch(g);
@@ -2750,16 +2942,25 @@ int launch_streamk(GemmArgs g, unsigned G) {
     const bool edge = g.M % 256 || g.N % 128 || g.n_store;
     const bool ktail = g.K % 16 || g.N % 4;
     hipStream_t s = np::stream();
+    const bool buf = kloop_takes(g, 1, ktail, false);
     if (edge && ktail)
         sgemm_streamk_kernel<true, true><<<G, 256, 0, s>>>(g, sk);
-    else if (edge)
-        sgemm_streamk_kernel<true, false><<<G, 256, 0, s>>>(g, sk);
-    else if (ktail)
+    else if (edge) {
+        if (buf)
+            sgemm_streamk_kernel<true, false, false, true><<<G, 256, 0, s>>>(g, sk);
+        else
+            sgemm_streamk_kernel<true, false><<<G, 256, 0, s>>>(g, sk);
+    } else if (ktail)
         sgemm_streamk_kernel<false, true><<<G, 256, 0, s>>>(g, sk);
     else if (g_prio_period) {
         g.prio_period = g_prio_period;
-        sgemm_streamk_kernel<false, false, true><<<G, 256, 0, s>>>(g, sk);
-    } else
+        if (buf)
+            sgemm_streamk_kernel<false, false, true, true><<<G, 256, 0, s>>>(g, sk);
+        else
+            sgemm_streamk_kernel<false, false, true><<<G, 256, 0, s>>>(g, sk);
+    } else if (buf)
+        sgemm_streamk_kernel<false, false, false, true><<<G, 256, 0, s>>>(g, sk);
+    else
         sgemm_streamk_kernel<false, false><<<G, 256, 0, s>>>(g, sk);
     NP_LAUNCH_CHECK("sgemm_streamk_kernel");
     return NP_OK;
@@ -3476,6 +3677,11 @@ int np_sgemm_set_variant(int variant) {
             np::lane_set_knob(-27 - variant);
             return NP_OK;
         }
+        if (variant <= -31 && variant >= -33) {   // -31: the flat-addressed K loop of the 256 x 128 LDS-DMA kernels everywhere, -32: the buffer-addressed one wherever eligible, -33: the default (kloop_takes)
+            g_kloop = variant == -31 ? 0 : variant == -32 ? 2 : 1;
+            return NP_OK;
+        }
+        if (variant <= -34 && variant >= -39) return np::fail(NP_ERR_INVALID, "np_sgemm_set_variant: -34 .. -39 are not assigned");
         if (variant == -16 || variant == -17) {
             g_mid_swizzle = variant == -17;
             return NP_OK;
@@ -3539,6 +3745,20 @@ int np_sgemm_overlap_stats(unsigned long long out[3]) {
     if (int rc = np::ensure_init()) return rc;
     np::lane_stats(out);
     return NP_OK;
+}
+
+int np_sgemm_debug_kloop_stats(unsigned long long out[2]) {
+    if (!out) return np::fail(NP_ERR_INVALID, "np_sgemm_debug_kloop_stats: null output");
+    out[0] = __atomic_load_n(&g_kloop_count[0], __ATOMIC_RELAXED);
+    out[1] = __atomic_load_n(&g_kloop_count[1], __ATOMIC_RELAXED);
+    return NP_OK;
+}
+
+int np_sgemm_debug_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, const float *B, size_t ldb, float *C, size_t ldc) {
+    if (!A || !B || !C || M == 0 || N == 0 || K == 0 || lda < K || ldb < N || ldc < N)
+        return np::fail(NP_ERR_INVALID, "np_sgemm_debug_ld: needs operands, M, N, K >= 1, lda >= K, ldb >= N, ldc >= N");
+    if (int rc = np::ensure_init()) return rc;
+    return launch_sgemm_ld(1, M, N, K, A, lda, 0, B, ldb, 0, C, ldc, 0);
 }
 
 int np_sgemm(size_t M, size_t N, size_t K, const float *A, const float *B, float *C) {
