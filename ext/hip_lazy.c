@@ -432,7 +432,7 @@ NDArray *NPH_LazyBinary(int op, NPH_EagerBinary eager, NDArray *a, NDArray *b) {
     if (!NPH_TAKES(a, b)) return eager(a, b);              /* CPU operands: the reference's own code, nothing pending */
     const int pa = find_chain(a) != NULL, pb = find_chain(b) != NULL;
     /* pow is a step like the others: the chain runs np_binary's arithmetic for it, `** 2` with a PHP number included
-     * (x * x in both, np_elementwise.hip) — an expression must not change its value with the way it is evaluated */
+     * (x * x in both: np_elementwise.hip, np_fused_chain.hip) — an expression must not change its value with the way it is evaluated */
     if (g_lazy_on) {
         NDArray *head = NULL, *other = NULL;
         int swap = 0;

@@ -93,7 +93,13 @@ int np_sgemm_debug_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, 
  * (1e300 = does not apply).  tests/test_abi_and_host_cpu.py pins the choices that matter (no reference counterpart:
  * linalg.c:75-79 hands every product to cblas / cuBLAS). */
 int np_sgemm_debug_plan(size_t M, size_t N, size_t K, size_t batch, int cus, double *out);
-int np_elementwise_set_variant(int variant);   /* launch shape of the streaming kernels (np_elementwise.hip cfg_from_variant) and A/B switches of single kernels, e.g. 9000 = np_binary(pow) with its log2 table in LDS instead of registers (same bits) */
+/* A/B switches of single kernels of np_elementwise.hip / np_fused_chain.hip, same bits either way; a plain setter, 0 = defaults.  7000: chains on
+ * the interpreter only (no compiled chain); 7001: chains that name an array twice as every other chain (compiled or streaming), 7002: never
+ * looked for; 7004: compiled first-axis chains with 4 rows in flight; 8000: a long row operand in the plain work order; 8100 / 8101: the 2-D
+ * broadcast kernels off / on again (kept beside the code: it does not replace it); 9000: np_binary(pow) with its log2 table in LDS instead of
+ * registers; 12000 + k / 14000 + k: first-axis chains on k workgroups per CU, compiled ones with 2 / 4 rows in flight.  Any non-zero code also
+ * keeps FULL (op) ROW off the 2-D form. */
+int np_elementwise_set_variant(int variant);
 int np_layout_set_variant(int variant);   /* transpose tile: 0 = default, 64, 128; 1 = default tiles without the write-aligned form for output rows off the 128-byte grid */
 int np_select_set_variant(int variant);   /* order statistics: 0 = plain three passes only (no bracket path, no one-workgroup kernel), 1 = default (n >= 2^26), else the smallest n that takes it */
 int np_select_last_path(int *path);       /* tests / tools: 1 if the last selection ran over the bracket's copied keys, 0 if over the array, 2 if in the one-workgroup kernel (synchronises) */

@@ -1,5 +1,5 @@
 // The op bodies of the elementwise path — one definition of every binary / unary float_* operation, shared by the
-// translation units that apply them (np_elementwise.hip: the stand-alone kernels and the chain interpreter;
+// translation units that apply them (np_elementwise.hip: the stand-alone kernels; np_fused_chain.hip: the chain interpreter;
 // np_fused_static.hip: the compiled chains), so that a fused chain is bit-identical to the op-by-op sequence by
 // construction.  Internal to libnp_hip.so; everything lives in an anonymous namespace (one copy per translation unit).
 //

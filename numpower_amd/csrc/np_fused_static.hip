@@ -1,6 +1,6 @@
 // Compiled chains — straight-line kernels for the short, cheap elementwise chains.
 //
-// The chain interpreter of np_elementwise.hip takes ANY chain of up to 12 steps: a loop over step descriptors, a uniform
+// The chain interpreter of np_fused_chain.hip takes ANY chain of up to 12 steps: a loop over step descriptors, a uniform
 // switch per step.  rocprofv3 (profiles/r03/pmc_sq_final.txt) showed what that costs where the chain itself is cheap:
 // sum(exp(X), axis 0) issued 19.5 VALU instructions per element for ~11 of arithmetic, 85 % VALU-active, 0.61 of the HBM
 // roofline — the switch's joins copy the chain value between register sets, every trip re-derives its live masks, zero-fills

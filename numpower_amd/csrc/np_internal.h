@@ -135,11 +135,10 @@ int sgemm_batched_piece(size_t count, size_t whole, size_t M, size_t N, size_t K
 // C (M x N, row stride ldc) -= A (M x K, row stride lda) . B (K x N, row stride ldb), one MFMA tile launch (np_sgemm.hip; the
 // LU's trailing updates and blocked triangular solves, np_lu.hip, and the Cholesky's trailing updates, np_cholesky.hip).  None of the np_sgemm* plans uses it.
 int sgemm_sub_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, const float *B, size_t ldb, float *C, size_t ldc);
-// Compiled chains (np_fused_static.hip): what np_elementwise.hip's fused_chain_impl hands over when a chain of 1-3 steps
+// Compiled chains (np_fused_static.hip): what np_fused_chain.hip's plan_chain hands over when a chain of 1-3 steps
 // might be on the menu of straight-line kernels.  operand[k] == nullptr: a scalar operand (or a unary step); idx[k]: how an
 // array operand is indexed by the flat element index e of the rows x cols result — 0 full, 1 row (e % cols), 2 column
 // (e / cols), 3 zero-d.  bcast_cols: the row length when some operand is broadcast (then a multiple of 4), else 0.
-extern int g_bcast2d_off;   // np_elementwise_set_variant(8100): the 2-D broadcast kernels off (A/B)
 struct FusedStaticDesc {
     int n_ops;
     const float *in0;
@@ -154,13 +153,19 @@ struct FusedStaticDesc {
 bool fused_static_covers(const FusedStaticDesc &d, int sink, int axis_mode);
 // flat: out[e] = chain(e) (sink < 0) or one partial per workgroup in out[] under the interpreter's protocol (ticket / result)
 int fused_static_flat(const FusedStaticDesc &d, float *out, size_t n, int sink, unsigned grid, unsigned *ticket, float *result);
-// first axis: out[chunk][c] = sum over the chunk's rows (the geometry fused_chain_impl computed for the interpreter's kernel)
+// first axis: out[chunk][c] = sum over the chunk's rows (the geometry np_fused_chain.hip's launch_cols computed for the interpreter's kernel)
 int fused_static_cols(const FusedStaticDesc &d, float *out, size_t rows, size_t cols, size_t rows_per_chunk, float mean_div,
                       unsigned col_blocks, unsigned chunks, int rows_in_flight);
 // last axis: out[r] = sum over the row, lane groups of L lanes per row (the interpreter's wave mode); cols % 4 == 0
 int fused_static_rows(const FusedStaticDesc &d, float *out, size_t rows, size_t cols, unsigned L, float mean_div, unsigned grid);
 // Copy kernel for large word-aligned device-to-device copies (np_elementwise.hip); bytes % 4 == 0.
 int device_copy(void *dst, const void *src, size_t bytes);
+// Knobs of np_elementwise_set_variant (np_elementwise.hip) that np_fused_chain.hip reads too
+extern int g_ew_variant;    // the last code set, 0 = defaults (np_hip_debug.h lists the codes)
+extern int g_bcast2d_off;   // 8100: the 2-D broadcast kernels off (A/B), 8101: back on
+// Grid of a streaming kernel (np_elementwise.hip): 256-thread workgroups for work_items at per_thread items per thread, capped
+// at blocks_per_cu workgroups per CU when that is > 0, made odd from 64 workgroups up (as np::capped_grid).
+unsigned grid_for(size_t work_items, int per_thread, int blocks_per_cu);
 
 // Scratch from the caching pool, released back to the pool when the object dies.  Freed blocks
 // are only reused by later launches on the same stream, so releasing right after the launch

@@ -448,6 +448,9 @@ CHAIN_AXIS_CASES = [
     (3001, 257, 1, CH_ROWS), (300, 4099, 1, CH_ROWS), (129, 64, 1, CH_ROWS), (5000, 256, 1, CH_ROWS),
     (3, 1000003, 1, CH_ROWS | CH_SPLIT),               # a few very long rows cut over several workgroups
     (900001, 10, 1, CH_ROWS_STAGED), (180001, 47, 1, CH_ROWS_STAGED),
+    # rows of 49 ... 512 floats of an array of >= 2^23 elements that the lane groups pack badly go through the same kernel in slabs of
+    # a few rows: 160 rows and a thread per row; 80 rows, 2 lanes per row; 16 rows, 16 lanes per row
+    (168001, 50, 1, CH_ROWS_STAGED), (84001, 100, 1, CH_ROWS_STAGED), (16801, 501, 1, CH_ROWS_STAGED),
     (3001, 15, 1, CH_TEMPORARY), (100, 300, 1, CH_TEMPORARY),          # rows shorter than 16 floats; fewer than 128 rows of a small array
     (4001, 257, 0, CH_COLS | CH_SPLIT), (40, 4099, 0, CH_COLS), (4001, 256, 0, CH_COLS | CH_SPLIT), (40, 4096, 0, CH_COLS),
     (31, 4096, 0, CH_TEMPORARY), (4001, 31, 0, CH_TEMPORARY), (4001, 124, 0, CH_TEMPORARY),   # fewer than 32 rows / 32 column slots
@@ -469,6 +472,17 @@ def test_chain_reduce_axis_exact(case, dev):
     as_interpreter = {(m & ~(CH_STATIC_ROWS | CH_STATIC_COLS)) | (CH_ROWS if m & CH_STATIC_ROWS else 0) | (CH_COLS if m & CH_STATIC_COLS else 0)
                       for m in seen}
     assert as_interpreter == {named} and named in seen, "chain probe %r, expected %#x" % (sorted(map(hex, seen)), named)
+
+
+def test_chain_on_a_staged_shape_off_alignment_takes_the_temporary(dev):
+    """The staged kernel needs input 0 on 16 bytes: one float off, the chain is stored and np_reduce_axis reduces it."""
+    rows, cols = 900001, 10
+    x = rf.ints((rows, cols, 1), 1900, 3, 1)
+    with dev.held(x, 1) as v:
+        for op in ("sum", "mean", "min", "max"):
+            got, mask = dev.chain("axis", op, v, rows, cols, 1)
+            _check(got, rf.expected(x, 1, op), "np_fused_chain_reduce_axis %dx%d one float off %s" % (rows, cols, op))
+            assert mask == CH_TEMPORARY, hex(mask)
 
 
 @pytest.mark.parametrize("n", [1, 7, 1025, 65537, 2 ** 20 + 1, 4200003])

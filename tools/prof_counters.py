@@ -39,7 +39,7 @@ prog1 = (FusedOp * 1)(FusedOp(0, UNARY_OPS["exp"], 0, 0, 0, 0, 0, 0))
 ptrs1 = (C.c_void_p * 1)(a.ptr)
 kinds1 = (C.c_int * 1)(0)
 # sum(exp(X), axis): the compiled chain (cchain_cols_kernel / cchain_rows_kernel) and, behind it, the chain interpreter it
-# replaced for this chain (np_elementwise_set_variant(7000): fused_chain_cols_kernel / fused_chain_rows_kernel)
+# replaced for this chain (np_fused_chain.hip; np_elementwise_set_variant(7000): fused_chain_cols_kernel / fused_chain_rows_kernel)
 for axis, nout, key in ((0, Cc, "cols"), (1, R, "rows")):
     if key in which:
         dred = D.DeviceArray((nout,))
