@@ -180,6 +180,39 @@ int np_debug_reduce_last_path(unsigned *host_mask);
 #define NP_CHAIN_PATH_SPLIT 0x0080u        /* the axis was cut into chunks: np_reduce_axis folds the partials */
 #define NP_CHAIN_PATH_TEMPORARY 0x0100u    /* the chain was stored to a temporary and np_reduce_axis reduced it */
 int np_debug_chain_reduce_last_path(unsigned *host_mask);
+/* the same for the product kernels of np_sgemm.hip: the OR of the NP_SGEMM_PATH_ bits naming everything the last np_sgemm /
+ * np_sgemm_strided_batched / np_sgemm_debug_ld / np_sgemv call of the process launched (0 = none yet).  A plain process global,
+ * cleared at the top of the OUTERMOST of those entry points only: the calls they make among themselves (N = 1 of a thin product
+ * is np_sgemv, a peeled product hands its edges to np_sgemm_strided_batched) OR into the mask of the call that made them.  Bits
+ * 0 .. 19 name kernels; the two fields above them carry the template argument where it selects another instantiation: bits
+ * 20 .. 23 = log2(L) + 1 of the lane-group width L of sgemm_thin_kernel / sgemv_short_rows_kernel, bits 24 .. 27 = log2(MV) + 1
+ * of the accumulator count MV of sgemm_fewrows_kernel / sgemm_thin_left_kernel (0 = no such kernel ran).  NP_SGEMM_PATH_LANES(L)
+ * and NP_SGEMM_PATH_MV(MV) build the fields, so a test writes a whole mask: NP_SGEMM_PATH_THIN_LANES | NP_SGEMM_PATH_LANES(8).
+ * Costs one store to a host global per launch site: no device work, no synchronisation.  Like the probes above it is meaningful
+ * only while one thread calls the products. */
+#define NP_SGEMM_PATH_THIN_LANES 0x00001u          /* sgemm_thin_kernel<NV, L>; L in the LANES field */
+#define NP_SGEMM_PATH_THIN_MFMA16 0x00002u         /* sgemm_thin_mfma_kernel<16> (N <= 16) */
+#define NP_SGEMM_PATH_THIN_MFMA32 0x00004u         /* sgemm_thin_mfma_kernel<32> (N <= 32) */
+#define NP_SGEMM_PATH_THIN_MFMA32X2 0x00008u       /* sgemm_thin_mfma_kernel<32, 2> (N = 33 .. 64) */
+#define NP_SGEMM_PATH_THIN_K_CHUNKS 0x00010u       /* that launch had gridDim.y > 1: K-chunks into partials */
+#define NP_SGEMM_PATH_FEWROWS_SPLITK1 0x00020u     /* sgemm_fewrows_splitk_kernel<1> (N <= 32) */
+#define NP_SGEMM_PATH_FEWROWS_SPLITK2 0x00040u     /* sgemm_fewrows_splitk_kernel<2> (N = 33 .. 64) */
+#define NP_SGEMM_PATH_THIN_CHUNKS 0x00080u         /* sgemm_thin_chunks_kernel<NV> */
+#define NP_SGEMM_PATH_FEWROWS 0x00100u             /* sgemm_fewrows_kernel<MV>; MV in the MV field */
+#define NP_SGEMM_PATH_SKINNY 0x00200u              /* sgemm_skinny_kernel */
+#define NP_SGEMM_PATH_FOLD 0x00400u                /* a launcher folded its partials with np_reduce_axis */
+#define NP_SGEMM_PATH_THIN_LEFT 0x00800u           /* sgemm_thin_left_kernel<MV>; MV in the MV field */
+#define NP_SGEMM_PATH_PEELED 0x01000u              /* try_peeled took the shape: main block + edge products */
+#define NP_SGEMM_PATH_GEMV_STAGED 0x02000u         /* sgemv_staged_rows_kernel */
+#define NP_SGEMM_PATH_GEMV_SHORT_ROWS 0x04000u     /* sgemv_short_rows_kernel<L>; L in the LANES field */
+#define NP_SGEMM_PATH_GEMV_FEWROWS_CHUNKS 0x08000u /* sgemv_fewrows_chunks_kernel */
+#define NP_SGEMM_PATH_GEMV_CHUNKS 0x10000u         /* sgemv_chunks_kernel */
+#define NP_SGEMM_PATH_GEMV_WAVE 0x20000u           /* sgemv_kernel, a wave per row */
+#define NP_SGEMM_PATH_GEMV_WAVE_VEC 0x40000u       /* ... in its aligned float4 form (vec) */
+#define NP_SGEMM_PATH_TILED 0x80000u               /* launch_sgemm reached: the planner's tiled, stream-K, padded, mid or kq plans */
+#define NP_SGEMM_PATH_LANES(L) ((unsigned)(__builtin_ctz((unsigned)(L)) + 1) << 20)   /* L = 1, 2, 4 .. 64 */
+#define NP_SGEMM_PATH_MV(MV) ((unsigned)(__builtin_ctz((unsigned)(MV)) + 1) << 24)    /* MV = 1, 2, 4, 8, 16 */
+int np_sgemm_debug_last_path(unsigned *host_mask);
 
 #ifdef __cplusplus
 }

@@ -2450,6 +2450,18 @@ __global__ __launch_bounds__(256) void sgemm_thin_chunks_kernel(const float *__r
 }
 
 int g_variant = 0;
+// np_sgemm_debug_last_path: the NP_SGEMM_PATH_* bits of what the last np_sgemm / np_sgemm_strided_batched / np_sgemm_debug_ld /
+// np_sgemv call launched.  PathScope stands at the top of each of those entry points and clears the record only in the outermost
+// one, so the calls they make among themselves (N = 1 -> np_sgemv, the edges of a peeled product) add to it.  One host store per
+// launch site, nothing on the device.  The record is one plain global (meaningful while one thread calls the products); the nesting
+// depth is per thread, so that concurrent callers cannot leave it off zero.
+unsigned g_last_path = 0;
+thread_local int g_path_depth = 0;
+inline void note_path(unsigned bits) { g_last_path |= bits; }
+struct PathScope {
+    PathScope() { if (g_path_depth++ == 0) g_last_path = 0; }
+    ~PathScope() { --g_path_depth; }
+};
 // sgemm_dma_kernel<.., PRIO>: K-tiles per priority phase; np_sgemm_set_variant(-(100 + p)) sets it (p = 0: off).
 // 16: 145.4 -> 146.4 TFLOP/s at 4096^3 (tools/gemm_prio_ab.py, profiles/r02/gemm_prio_ab.log; 2...64 all within 0.3 %)
 unsigned g_prio_period = 16;
@@ -3193,6 +3205,7 @@ int launch_plan(const Plan &p, GemmArgs g, size_t batch, bool vec) {
     part.K_last = (unsigned)rem;
     if (p.cfg >= kFirstKqCfg && g_kq_chunk_major) part.k_chunks = (unsigned)chunks;
     if (int rc = launch_cfg(p.cfg, part, (unsigned)chunks, vec && rem % 4 == 0)) return rc;
+    note_path(NP_SGEMM_PATH_FOLD);
     return np_reduce_axis(NP_SUM, W, 1, chunks, m2 * N, g.C + m1 * N, 0);
 }
 
@@ -3202,6 +3215,7 @@ int launch_sgemm_ld(size_t batch, size_t M, size_t N, size_t K, const float *A, 
     if (M > 0x7fffffffu || N > 0x7fffffffu || K > 0x7fffffffu || lda > 0x7fffffffu || ldb > 0x7fffffffu || ldc > 0x7fffffffu ||
         batch > 65535)
         return np::fail(NP_ERR_INVALID, "np_sgemm: dimension too large");
+    note_path(NP_SGEMM_PATH_TILED);
     GemmArgs g;
     g.A = A; g.B = B; g.C = C;
     g.M = (unsigned)M; g.N = (unsigned)N; g.K = (unsigned)K; g.K_last = 0; g.n_store = 0;
@@ -3318,6 +3332,7 @@ int try_peeled(size_t M, size_t N, size_t K, const float *A, const float *B, flo
         if (t < best) { best = t; M0 = m0; N0 = n0; }
     }
     if (M0 == M && N0 == N) return 1;
+    note_path(NP_SGEMM_PATH_PEELED);
     if (int rc = launch_sgemm_ld(1, M0, N0, K, A, K, 0, B, N, 0, C, N, 0)) return rc;
     if (M0 != M)
         if (int rc = np_sgemm_strided_batched(1, M - M0, N, K, A + M0 * K, 0, B, 0, C + M0 * N, 0)) return rc;
@@ -3361,6 +3376,7 @@ int launch_thin_nv(size_t M, size_t N, size_t K, const float *A, const float *B,
         }
 #undef NP_TH
         NP_LAUNCH_CHECK("sgemm_thin_kernel");
+        note_path(NP_SGEMM_PATH_THIN_LANES | NP_SGEMM_PATH_LANES(L));
         return NP_OK;
     }
     if (M >= 2048 && (N > 4 || (K >= 1024 && M < 65536)) && N <= 32 && K >= 4) {
@@ -3383,12 +3399,14 @@ int launch_thin_nv(size_t M, size_t N, size_t K, const float *A, const float *B,
                 if (N <= 16) sgemm_thin_mfma_kernel<16><<<grid, 256, 0, s>>>(A, B, (float *)partial.ptr, M, (unsigned)N, (unsigned)K, (unsigned)kc);
                 else sgemm_thin_mfma_kernel<32><<<grid, 256, 0, s>>>(A, B, (float *)partial.ptr, M, (unsigned)N, (unsigned)K, (unsigned)kc);
                 NP_LAUNCH_CHECK("sgemm_thin_mfma_kernel");
+                note_path((N <= 16 ? NP_SGEMM_PATH_THIN_MFMA16 : NP_SGEMM_PATH_THIN_MFMA32) | NP_SGEMM_PATH_THIN_K_CHUNKS | NP_SGEMM_PATH_FOLD);
                 return np_reduce_axis(NP_SUM, (const float *)partial.ptr, 1, chunks, M * N, C, 0);
             }
         }
         if (N <= 16) sgemm_thin_mfma_kernel<16><<<(unsigned)blocks, 256, 0, s>>>(A, B, C, M, (unsigned)N, (unsigned)K, (unsigned)K);
         else sgemm_thin_mfma_kernel<32><<<(unsigned)blocks, 256, 0, s>>>(A, B, C, M, (unsigned)N, (unsigned)K, (unsigned)K);
         NP_LAUNCH_CHECK("sgemm_thin_mfma_kernel");
+        note_path(N <= 16 ? NP_SGEMM_PATH_THIN_MFMA16 : NP_SGEMM_PATH_THIN_MFMA32);
         return NP_OK;
     }
     // measured (profiles/r01/skinny_gemm.log): wins for one or two row tiles and N > 16 (32 x 64 x 2e6: 0.334 -> 0.199 ms,
@@ -3411,6 +3429,7 @@ int launch_thin_nv(size_t M, size_t N, size_t K, const float *A, const float *B,
                 if (N <= 32) sgemm_fewrows_splitk_kernel<1><<<grid, 256, 0, s>>>(A, B, (float *)partial.ptr, (unsigned)M, (unsigned)N, (unsigned)K, (unsigned)kc);
                 else sgemm_fewrows_splitk_kernel<2><<<grid, 256, 0, s>>>(A, B, (float *)partial.ptr, (unsigned)M, (unsigned)N, (unsigned)K, (unsigned)kc);
                 NP_LAUNCH_CHECK("sgemm_fewrows_splitk_kernel");
+                note_path((N <= 32 ? NP_SGEMM_PATH_FEWROWS_SPLITK1 : NP_SGEMM_PATH_FEWROWS_SPLITK2) | NP_SGEMM_PATH_FOLD);
                 return np_reduce_axis(NP_SUM, (const float *)partial.ptr, 1, chunks, M * N, C, 0);
             }
         }
@@ -3436,6 +3455,8 @@ int launch_thin_nv(size_t M, size_t N, size_t K, const float *A, const float *B,
             else if (N <= 32) sgemm_thin_mfma_kernel<32><<<grid, 256, 0, s>>>(A, B, (float *)partial.ptr, M, (unsigned)N, (unsigned)K, (unsigned)kc);
             else sgemm_thin_mfma_kernel<32, 2><<<grid, 256, 0, s>>>(A, B, (float *)partial.ptr, M, (unsigned)N, (unsigned)K, (unsigned)kc);
             NP_LAUNCH_CHECK("sgemm_thin_mfma_kernel");
+            note_path((N <= 16 ? NP_SGEMM_PATH_THIN_MFMA16 : N <= 32 ? NP_SGEMM_PATH_THIN_MFMA32 : NP_SGEMM_PATH_THIN_MFMA32X2) |
+                      NP_SGEMM_PATH_THIN_K_CHUNKS | NP_SGEMM_PATH_FOLD);
             return np_reduce_axis(NP_SUM, (const float *)partial.ptr, 1, chunks, M * N, C, 0);
         }
     }
@@ -3452,6 +3473,7 @@ int launch_thin_nv(size_t M, size_t N, size_t K, const float *A, const float *B,
         sgemm_thin_chunks_kernel<NV><<<dim3((unsigned)chunks, (unsigned)M), 256, 0, s>>>(
             A, B, (float *)partial.ptr, (unsigned)N, (unsigned)K, (unsigned)chunk_len);
         NP_LAUNCH_CHECK("sgemm_thin_chunks_kernel");
+        note_path(NP_SGEMM_PATH_THIN_CHUNKS | NP_SGEMM_PATH_FOLD);
         return np_reduce_axis(NP_SUM, (const float *)partial.ptr, M, chunks, N, C, 0);
     }
     return 1;
@@ -3484,6 +3506,7 @@ int launch_fewrows(size_t M, size_t N, size_t K, const float *A, const float *B,
     else NP_FR(8);
 #undef NP_FR
     NP_LAUNCH_CHECK("sgemm_fewrows_kernel");
+    note_path(NP_SGEMM_PATH_FEWROWS | NP_SGEMM_PATH_MV(M == 1 ? 1 : M == 2 ? 2 : M <= 4 ? 4 : 8) | (chunks > 1 ? NP_SGEMM_PATH_FOLD : 0u));
     if (chunks > 1) return np_reduce_axis(NP_SUM, out, 1, chunks, M * N, C, 0);
     return NP_OK;
 }
@@ -3517,6 +3540,7 @@ int launch_skinny(size_t M, size_t N, size_t K, const float *A, const float *B, 
     else
         sgemm_skinny_kernel<2><<<grid, 256, 0, s>>>(A, B, out, (unsigned)M, (unsigned)N, (unsigned)K, (unsigned)chunk_len);
     NP_LAUNCH_CHECK("sgemm_skinny_kernel");
+    note_path(NP_SGEMM_PATH_SKINNY | (chunks > 1 ? NP_SGEMM_PATH_FOLD : 0u));
     if (chunks > 1) return np_reduce_axis(NP_SUM, out, 1, chunks, M * N, C, 0);
     return NP_OK;
 }
@@ -3754,9 +3778,16 @@ int np_sgemm_debug_kloop_stats(unsigned long long out[2]) {
     return NP_OK;
 }
 
+int np_sgemm_debug_last_path(unsigned *host_mask) {
+    if (!host_mask) return np::fail(NP_ERR_INVALID, "np_sgemm_debug_last_path: null pointer");
+    *host_mask = g_last_path;
+    return NP_OK;
+}
+
 int np_sgemm_debug_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, const float *B, size_t ldb, float *C, size_t ldc) {
     if (!A || !B || !C || M == 0 || N == 0 || K == 0 || lda < K || ldb < N || ldc < N)
         return np::fail(NP_ERR_INVALID, "np_sgemm_debug_ld: needs operands, M, N, K >= 1, lda >= K, ldb >= N, ldc >= N");
+    PathScope scope;
     if (int rc = np::ensure_init()) return rc;
     return launch_sgemm_ld(1, M, N, K, A, lda, 0, B, ldb, 0, C, ldc, 0);
 }
@@ -3768,6 +3799,7 @@ int np_sgemm(size_t M, size_t N, size_t K, const float *A, const float *B, float
 int np_sgemm_strided_batched(size_t batch, size_t M, size_t N, size_t K, const float *A,
                              size_t stride_a, const float *B, size_t stride_b, float *C,
                              size_t stride_c) {
+    PathScope scope;
     if (batch == 0 || M == 0 || N == 0) return NP_OK;
     if (!C) return np::fail(NP_ERR_INVALID, "np_sgemm: null output");
     if (int rc = np::ensure_init()) return rc;
@@ -3815,6 +3847,7 @@ int np_sgemm_strided_batched(size_t batch, size_t M, size_t N, size_t K, const f
         else
             sgemm_thin_left_kernel<16><<<(unsigned)blocks, 256, 0, np::stream()>>>(A, B, C, (unsigned)M, N, (unsigned)K);
         NP_LAUNCH_CHECK("sgemm_thin_left_kernel");
+        note_path(NP_SGEMM_PATH_THIN_LEFT | NP_SGEMM_PATH_MV(M <= 4 ? 4 : M <= 8 ? 8 : 16));
         return NP_OK;
     }
     // blockIdx.z carries the batch index: more than 65535 matrices go in slabs
@@ -3834,6 +3867,7 @@ int np_sgemm_strided_batched_piece(size_t count, size_t whole, size_t M, size_t 
 }
 
 int np_sgemv(size_t M, size_t N, const float *A, const float *x, float *y) {
+    PathScope scope;
     if (M == 0) return NP_OK;
     if (!A || !x || !y) return np::fail(NP_ERR_INVALID, "np_sgemv: null pointer");
     if (M > 0x7fffffffu || N > 0x7fffffffu)
@@ -3851,6 +3885,7 @@ int np_sgemv(size_t M, size_t N, const float *A, const float *x, float *y) {
             const unsigned magic = (unsigned)((0x100000000ull + N - 1) / N);
             sgemv_staged_rows_kernel<<<(unsigned)blocks, 256, lds, np::stream()>>>(A, x, y, M, (unsigned)N, R, magic);
             NP_LAUNCH_CHECK("sgemv_staged_rows_kernel");
+            note_path(NP_SGEMM_PATH_GEMV_STAGED);
             return NP_OK;
         }
     }
@@ -3870,6 +3905,7 @@ int np_sgemv(size_t M, size_t N, const float *A, const float *x, float *y) {
             }
 #undef NP_SR
             NP_LAUNCH_CHECK("sgemv_short_rows_kernel");
+            note_path(NP_SGEMM_PATH_GEMV_SHORT_ROWS | NP_SGEMM_PATH_LANES(L));
             return NP_OK;
         }
     }
@@ -3884,6 +3920,7 @@ int np_sgemv(size_t M, size_t N, const float *A, const float *x, float *y) {
         sgemv_fewrows_chunks_kernel<<<(unsigned)chunks, 256, 0, np::stream()>>>(A, x, (float *)partial.ptr, (unsigned)M, (unsigned)N,
                                                                               (unsigned)chunk_len);
         NP_LAUNCH_CHECK("sgemv_fewrows_chunks_kernel");
+        note_path(NP_SGEMM_PATH_GEMV_FEWROWS_CHUNKS | NP_SGEMM_PATH_FOLD);
         return np_reduce_axis(NP_SUM, (const float *)partial.ptr, M, chunks, 1, y, 0);
     }
     if (M < 2 * target && N >= 16384 && M <= 65535) {   // one wave per row would leave most of the chip idle
@@ -3898,6 +3935,7 @@ int np_sgemv(size_t M, size_t N, const float *A, const float *x, float *y) {
             sgemv_chunks_kernel<<<dim3((unsigned)chunks, (unsigned)M), 256, 0, np::stream()>>>(
                 A, x, (float *)partial.ptr, (unsigned)N, (unsigned)chunk_len);
             NP_LAUNCH_CHECK("sgemv_chunks_kernel");
+            note_path(NP_SGEMM_PATH_GEMV_CHUNKS | NP_SGEMM_PATH_FOLD);
             return np_reduce_axis(NP_SUM, (const float *)partial.ptr, M, chunks, 1, y, 0);
         }
     }
@@ -3905,6 +3943,7 @@ int np_sgemv(size_t M, size_t N, const float *A, const float *x, float *y) {
     sgemv_kernel<<<(unsigned)((M + 3) / 4), 256, 0, np::stream()>>>(A, x, y, (unsigned)M,
                                                                   (unsigned)N, vec);
     NP_LAUNCH_CHECK("sgemv_kernel");
+    note_path(NP_SGEMM_PATH_GEMV_WAVE | (vec ? NP_SGEMM_PATH_GEMV_WAVE_VEC : 0u));
     return NP_OK;
 }
 

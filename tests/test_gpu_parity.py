@@ -923,21 +923,31 @@ def test_axis_reduce_few_outputs_long_axis(shape, axis, hip, oracle):
 
 
 @pytest.mark.parametrize("mn", [(1, 3_000_001), (1, 65536), (10, 500_000), (7, 16385), (200_000, 10), (5000, 1), (4096, 33),
-                                # 2 .. 16 long rows: a workgroup per chunk of x takes all rows (sgemv_fewrows_chunks_kernel, round 5)
+                                # 2 .. 16 long rows: a workgroup per chunk of x takes all rows (sgemv_fewrows_chunks_kernel, round 5);
+                                # 17 and 300 rows: sgemv_chunks_kernel; 1024 rows and more of up to 256 columns: sgemv_short_rows_kernel;
+                                # (20_000, 257): a wave per row (sgemv_kernel)
                                 (2, 1_000_003), (16, 300_001), (3, 65536), (13, 70_002), (17, 200_000),
                                 (300, 70_001), (50_000, 100), (20_000, 256), (20_000, 257), (100_000, 8), (100_000, 9),
                                 # LDS-staged slabs of short rows (M >= 262144, 4 <= N <= 63), incl. a ragged last slab and M * N % 4 != 0
                                 (300_000, 10), (262_144, 4), (262_145, 63), (400_003, 7), (1_000_000, 16), (270_001, 33)])
 def test_sgemv_shapes(mn, hip, oracle):
     """np_sgemv / NDArray_Dot outside the square case: inner products and few long rows (chunked:
-    sgemv_chunks_kernel + fold), many short rows (thread per row), against fp64 and the oracle's
-    OpenBLAS sgemv."""
+    sgemv_chunks_kernel / sgemv_fewrows_chunks_kernel + fold), many short rows (lane groups: sgemv_short_rows_kernel, or slabs
+    through LDS: sgemv_staged_rows_kernel), against fp64 and the oracle's OpenBLAS sgemv.  Which kernel ran is asserted:
+    np_sgemm_debug_last_path against the dispatcher's arithmetic (tests/gemm_family.py: gemv_path) for the CU count at hand."""
+    import ctypes as C
+    from numpower_amd import _lib
     from numpower_amd.ndarray import NDArray
+    from tests import gemm_family as gf
     m, n = mn
     a = synth.uniform((m, n), 37, -1.0, 1.0)
     x = synth.uniform((n,), 38, -1.0, 1.0)
     ga, gx = NDArray.array(a).gpu(), NDArray.array(x).gpu()
     got = NDArray.dot(ga, gx).cpu().numpy()
+    mask, cus = C.c_uint(), C.c_int()
+    _lib.check(_lib.load().np_sgemm_debug_last_path(C.byref(mask)))
+    _lib.check(_lib.load().np_debug_cus(C.byref(cus)))
+    assert mask.value == gf.gemv_path(m, n, cus.value), (gf.describe(mask.value), gf.describe(gf.gemv_path(m, n, cus.value)))
     ref64 = a.astype(np.float64) @ x.astype(np.float64)
     scale = np.abs(a).astype(np.float64) @ np.abs(x).astype(np.float64)
     assert got.shape == (m,)
@@ -991,11 +1001,14 @@ def test_row_reductions_short_rows(cols, hip, oracle):
                                  (2049, 31, 36), (5001, 17, 8), (3001, 12, 132), (2500, 9, 64), (2100, 16, 96), (70_001, 24, 1024),
                                  (2048, 5, 12), (9999, 32, 260), (100_003, 6, 4),
                                  (50_000, 10, 785), (3000, 20, 7), (4099, 16, 33), (2050, 30, 66), (2500, 8, 5),
-                                 # 17 <= M < 2048 against a very long K: the same kernel over K-chunks + a fold (X^T . G)
+                                 # 17 <= M < 2048 against a very long K (X^T . G): the K-chunked forms of that kernel would launch fewer
+                                 # than 59 / 4 workgroups per CU here, and since round 5 thin_to_planner() hands such a launch to the
+                                 # planner: every shape of the next four lines runs the TILED kernels (the K-chunked thin kernels
+                                 # themselves: tests/test_gpu_gemm_exact.py, under np_sgemm_set_variant(-40))
                                  (784, 10, 200_000), (500, 5, 30_001), (100, 17, 16_384), (2047, 3, 20_000), (17, 32, 100_000), (300, 16, 65_537),
-                                 # ... and N = 33..64 there (two 32-column blocks): cluster sums H^T . X, Gram matrices of <= 64 features
+                                 # ... N = 33..64 there (cluster sums H^T . X, Gram matrices of <= 64 features): to the planner as well
                                  (32, 64, 300_000), (64, 64, 100_001), (100, 33, 20_000), (2047, 50, 16_384), (40, 63, 70_000),
-                                 # fewer row tiles than four waves: 128- and 64-thread workgroups
+                                 # fewer row tiles than four waves: to the planner as well
                                  (20, 8, 50_000), (30, 16, 20_000), (32, 32, 65_536), (33, 20, 40_000), (48, 12, 30_000),
                                  # 2048 <= M, too few rows to fill the machine, a long K: the MFMA thin kernel over K-chunks + a fold;
                                  # N = 1 there: the matrix . vector kernel (rows of any alignment)
@@ -1004,12 +1017,22 @@ def test_row_reductions_short_rows(cols, hip, oracle):
 def test_matmul_thin(mnk, hip, oracle):
     """N <= 32: GEMV-with-several-right-hand-sides kernels (sgemm_thin_kernel: lane groups per row of A;
     sgemm_thin_mfma_kernel: one wave = 16 / 32 rows on the MFMA with B through LDS; sgemm_thin_chunks_kernel:
-    few rows, long K) instead of mostly empty 64-wide tiles."""
+    few rows, long K) instead of mostly empty 64-wide tiles.  Which of them ran is asserted: np_sgemm_debug_last_path against
+    the dispatcher's arithmetic (tests/gemm_family.py: path) for the CU count at hand — the whole mask, except that where the
+    shape goes to the planner only TILED is asserted (whether the planner folds K-chunks of its own is its model's business)."""
+    import ctypes as C
+    from numpower_amd import _lib
     from numpower_amd.ndarray import NDArray
+    from tests import gemm_family as gf
     m, n, k = mnk
     a = synth.uniform((m, k), 45, -1.0, 1.0)
     b = synth.uniform((k, n), 46, -1.0, 1.0)
     got = NDArray.matmul(NDArray.array(a).gpu(), NDArray.array(b).gpu()).cpu().numpy()
+    mask, cus = C.c_uint(), C.c_int()
+    _lib.check(_lib.load().np_sgemm_debug_last_path(C.byref(mask)))
+    _lib.check(_lib.load().np_debug_cus(C.byref(cus)))
+    named = gf.path(m, n, k, cus.value)
+    assert (mask.value & ~gf.FOLD if named == gf.TILED else mask.value) == named, (gf.describe(mask.value), gf.describe(named))
     ref64 = a.astype(np.float64) @ b.astype(np.float64)
     scale = np.abs(a).astype(np.float64) @ np.abs(b).astype(np.float64)
     assert got.shape == (m, n)
