@@ -206,3 +206,130 @@ NDArray **NPH_Conv2D_BackwardEx(NDArray *x, NDArray *y, NDArray *filters, const 
     rtns[1] = dx;
     return rtns;
 }
+
+/* ---- the layer: a bias and an activation (hip_dnn.h) ---- */
+
+/* 'r', 't', 's', 'n' or 0 -> np_conv_act, -1 for anything else */
+static int activation_of(char activation) {
+    switch (activation) {
+    case 'r': return NP_ACT_RELU;
+    case 't': return NP_ACT_TANH;
+    case 's': return NP_ACT_SIGMOID;
+    case 'n': case 0: return NP_ACT_NONE;
+    default: return -1;
+    }
+}
+
+/* the layer's own checks, which come before layer_of()'s; bias may be NULL, and so may out and dy (forward).  0 after a raised error */
+static int layer_extras(NDArray *x, NDArray *filters, NDArray *bias, NDArray *out, NDArray *dy, int act) {
+    if (act < 0) {
+        np_ext_throw(NPH_DNN_MSG_ACTIVATION);
+        return 0;
+    }
+    if (bias != NULL && NDArray_NDIM(filters) == 4 && (NDArray_NDIM(bias) != 1 || NDArray_SHAPE(bias)[0] != NDArray_SHAPE(filters)[0])) {
+        np_ext_throw(NPH_DNN_MSG_BIAS);
+        return 0;
+    }
+    if (dy != NULL && (out != NULL || act != NP_ACT_NONE)) {
+        int same = out != NULL && NDArray_NDIM(out) == NDArray_NDIM(dy);
+        for (int d = 0; same && d < NDArray_NDIM(dy); ++d) same = NDArray_SHAPE(out)[d] == NDArray_SHAPE(dy)[d];
+        if (!same) {
+            np_ext_throw(NPH_DNN_MSG_OUT);
+            return 0;
+        }
+    }
+    if (bias != NULL && (NDArray_DEVICE(bias) != NDArray_DEVICE(x) || NDArray_DEVICE(bias) != NDArray_DEVICE(filters))) {
+        np_ext_throw(NPH_DNN_MSG_BIAS_DEVICE);
+        return 0;
+    }
+    if (dy != NULL && out != NULL && NDArray_DEVICE(out) != NDArray_DEVICE(dy)) {
+        np_ext_throw(NPH_DNN_MSG_DEVICE);
+        return 0;
+    }
+    return 1;
+}
+
+/* a new 1-d GPU array of n floats */
+static NDArray *empty1_on_gpu(size_t n) {
+    int *shape = (int *) NPH_ALLOC(sizeof(int));
+    if (shape == NULL) return NULL;
+    shape[0] = (int) n;
+    NDArray *rtn = NDArray_Empty(shape, 1, "float32", NDARRAY_DEVICE_GPU);
+    if (NPH_SHAPE_IS_COPIED) NPH_RELEASE(shape);
+    return rtn;
+}
+
+NDArray *NPH_Conv2D_LayerForward(NDArray *x, NDArray *filters, NDArray *bias, const int stride[2], const int padding[2], const int dilation[2],
+                                 char activation) {
+    nph_layer l;
+    const nph_geometry g = geometry_of(stride, padding, dilation);
+    const int act = activation_of(activation);
+    if (x == NULL || filters == NULL || !layer_extras(x, filters, bias, NULL, NULL, act) || !layer_of(x, NULL, filters, &g, &l)) return NULL;
+    size_t oh = 0, ow = 0;
+    if (l.N < 1 || l.C < 1 || l.F < 1) {
+        np_ext_throw("dnn_conv2d: an operand has no elements");
+        return NULL;
+    }
+    if (np_conv2d_shape_ex(l.H, l.W, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw, (size_t) g.sh, (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, &oh, &ow) != NP_OK) {
+        np_ext_throw_last();
+        return NULL;
+    }
+    NDArray *rtn = empty4_on_gpu(l.N, l.F, oh, ow);
+    if (rtn == NULL) return NULL;
+    if (np_conv2d_forward_act(NDArray_FDATA(x), NDArray_FDATA(filters), bias != NULL ? NDArray_FDATA(bias) : NULL, l.N, l.C, l.H, l.W, l.F, l.kh, l.kw,
+                              (size_t) g.ph, (size_t) g.pw, (size_t) g.sh, (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, act, NDArray_FDATA(rtn)) != NP_OK) {
+        np_ext_throw_last();
+        NDArray_FREE(rtn);
+        return NULL;
+    }
+    return rtn;
+}
+
+NDArray **NPH_Conv2D_LayerBackward(NDArray *x, NDArray *out, NDArray *dy, NDArray *filters, const int stride[2], const int padding[2],
+                                   const int dilation[2], char activation, int use_bias) {
+    nph_layer l;
+    const nph_geometry g = geometry_of(stride, padding, dilation);
+    const int act = activation_of(activation);
+    if (x == NULL || dy == NULL || filters == NULL) return NULL;
+    if (!layer_extras(x, filters, NULL, out, dy, act) || !layer_of(x, dy, filters, &g, &l)) return NULL;
+    if (NDArray_NUMELEMENTS(x) < 1 || NDArray_NUMELEMENTS(filters) < 1) {
+        np_ext_throw("dnn_conv2d: an operand has no elements");
+        return NULL;
+    }
+    const size_t P = (size_t) NDArray_SHAPE(dy)[2] * (size_t) NDArray_SHAPE(dy)[3];
+    NDArray *dw = empty4_on_gpu(l.F, l.C, l.kh, l.kw), *dx = empty4_on_gpu(l.N, l.C, l.H, l.W), *db = use_bias ? empty1_on_gpu(l.F) : NULL;
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 3);
+    void *dz = NULL;   /* pool scratch, only with an activation: dz = dy otherwise */
+    int ok = dw != NULL && dx != NULL && rtns != NULL && (db != NULL || !use_bias);
+    if (ok && act != NP_ACT_NONE && np_malloc(&dz, l.N * l.F * P * sizeof(float)) != NP_OK) {
+        np_ext_throw_last();
+        dz = NULL;
+        ok = 0;
+    }
+    const float *grad = dz != NULL ? (const float *) dz : NDArray_FDATA(dy);
+    if (ok && (act != NP_ACT_NONE || use_bias) &&
+        np_conv2d_backward_act(out != NULL ? NDArray_FDATA(out) : NULL, NDArray_FDATA(dy), l.N, l.F, P, act, (float *) dz,
+                               db != NULL ? NDArray_FDATA(db) : NULL) != NP_OK) {
+        np_ext_throw_last();
+        ok = 0;
+    }
+    if (ok && (np_conv2d_backward_filter_ex(NDArray_FDATA(x), grad, l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw, (size_t) g.sh,
+                                            (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, NDArray_FDATA(dw)) != NP_OK ||
+               np_conv2d_backward_data_ex(grad, NDArray_FDATA(filters), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw, (size_t) g.sh,
+                                          (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, NDArray_FDATA(dx)) != NP_OK)) {
+        np_ext_throw_last();
+        ok = 0;
+    }
+    if (dz != NULL) np_free(dz);   /* released on every path; the pool is stream-ordered: safe right behind the launches that read it */
+    if (!ok) {
+        if (dw != NULL) NDArray_FREE(dw);
+        if (dx != NULL) NDArray_FREE(dx);
+        if (db != NULL) NDArray_FREE(db);
+        if (rtns != NULL) NPH_RELEASE(rtns);
+        return NULL;
+    }
+    rtns[0] = dw;
+    rtns[1] = dx;
+    rtns[2] = db;
+    return rtns;
+}

@@ -74,6 +74,27 @@ struct NDArray *NPH_Conv2D_ForwardEx(struct NDArray *x, struct NDArray *filters,
 struct NDArray **NPH_Conv2D_BackwardEx(struct NDArray *x, struct NDArray *y, struct NDArray *filters, const int stride[2], const int padding[2],
                                        const int dilation[2]);
 
+/* ---- the layer: a bias per filter and an activation (np_conv2d_forward_act / np_conv2d_backward_act of include/np_hip.h) ----
+ * The reference's signature names `activation` and `use_bias`, has no bias operand and ignores both; the functions above keep
+ * ignoring them.  These two are what a binding with a bias argument calls.  activation: 'r' relu, 't' tanh, 's' sigmoid, 'n' or 0
+ * none.  y = act(conv(x, filters) + bias[f]): the bias is ONE fp32 add after the reduction, the activation runs in the forward
+ * kernel's store loop.  The backward pass takes `out`, the forward RESULT (gradients are expressed through the output, a layer
+ * keeps no pre-activation), and dy, the gradient of that result: dz = dy . act'(out) goes to pool scratch, is released on every
+ * path, and dW and dX are the Ex gradients of dz; db[f] = sum_{n,i,j} dz.
+ * The messages: these four, checked in this order BEFORE the ones above (the last needs its operands' devices): */
+#define NPH_DNN_MSG_ACTIVATION "dnn_conv2d: unknown activation: 'r' (relu), 't' (tanh), 's' (sigmoid), 'n' or 0 (none)"
+#define NPH_DNN_MSG_BIAS "dnn_conv2d: the bias must be 1-dimensional with one element per filter (F,)"
+#define NPH_DNN_MSG_OUT "dnn_conv2d_backward: out, the forward result, must have the shape of the gradient"
+#define NPH_DNN_MSG_BIAS_DEVICE "dnn_conv2d: the bias must be on the device of the input and the filters"
+
+/* y (N, F, oh, ow), a new GPU array; bias: 1-D (F,) on the GPU, or NULL */
+struct NDArray *NPH_Conv2D_LayerForward(struct NDArray *x, struct NDArray *filters, struct NDArray *bias, const int stride[2], const int padding[2],
+                                        const int dilation[2], char activation);
+/* A vector of THREE: rtn[0] = dW, rtn[1] = dX as NPH_Conv2D_BackwardEx, rtn[2] = db (F,), NULL without use_bias.  `out` may be
+ * NULL when the activation is none. */
+struct NDArray **NPH_Conv2D_LayerBackward(struct NDArray *x, struct NDArray *out, struct NDArray *dy, struct NDArray *filters, const int stride[2],
+                                          const int padding[2], const int dilation[2], char activation, int use_bias);
+
 #ifdef __cplusplus
 }
 #endif

@@ -627,6 +627,43 @@ int np_conv2d_backward_data_ex(const float *dy, const float *w, size_t N, size_t
 int np_conv2d_backward_filter_ex(const float *x, const float *dy, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
                                  size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, float *dw_out);
 
+/* ---- convolution layers with a bias and an activation (np_dnn.hip; DESIGN.md "dnn_conv2d") ------------
+ * np_conv2d_forward_act is np_conv2d_forward_ex with an epilogue in the same kernel, applied to every output while it is still
+ * in registers.  With acc the fmaf chain of np_conv2d_forward_ex, untouched, for an output of filter f:
+ *   v = bias ? acc + bias[f] : acc        ONE fp32 add after the chain: the bias is NOT the chain's start value
+ *   y = act(v)
+ *   NP_ACT_NONE     v
+ *   NP_ACT_RELU     (v <= 0) ? +0.0f : v          a NaN stays NaN, -0.0 becomes +0.0
+ *   NP_ACT_TANH     tanhf(v)                      the function np_unary(NP_TANH) evaluates: bit for bit the unfused result
+ *   NP_ACT_SIGMOID  1 / (1 + exp(-v))             with the exp of np_unary(NP_EXP): 0 and 1 at -Inf and +Inf, NaN at NaN
+ * bias: F floats, or NULL for no bias; bias[f] is read for f < F only.  A NaN in bias[f] reaches exactly the outputs of filter
+ * f.  With bias == NULL and NP_ACT_NONE the call launches the same kernels as np_conv2d_forward_ex and returns the same bits.
+ *
+ * np_conv2d_backward_act is the backward pass of that epilogue: one streaming kernel over y (the forward RESULT) and dy, both
+ * (N, F, P) with P = oh.ow, and a fold.  The derivative is expressed through the output, so a layer keeps y only:
+ *   dz[n,f,i,j] = dy . act'(y)
+ *   NP_ACT_RELU     (y <= 0) ? +0.0f : dy         a select, not a product: a NaN or Inf in dy over y <= 0 reaches nothing; a NaN y
+ *                                                 passes dy
+ *   NP_ACT_TANH     dy * (1 - y*y)                each operation rounded on its own, in this order
+ *   NP_ACT_SIGMOID  dy * ((1 - y) * y)
+ *   db[f]       = sum_{n,i,j} dz[n,f,i,j]
+ * With NP_ACT_NONE dz = dy: dz is NOT written (it may be NULL, and so may y) and only db is produced.  With db == NULL only dz is
+ * written.  dW and dX of the layer are np_conv2d_backward_filter_ex / np_conv2d_backward_data_ex on dz.
+ * The summation order of db: the M = N.P elements of filter f, indexed m = n.P + i.ow + j, are cut into S slices of L elements
+ * (S and L from (N, F, P) alone); inside a slice lane t of 256 adds elements t, t + 256, ... in ascending order from +0.0f, the 256
+ * lane sums are folded in a fixed tree (lanes 32, 16, 8, 4, 2, 1 apart inside a wave of 64, then the four waves in order), the
+ * slices go to pool scratch and a second kernel adds them in slice order (S == 1 writes db directly).  No float atomics; db is
+ * bit-identical from run to run, and dz of an image does not depend on the batch it is in.  db of a batch is not the sum of the
+ * dbs of its images.
+ * dz may not overlap y or dy; db may not overlap anything.
+ * Convention as above: pointers are checked first, then the shape, then work begins.  NP_ERR_INVALID before any device work:
+ * everything np_conv2d_forward_ex refuses; an unknown act; dz and db both NULL; dz (or y) NULL with an activation; an extent
+ * of zero; N.F.P at 2^31 or more. */
+typedef enum np_conv_act { NP_ACT_NONE = 0, NP_ACT_RELU = 1, NP_ACT_TANH = 2, NP_ACT_SIGMOID = 3 } np_conv_act;
+int np_conv2d_forward_act(const float *x, const float *w, const float *bias, size_t N, size_t C, size_t H, size_t W, size_t F,
+                          size_t kh, size_t kw, size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, int act, float *y);
+int np_conv2d_backward_act(const float *y, const float *dy, size_t N, size_t F, size_t P, int act, float *dz, float *db);
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

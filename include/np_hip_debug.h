@@ -149,6 +149,10 @@ int np_debug_dnn_last_path(int *host_tm, int *host_slices);
 /* tests / tools: the form of the gather that call compiled to: 0 unit (stride 1, dilation 1), 1 strided / dilated window,
  * 2 dilated input (the data gradient of a strided layer). */
 int np_debug_dnn_last_form(int *host_form);
+/* tests / tools: the epilogue of the last forward launch of the process (np_conv_act and whether a bias was added; 0, 0 for the
+ * plain kernels, the data gradient included) and the number of slices S of the last np_conv2d_backward_act call that produced
+ * a db (1: written directly, no fold kernel).  (0, 0, 0) before any launch. */
+int np_debug_dnn_last_epilogue(int *act, int *has_bias, int *bias_slices);
 /* tests / tools: which kernel families the last np_reduce_axis or np_reduce_all(_dev) call of the process launched, the calls it
  * makes on its own partials included: the OR of the NP_REDUCE_PATH_ bits below (0 = none yet).  A plain process global, cleared
  * at the top of those entry points; calls the library makes itself (split-K GEMM folds, chain partials) overwrite it too. */

@@ -394,6 +394,18 @@ NDArray **NDArrayDNN_Conv2D_Backward(NDArray *input, NDArray *y, NDArray *filter
  * _DILATION, _PADDING, _EFFECTIVE and _STRIDED_GRADIENT in place of the window and gradient messages. */
 NDArray *NDArrayDNN_Conv2D_ForwardEx(NDArray *x, NDArray *filters, const int *stride, const int *padding, const int *dilation);
 NDArray **NDArrayDNN_Conv2D_BackwardEx(NDArray *input, NDArray *y, NDArray *filters, const int *stride, const int *padding, const int *dilation);
+/* The layer with a bias per filter and an activation: y = act(conv(x, filters) + bias[f]), the bias ONE fp32 add after the
+ * reduction, the activation applied in the forward kernel (np_conv2d_forward_act).  bias: a 1-D GPU array (F,) or NULL;
+ * activation: 'r' relu, 't' tanh, 's' sigmoid, 'n' or 0 none.  _LayerBackward takes `out`, the forward result (gradients are
+ * expressed through the output; NULL is allowed without an activation), and dy, the gradient of that result, and returns a
+ * malloc'd vector of THREE: dW, dX (the reference's order) and db (F,), which is NULL without use_bias.  Views are made
+ * contiguous; NPH_Conv2D_LayerForward / _LayerBackward do the work.  Errors as for the Ex functions, and before them
+ * NPH_DNN_MSG_ACTIVATION, _BIAS, _OUT and _BIAS_DEVICE.  The reference-signature functions above still ignore `activation` and
+ * `use_bias`. */
+NDArray *NDArrayDNN_Conv2D_LayerForward(NDArray *x, NDArray *filters, NDArray *bias, const int *stride, const int *padding, const int *dilation,
+                                        char activation);
+NDArray **NDArrayDNN_Conv2D_LayerBackward(NDArray *input, NDArray *out, NDArray *dy, NDArray *filters, const int *stride, const int *padding,
+                                          const int *dilation, char activation, int use_bias);
 
 #ifdef __cplusplus
 }

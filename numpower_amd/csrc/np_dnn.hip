@@ -33,10 +33,24 @@
 // resp. (F, kh, kw) alone — not on N, the position of the pixel, TM or any device state — so the same image gives the same bits
 // at any batch size and position.  For dW the chain runs over jg inside a slice and the slices are then added in order; S is a
 // function of the extents alone.  Results are bit-identical from run to run.
+//
+// The layer (np_conv2d_forward_act, np_conv2d_backward_act).  The forward kernel has a second store loop, selected at compile
+// time (EPI) for gather forms 0 and 1: v = acc + bias[f] — ONE fp32 add after the chain, not the chain's start value — and
+// y = act(v), the activation a wave-uniform switch taken once, around one store loop each.  The plain instantiations, their
+// kernel argument and their instruction stream are what they were: the epilogue's operands travel in EpiArgs, which only the EPI forms read.
+// tanh and sigmoid evaluate the functions of np_elementwise_ops.h (tanhf; fast_exp), so a fused result is bit for bit the
+// unfused one.  The backward pass of the activation is one streaming kernel over y and dy (N, F, P): dz = dy . act'(y), the
+// derivative expressed through the OUTPUT, and db[f] = sum_{n,pixel} dz.  A workgroup owns one filter f and one slice of the
+// flattened index m = n.P + pixel; a lane adds its elements m0 + lane, m0 + lane + 256, ... in ascending order, the workgroup
+// folds its 256 lanes in a fixed tree, slices go to pool scratch and dnn_bias_fold_kernel adds them in slice order (S == 1
+// writes db directly).  No float atomics; S is a function of (N, F, P) alone; bit-identical from run to run.  The walk decodes
+// m into (n, pixel) ONCE per lane and then steps by 256 = q.P + r with one compare: no division per element, consecutive lanes
+// read consecutive addresses inside an (n, f) plane, whatever P is.
 #include <limits.h>
 
 #include <type_traits>
 
+#include "np_elementwise_ops.h"   // the bodies of NP_TANH and NP_EXP; fp contraction is off in a unit that includes it
 #include "np_internal.h"
 
 namespace {
@@ -49,9 +63,15 @@ constexpr int kAStr = kTK + 1, kBStr = kTN + 1;             // LDS row strides (
 // dW: a slice is at least kWgradMinSteps steps long, slices stop once tiles x S reaches kWgradTargetGroups workgroups
 constexpr int kWgradMinSteps = 8, kWgradTargetGroups = 512, kWgradMaxSlices = 256;
 
+// db (tests/test_gpu_dnn_act.py mirrors the rule): the M = N.P elements of a filter are cut into S slices,
+//   want = min(M / kActMinSlice, ceil(kActTargetGroups / F), kActMaxSlices), at least 1
+//   L = ceil(M / want) rounded up to a multiple of kActBlock,  S = ceil(M / L)
+constexpr int kActBlock = 256, kActMinSlice = 4096, kActTargetGroups = 2048, kActMaxSlices = 256;
+
 typedef float dnn_v16f __attribute__((ext_vector_type(16)));
 
 int g_dnn_last_tm = 0, g_dnn_last_slices = 0, g_dnn_last_form = 0;
+int g_dnn_last_act = 0, g_dnn_last_has_bias = 0, g_dnn_last_bias_slices = 0;
 
 // what the unit form reads: its kernel arguments, and with them its instruction stream, are what they were before the general gather
 struct ConvCore {
@@ -69,6 +89,34 @@ struct ConvArgs : ConvCore {
 // a kernel's argument: forms 1 and 2 read the whole of ConvArgs
 template <int FORM>
 using KernelArgs = std::conditional_t<FORM == 0, ConvCore, ConvArgs>;
+
+// the same with the epilogue's operands behind it: the argument of the EPI instantiations alone
+template <int FORM>
+struct EpiArgs : KernelArgs<FORM> {
+    const float *bias;   // F floats or nullptr
+    int act;             // np_conv_act
+};
+
+template <int FORM, bool EPI>
+using FpropArgs = std::conditional_t<EPI, EpiArgs<FORM>, KernelArgs<FORM>>;
+
+// y = act(v).  relu: a NaN stays NaN, -0.0 becomes +0.0; sigmoid: 0 and 1 at -+Inf, NaN at NaN
+template <int ACT>
+__device__ __forceinline__ float act_apply(float v) {
+    if constexpr (ACT == NP_ACT_RELU) return (v <= 0.0f) ? 0.0f : v;
+    if constexpr (ACT == NP_ACT_TANH) return unary_apply<NP_TANH>(v, 0.0f, 0.0f);
+    if constexpr (ACT == NP_ACT_SIGMOID) return 1.0f / (1.0f + unary_apply<NP_EXP>(-v, 0.0f, 0.0f));
+    return v;
+}
+
+// dz = dy . act'(y) through the output y.  relu is a select: a NaN y passes dy, a dy over y <= 0 reaches nothing
+template <int ACT>
+__device__ __forceinline__ float act_grad(float y, float dy) {
+    if constexpr (ACT == NP_ACT_RELU) return (y <= 0.0f) ? 0.0f : dy;
+    if constexpr (ACT == NP_ACT_TANH) return dy * (1.0f - y * y);
+    if constexpr (ACT == NP_ACT_SIGMOID) return dy * ((1.0f - y) * y);
+    return dy;
+}
 
 int form_of(const ConvArgs &a) { return (a.lh != 1 || a.lw != 1) ? 2 : (a.sh != 1 || a.sw != 1 || a.dh != 1 || a.dw != 1) ? 1 : 0; }
 
@@ -156,9 +204,32 @@ __device__ __forceinline__ float gather(const KernelArgs<FORM> &p, bool pixel, l
     return 0.0f;
 }
 
+// the layer's store loop for one activation: v = acc + bias[f] (one add after the chain), y = act(v).  fw is the first row of
+// the wave's blocks; a row's bias is read once, and only for rows below F; yb[nj] == nullptr: the column lies beyond N.P
+template <int TM, int ACT>
+__device__ __forceinline__ void epi_store(const dnn_v16f (&acc)[Tile<TM>::MI][Tile<TM>::NJ], float *const (&yb)[Tile<TM>::NJ], const float *bias, int fw,
+                                          int kq, int F, int P) {
+    using T = Tile<TM>;
+    const bool has_bias = bias != nullptr;
+#pragma unroll
+    for (int mi = 0; mi < T::MI; ++mi)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int f = fw + mi * 32 + acc_row(r, kq);
+            if (f >= F) continue;
+            const float b = has_bias ? bias[f] : 0.0f;
+#pragma unroll
+            for (int nj = 0; nj < T::NJ; ++nj) {
+                const float v = has_bias ? acc[mi][nj][r] + b : acc[mi][nj][r];
+                if (yb[nj]) yb[nj][(size_t)f * P] = act_apply<ACT>(v);
+            }
+        }
+}
+
 // grid.x = F-tiles x pixel-tiles, F-tiles fastest: neighbouring workgroups gather the same pixels
-template <int TM, int FORM>
-__global__ __launch_bounds__(256, 2) void dnn_fprop_kernel(const KernelArgs<FORM> p) {
+template <int TM, int FORM, bool EPI = false>
+__global__ __launch_bounds__(256, 2) void dnn_fprop_kernel(const FpropArgs<FORM, EPI> p) {
+    static_assert(!EPI || FORM != 2, "the data gradient has no bias and no activation");
     using T = Tile<TM>;
     __shared__ float As[TM * kAStr];
     __shared__ float Bs[kTK * kBStr];
@@ -211,6 +282,26 @@ __global__ __launch_bounds__(256, 2) void dnn_fprop_kernel(const KernelArgs<FORM
     }
 
     const int i = lane & 31, kq = lane >> 5;
+    if constexpr (EPI) {
+        // the layer's store loop: one add after the chain, then the activation.  A lane's rows are the same for every nj: their
+        // bias is read once, and only for rows below F (the tile rows the K loop zero-filled never touch the array)
+        float *yb[T::NJ];   // nullptr: the column lies beyond N.P
+#pragma unroll
+        for (int nj = 0; nj < T::NJ; ++nj) {
+            const int col = j0 + (wn * T::NJ + nj) * 32 + i;
+            const int n = col / p.P, pix = col - n * p.P;
+            yb[nj] = col < p.NP ? p.out + ((size_t)n * p.F * p.P + pix) : nullptr;
+        }
+        // one compact loop per activation: the switch is taken once, not once per output
+        const int fw = f0 + wm * T::MI * 32;
+        switch (p.act) {
+        case NP_ACT_RELU: epi_store<TM, NP_ACT_RELU>(acc, yb, p.bias, fw, kq, p.F, p.P); break;
+        case NP_ACT_TANH: epi_store<TM, NP_ACT_TANH>(acc, yb, p.bias, fw, kq, p.F, p.P); break;
+        case NP_ACT_SIGMOID: epi_store<TM, NP_ACT_SIGMOID>(acc, yb, p.bias, fw, kq, p.F, p.P); break;
+        default: epi_store<TM, NP_ACT_NONE>(acc, yb, p.bias, fw, kq, p.F, p.P); break;
+        }
+        return;
+    }
 #pragma unroll
     for (int nj = 0; nj < T::NJ; ++nj) {
         const int col = j0 + (wn * T::NJ + nj) * 32 + i;
@@ -318,6 +409,65 @@ __global__ __launch_bounds__(256) void dnn_wgrad_fold_kernel(const float *__rest
     float acc = part[idx];
     for (int s = 1; s < slices; ++s) acc += part[(size_t)s * n + idx];
     dw[idx] = acc;
+}
+
+// grid.x = F, grid.y = slices.  Workgroup (f, s) walks m = n.P + pixel over [s.slice_len, (s + 1).slice_len) of filter f's M = N.P
+// elements: lane t takes m0 + t, m0 + t + 256, ... and adds them in that order.  (n, pixel) is decoded once; a step of
+// 256 = q.P + r moves the address by q planes of the batch and r pixels, and by one more plane when the pixel wraps.
+// dz == nullptr: no dz is written; out == nullptr: no sum is formed.  out[s.F + f] is the workgroup's sum (out is db when S == 1).
+template <int ACT>
+__global__ __launch_bounds__(kActBlock) void dnn_act_grad_kernel(const float *__restrict__ y, const float *__restrict__ dy, float *__restrict__ dz,
+                                                                  float *__restrict__ out, int F, int P, unsigned M, unsigned slice_len) {
+    __shared__ float lds4[4];
+    const int f = (int)blockIdx.x, tid = (int)threadIdx.x;
+    // M < 2^31 and slice_len <= M + 255: every sum below fits 32 unsigned bits
+    const unsigned m0 = blockIdx.y * slice_len, m1 = (M - m0 < slice_len) ? M : m0 + slice_len, mt = m0 + (unsigned)tid;
+    const unsigned n0 = mt / (unsigned)P;
+    int pix = (int)(mt - n0 * (unsigned)P);
+    const int q = kActBlock / P, r = kActBlock - q * P;   // uniform
+    const size_t plane = (size_t)F * P, step = (size_t)q * plane + r, wrap = plane - P;
+    size_t idx = (size_t)n0 * plane + (size_t)f * P + pix;
+    float sum = 0.0f;
+    // four elements in flight per lane; an element is loaded, and its address used, only where its index is below m1 <= M.
+    // m is the element's index minus m1: negative inside the slice
+    for (long long m = (long long)mt - (long long)m1; m < 0; m += 4 * kActBlock) {
+        size_t at[4];
+        float g[4], yv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            at[u] = idx;
+            idx += step, pix += r;
+            if (pix >= P) pix -= P, idx += wrap;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool in = m + u * kActBlock < 0;
+            g[u] = in ? dy[at[u]] : 0.0f;
+            yv[u] = 1.0f;
+            if constexpr (ACT != NP_ACT_NONE) yv[u] = in ? y[at[u]] : 1.0f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (m + u * kActBlock < 0) {
+                const float d = act_grad<ACT>(yv[u], g[u]);
+                if constexpr (ACT != NP_ACT_NONE)
+                    if (dz) dz[at[u]] = d;
+                sum += d;
+            }
+        }
+    }
+    if (!out) return;
+    sum = np::dev::block_reduce<NP_SUM>(sum, lds4);   // lanes 32 apart, 16, ..., 1, then the four waves in order
+    if (tid == 0) out[(size_t)blockIdx.y * F + f] = sum;
+}
+
+// db[f] = part[0][f] + part[1][f] + ... in slice order
+__global__ __launch_bounds__(256) void dnn_bias_fold_kernel(const float *__restrict__ part, float *__restrict__ db, unsigned F, int slices) {
+    const unsigned f = blockIdx.x * 256u + threadIdx.x;
+    if (f >= F) return;
+    float acc = part[f];
+    for (int s = 1; s < slices; ++s) acc += part[(size_t)s * F + f];
+    db[f] = acc;
 }
 
 template <int FORM>
@@ -438,6 +588,76 @@ int launch_fprop(const ConvArgs &a) {
     g_dnn_last_tm = tm;
     g_dnn_last_slices = 0;
     g_dnn_last_form = form;
+    g_dnn_last_act = g_dnn_last_has_bias = 0;
+    return NP_OK;
+}
+
+template <int FORM>
+void launch_fprop_epi_form(int tm, dim3 grid, dim3 block, const ConvArgs &a, const float *bias, int act) {
+    EpiArgs<FORM> e;
+    static_cast<KernelArgs<FORM> &>(e) = a;
+    e.bias = bias;
+    e.act = act;
+    if (tm == kTMSmall) dnn_fprop_kernel<kTMSmall, FORM, true><<<grid, block, 0, np::stream()>>>(e);
+    else if (tm == kTMMid) dnn_fprop_kernel<kTMMid, FORM, true><<<grid, block, 0, np::stream()>>>(e);
+    else dnn_fprop_kernel<kTMLarge, FORM, true><<<grid, block, 0, np::stream()>>>(e);
+}
+
+// the forward pass with the layer's epilogue: a bias, an activation or both (form 0 or 1)
+int launch_fprop_epi(const ConvArgs &a, const float *bias, int act) {
+    const int tm = pick_tm((size_t)a.F);
+    const size_t tiles = (((size_t)a.F + tm - 1) / tm) * (((size_t)a.NP + kTN - 1) / kTN);
+    if (tiles >= kLim) return np::fail(NP_ERR_INVALID, "np_conv2d: %zu tiles are more than one launch holds", tiles);
+    const dim3 grid((unsigned)tiles), block(256);
+    const int form = form_of(a);
+    if (form == 0) launch_fprop_epi_form<0>(tm, grid, block, a, bias, act);
+    else launch_fprop_epi_form<1>(tm, grid, block, a, bias, act);
+    NP_LAUNCH_CHECK("dnn_fprop_kernel");
+    g_dnn_last_tm = tm;
+    g_dnn_last_slices = 0;
+    g_dnn_last_form = form;
+    g_dnn_last_act = act;
+    g_dnn_last_has_bias = bias != nullptr;
+    return NP_OK;
+}
+
+// db's launch shape, from the extents alone (the rule next to kAct*)
+struct ActGradPlan {
+    size_t slice_len, slices;
+};
+
+ActGradPlan plan_act_grad(size_t F, size_t M) {
+    size_t want = M / kActMinSlice, fill = (kActTargetGroups + F - 1) / F;
+    if (want > fill) want = fill;
+    if (want > (size_t)kActMaxSlices) want = kActMaxSlices;
+    if (want < 1) want = 1;
+    ActGradPlan pl;
+    pl.slice_len = ((M + want - 1) / want + kActBlock - 1) / kActBlock * kActBlock;
+    pl.slices = (M + pl.slice_len - 1) / pl.slice_len;
+    return pl;
+}
+
+template <int ACT>
+void launch_act_grad_as(dim3 grid, const float *y, const float *dy, float *dz, float *out, int F, int P, unsigned M, unsigned slice_len) {
+    dnn_act_grad_kernel<ACT><<<grid, dim3(kActBlock), 0, np::stream()>>>(y, dy, dz, out, F, P, M, slice_len);
+}
+
+// out is db (one slice), the slices' scratch, which is then folded into db, or nullptr (no db wanted)
+int launch_act_grad(const ActGradPlan &pl, const float *y, const float *dy, float *dz, float *out, float *db, size_t F, size_t P, size_t M, int act) {
+    const dim3 grid((unsigned)F, (unsigned)pl.slices);
+    const unsigned len = (unsigned)pl.slice_len;
+    if (act == NP_ACT_RELU) launch_act_grad_as<NP_ACT_RELU>(grid, y, dy, dz, out, (int)F, (int)P, (unsigned)M, len);
+    else if (act == NP_ACT_TANH) launch_act_grad_as<NP_ACT_TANH>(grid, y, dy, dz, out, (int)F, (int)P, (unsigned)M, len);
+    else if (act == NP_ACT_SIGMOID) launch_act_grad_as<NP_ACT_SIGMOID>(grid, y, dy, dz, out, (int)F, (int)P, (unsigned)M, len);
+    else launch_act_grad_as<NP_ACT_NONE>(grid, y, dy, nullptr, out, (int)F, (int)P, (unsigned)M, len);
+    NP_LAUNCH_CHECK("dnn_act_grad_kernel");
+    if (db) {
+        if (pl.slices > 1) {
+            dnn_bias_fold_kernel<<<dim3((unsigned)((F + 255) / 256)), dim3(256), 0, np::stream()>>>(out, db, (unsigned)F, (int)pl.slices);
+            NP_LAUNCH_CHECK("dnn_bias_fold_kernel");
+        }
+        g_dnn_last_bias_slices = (int)pl.slices;
+    }
     return NP_OK;
 }
 
@@ -590,6 +810,46 @@ int np_conv2d_backward_filter_ex(const float *x, const float *dy, size_t N, size
     a.w = dy;
     a.out = pl.slices > 1 ? (float *)part.ptr : dw_out;
     return launch_wgrad(a, pl, (const float *)part.ptr, dw_out);
+}
+
+int np_conv2d_forward_act(const float *x, const float *w, const float *bias, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh,
+                          size_t kw, size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, int act, float *y) {
+    if (!x || !w || !y) return np::fail(NP_ERR_INVALID, "np_conv2d_forward_act: null pointer");
+    ConvArgs a = {};
+    if (int rc = check_layer_ex("np_conv2d_forward_act", N, C, H, W, F, kh, kw, ph, pw, sh, sw, dh, dw, a)) return rc;
+    if (act < NP_ACT_NONE || act > NP_ACT_SIGMOID) return np::fail(NP_ERR_INVALID, "np_conv2d_forward_act: unknown activation %d", act);
+    if (int rc = np::ensure_init()) return rc;
+    a.x = x;
+    a.w = w;
+    a.out = y;
+    if (!bias && act == NP_ACT_NONE) return launch_fprop(a);   // the plain kernels, the plain bits
+    return launch_fprop_epi(a, bias, act);
+}
+
+int np_conv2d_backward_act(const float *y, const float *dy, size_t N, size_t F, size_t P, int act, float *dz, float *db) {
+    if (!dy) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_act: null pointer");
+    if (!dz && !db) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_act: null pointer: dz and db are both null, nothing is asked for");
+    if (N < 1 || F < 1 || P < 1) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_act: every extent must be at least 1");
+    if (mul_lim(mul_lim(N, F), P) >= kLim) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_act: the arrays have 2^31 elements or more");
+    if (act < NP_ACT_NONE || act > NP_ACT_SIGMOID) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_act: unknown activation %d", act);
+    if (act != NP_ACT_NONE && (!y || !dz))
+        return np::fail(NP_ERR_INVALID, "np_conv2d_backward_act: null pointer: an activation needs y and dz");
+    if (act == NP_ACT_NONE && !db) return NP_OK;   // dz = dy is not written and no sum is wanted: nothing to do
+    if (int rc = np::ensure_init()) return rc;
+    const ActGradPlan pl = plan_act_grad(F, N * P);
+    np::Scratch part;   // released on every path below
+    if (db && pl.slices > 1)
+        if (int rc = part.alloc(pl.slices * F * sizeof(float))) return rc;
+    float *out = !db ? nullptr : pl.slices > 1 ? (float *)part.ptr : db;
+    return launch_act_grad(pl, y, dy, dz, out, db, F, P, N * P, act);
+}
+
+int np_debug_dnn_last_epilogue(int *act, int *has_bias, int *bias_slices) {
+    if (!act || !has_bias || !bias_slices) return np::fail(NP_ERR_INVALID, "np_debug_dnn_last_epilogue: null pointer");
+    *act = g_dnn_last_act;
+    *has_bias = g_dnn_last_has_bias;
+    *bias_slices = g_dnn_last_bias_slices;
+    return NP_OK;
 }
 
 }  // extern "C"

@@ -66,4 +66,37 @@ NDArray **NDArrayDNN_Conv2D_BackwardEx(NDArray *input, NDArray *y, NDArray *filt
     return cf.arr ? NPH_Conv2D_BackwardEx(cx.arr, cy.arr, cf.arr, stride, padding, dilation) : nullptr;
 }
 
+// The layer with a bias per filter (1-D (F,), or nullptr) and an activation ('r', 't', 's', 'n' or 0): what a binding with a bias
+// argument calls.  The reference-signature functions at the top keep ignoring `activation` and `use_bias`.
+NDArray *NDArrayDNN_Conv2D_LayerForward(NDArray *x, NDArray *filters, NDArray *bias, const int *stride, const int *padding, const int *dilation,
+                                        char activation) {
+    if (!x || !filters) return nullptr;
+    if (!on_gpu(x) || !on_gpu(filters) || (bias && !on_gpu(bias))) return NPH_Conv2D_LayerForward(x, filters, bias, stride, padding, dilation, activation);
+    Operand cx(x);
+    if (!cx.arr) return nullptr;
+    Operand cf(filters);
+    if (!cf.arr) return nullptr;
+    if (!bias) return NPH_Conv2D_LayerForward(cx.arr, cf.arr, nullptr, stride, padding, dilation, activation);
+    Operand cb(bias);
+    return cb.arr ? NPH_Conv2D_LayerForward(cx.arr, cf.arr, cb.arr, stride, padding, dilation, activation) : nullptr;
+}
+
+// out: the forward result (may be nullptr without an activation); dy: its gradient.  A malloc'd vector of three: dW, dX and db
+// (nullptr without use_bias).
+NDArray **NDArrayDNN_Conv2D_LayerBackward(NDArray *input, NDArray *out, NDArray *dy, NDArray *filters, const int *stride, const int *padding,
+                                          const int *dilation, char activation, int use_bias) {
+    if (!input || !dy || !filters) return nullptr;
+    if (!on_gpu(input) || !on_gpu(dy) || !on_gpu(filters) || (out && !on_gpu(out)))
+        return NPH_Conv2D_LayerBackward(input, out, dy, filters, stride, padding, dilation, activation, use_bias);
+    Operand cx(input);
+    if (!cx.arr) return nullptr;
+    Operand cy(dy);
+    if (!cy.arr) return nullptr;
+    Operand cf(filters);
+    if (!cf.arr) return nullptr;
+    if (!out) return NPH_Conv2D_LayerBackward(cx.arr, nullptr, cy.arr, cf.arr, stride, padding, dilation, activation, use_bias);
+    Operand co(out);
+    return co.arr ? NPH_Conv2D_LayerBackward(cx.arr, co.arr, cy.arr, cf.arr, stride, padding, dilation, activation, use_bias) : nullptr;
+}
+
 }  // extern "C"

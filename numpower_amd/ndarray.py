@@ -157,6 +157,8 @@ def _load_host():
     sig["NDArrayDNN_Conv2D_Backward"] = (C.POINTER(_P), [_P, _P, _P, C.c_int, C.c_char, C.c_int])
     sig["NDArrayDNN_Conv2D_ForwardEx"] = (_P, [_P, _P, ip, ip, ip])
     sig["NDArrayDNN_Conv2D_BackwardEx"] = (C.POINTER(_P), [_P, _P, _P, ip, ip, ip])
+    sig["NDArrayDNN_Conv2D_LayerForward"] = (_P, [_P, _P, _P, ip, ip, ip, C.c_char])
+    sig["NDArrayDNN_Conv2D_LayerBackward"] = (C.POINTER(_P), [_P, _P, _P, _P, ip, ip, ip, C.c_char, C.c_int])
     sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
     sig["NDArray_Eig"] = (C.POINTER(_P), [_P])
     sig["NDArray_Qr"] = (C.POINTER(_P), [_P])
@@ -882,38 +884,63 @@ class NDArray:
             return None
         return tuple((C.c_int * 2)(*v) for v in (s, p, d))
 
+    _DNN_ACTIVATIONS = {None: b"n", "relu": b"r", "tanh": b"t", "sigmoid": b"s"}
+
     @staticmethod
-    def dnn_conv2d_forward(x, filters, stride=1, padding=0, dilation=1):   # numpower.c:4293: NDArrayDNN_Conv2D_Forward(x, filters, NULL, 'r', 1)
+    def _dnn_activation(activation):
+        if not (activation is None or isinstance(activation, str)) or activation not in NDArray._DNN_ACTIVATIONS:
+            raise Error("dnn_conv2d: activation must be None, 'relu', 'tanh' or 'sigmoid', not %r" % (activation,))
+        return NDArray._DNN_ACTIVATIONS[activation]
+
+    @staticmethod
+    def dnn_conv2d_forward(x, filters, stride=1, padding=0, dilation=1, bias=None, activation=None):   # numpower.c:4293: NDArrayDNN_Conv2D_Forward(x, filters, NULL, 'r', 1)
         """y (N, F, oh, ow) of x (N, C, H, W) and filters (F, C, kh, kw): cross-correlation, no bias, no activation (DESIGN.md
         §3.14).  stride, padding and dilation take an int or a (rows, columns) pair; padding also 'valid' (0) and 'same'
         ((keh - 1) / 2 of the effective window keh = dilation . (kh - 1) + 1, for stride 1 and odd keh, kew).
-        oh = floor((H + 2 ph - keh) / sh) + 1.  With the defaults: the reference's call, y (N, F, H - kh + 1, W - kw + 1)."""
+        oh = floor((H + 2 ph - keh) / sh) + 1.  With the defaults: the reference's call, y (N, F, H - kh + 1, W - kw + 1).
+        bias: a 1-D array (F,) added to every output of its filter, ONE fp32 add after the reduction; activation: None, 'relu',
+        'tanh' or 'sigmoid', applied in the same kernel: y = act(conv + bias).  With both at None: the code path above."""
         h = _load_host()
         geometry = NDArray._dnn_geometry(filters, stride, padding, dilation)
+        act = NDArray._dnn_activation(activation)
         a, _ = NDArray._coerce(x)
         w, _ = NDArray._coerce(filters)
+        if bias is not None or activation is not None:
+            b = None if bias is None else NDArray._coerce(bias)[0]
+            return NDArray._wrap(h.NDArrayDNN_Conv2D_LayerForward(a._p, w._p, None if b is None else b._p, *(geometry or (None, None, None)), act))
         if geometry is None:
             return NDArray._wrap(h.NDArrayDNN_Conv2D_Forward(a._p, w._p, None, b"r", 1))
         return NDArray._wrap(h.NDArrayDNN_Conv2D_ForwardEx(a._p, w._p, *geometry))
 
     @staticmethod
-    def dnn_conv2d_backward(x, y, filters, stride=1, padding=0, dilation=1):   # numpower.c:4348: NDArrayDNN_Conv2D_Backward(x, y, filters, 3, 'r', 1) -> RETURN_2NDARRAY
+    def dnn_conv2d_backward(x, y, filters, stride=1, padding=0, dilation=1, out=None, activation=None, bias=False):   # numpower.c:4348: NDArrayDNN_Conv2D_Backward(x, y, filters, 3, 'r', 1) -> RETURN_2NDARRAY
         """(dW (F, C, kh, kw), dX (N, C, H, W)) for y = the gradient of dnn_conv2d_forward(x, filters, stride, padding, dilation),
-        the reference's order.  Rows and columns of x that no window reads get dX = 0."""
+        the reference's order.  Rows and columns of x that no window reads get dX = 0.
+        For a layer with an activation pass it and `out`, the forward RESULT: the gradient goes through act'(out) first (relu: a
+        select on out <= 0; tanh: 1 - out^2; sigmoid: (1 - out) out).  bias=True: (dW, dX, db) with db (F,) the gradient of the
+        bias.  With the three at their defaults: the code path above and its 2-tuple."""
         h = _load_host()
         geometry = NDArray._dnn_geometry(filters, stride, padding, dilation)
+        act = NDArray._dnn_activation(activation)
+        if activation is not None and out is None:
+            raise Error("dnn_conv2d_backward: an activation needs out, the forward result (gradients are expressed through the output)")
         a, _ = NDArray._coerce(x)
         g, _ = NDArray._coerce(y)
         w, _ = NDArray._coerce(filters)
-        if geometry is None:
+        count = 2
+        if activation is not None or bias or out is not None:
+            o = None if out is None else NDArray._coerce(out)[0]
+            rtns = h.NDArrayDNN_Conv2D_LayerBackward(a._p, None if o is None else o._p, g._p, w._p, *(geometry or (None, None, None)), act, 1 if bias else 0)
+            count = 3 if bias else 2
+        elif geometry is None:
             rtns = h.NDArrayDNN_Conv2D_Backward(a._p, g._p, w._p, 3, b"r", 1)
         else:
             rtns = h.NDArrayDNN_Conv2D_BackwardEx(a._p, g._p, w._p, *geometry)
         if not rtns:
             _raise_pending(h)
-        out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(2))
+        out_arrays = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(count))
         _libc_free(C.cast(rtns, C.c_void_p))
-        return out
+        return out_arrays
 
     def copy(self):          # PHP_METHOD copy: NDArray_Copy on the array's own device
         return NDArray._wrap(_load_host().NDArray_Copy(self._p, C.cast(self._p, _P).contents.device))

@@ -15,7 +15,17 @@ Every layer runs in a child process of its own under its own time limit (--limit
 layer that fails or runs out of time.  --torch adds, as information, torch.nn.functional.conv2d and its autograd on the device
 where this installation runs them (one more child); if it does not, the log says so in one line.
 
+--act is the leg of the layer's bias and activation (np_conv2d_forward_act, np_conv2d_backward_act): per layer, in one child,
+the plain forward pass, the fused one (a bias and relu) with the ratio fused / plain, and the plain pass plus ONE elementwise
+pass over y (np_binary add of two arrays of numel(y): the cheapest unfused alternative if N-D broadcasting existed); then
+np_conv2d_backward_act (relu, dz and db) against an elementwise multiply on arrays of the same element count (both move
+12 B / element: two reads and a write), with the ratio and the fraction of 8 TB/s; and the same pair at one large case of about
+10^8 elements.  Writes profiles/dnn/conv2d_act_sweep.log.
+--forward-only times the forward pass alone, one line per layer: for alternating two builds of the library in one session.
+
 Usage: python tools/dnn_sweep.py [--layers 0,1,...] [--rounds N] [--limit S] [--torch] [--out FILE]
+       python tools/dnn_sweep.py --act [--layers ...]         the bias / activation leg
+       python tools/dnn_sweep.py --forward-only [--layers ...]
        python tools/dnn_sweep.py --profile LAYER     three calls of each operation and nothing else, for a run under the kernel profiler"""
 import argparse
 import statistics
@@ -43,10 +53,16 @@ ap.add_argument("--layers", default=",".join(str(i) for i in range(len(LAYERS)))
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--limit", type=int, default=120, help="seconds each child process may take")
 ap.add_argument("--torch", action="store_true")
-ap.add_argument("--out", default=str(ROOT / "profiles" / "dnn" / "conv2d_sweep.log"))
+ap.add_argument("--act", action="store_true")
+ap.add_argument("--forward-only", action="store_true")
+ap.add_argument("--out", default=None)
 ap.add_argument("--profile", type=int, default=None)
 ap.add_argument("--child", default=None, help="internal: 'layer:<i>' or 'torch'")
 args = ap.parse_args()
+if args.out is None:
+    args.out = str(ROOT / "profiles" / "dnn" / ("conv2d_act_sweep.log" if args.act else "conv2d_forward_only.log" if args.forward_only else "conv2d_sweep.log"))
+LARGE = (256, 128, 3136)                        # (N, F, P) of the large case of --act: 1.03e8 elements
+HBM_TBS = 8.0
 
 
 def shapes(i):
@@ -130,6 +146,111 @@ def run_layer(i, rounds, profile=False):
             d.free()
 
 
+def _setup():
+    from numpower_amd import device as D
+    from numpower_amd._lib import Timer, check, load
+    D.init(0)
+    lib = load()
+    t = Timer()
+
+    def ramp():                                 # clock ramp: ~1 s of 4096^3 GEMMs
+        import numpy as np
+        ga = D.DeviceArray.from_host(np.random.default_rng(0).standard_normal((4096, 4096)).astype(np.float32))
+        gc = D.DeviceArray((4096, 4096))
+        t0 = time.time()
+        while time.time() - t0 < 1.0:
+            for _ in range(10):
+                check(lib.np_sgemm(4096, 4096, 4096, ga.ptr, ga.ptr, gc.ptr))
+            D.sync()
+        ga.free()
+        gc.free()
+
+    def median_ms(fn, rounds):
+        fn()
+        D.sync()
+        t0 = time.time()
+        fn()
+        D.sync()
+        reps = max(3, min(200, int(0.1 / max(time.time() - t0, 1e-5))))
+        ms = []
+        for _ in range(rounds):
+            t.start()
+            for _ in range(reps):
+                fn()
+            t.stop()
+            ms.append(t.elapsed_ms() / reps)
+        return statistics.median(ms)
+
+    return D, lib, check, ramp, median_ms
+
+
+def _forward_call(lib, check, i, x, w, y, bias=None, act=0, fused=False):
+    xs, ws, ys, (ph, pw), _ = shapes(i)
+    dims = (xs[0], xs[1], xs[2], xs[3], ws[0], ws[2], ws[3], ph, pw)
+    if fused:
+        return lambda: check(lib.np_conv2d_forward_act(x.ptr, w.ptr, bias.ptr if bias is not None else None, *dims, *geometry(i), act, y.ptr))
+    if len(LAYERS[i]) > 4:
+        return lambda: check(lib.np_conv2d_forward_ex(x.ptr, w.ptr, *dims, *geometry(i), y.ptr))
+    return lambda: check(lib.np_conv2d_forward(x.ptr, w.ptr, *dims, y.ptr))
+
+
+def run_forward_only(i, rounds):
+    import numpy as np
+    D, lib, check, ramp, median_ms = _setup()
+    xs, ws, ys, _, _ = shapes(i)
+    rng = np.random.default_rng(i)
+    dev = lambda s: D.DeviceArray.from_host(rng.standard_normal(s).astype(np.float32))
+    x, w, y = dev(xs), dev(ws), D.DeviceArray(ys)
+    ramp()
+    print("%-42s forward %9.4f" % (LAYERS[i][0], median_ms(_forward_call(lib, check, i, x, w, y), rounds)), flush=True)
+
+
+def _backward_pair(D, lib, check, median_ms, rounds, name, N, F, P):
+    """np_conv2d_backward_act (relu, dz and db) against np_binary multiply on the same element count"""
+    import ctypes as C_
+    import numpy as np
+    rng = np.random.default_rng(F)
+    dev = lambda s: D.DeviceArray.from_host(rng.standard_normal(s).astype(np.float32))
+    n = N * F * P
+    y, dy, dz, db = dev((n,)), dev((n,)), D.DeviceArray((n,)), D.DeviceArray((F,))
+    act_ms = median_ms(lambda: check(lib.np_conv2d_backward_act(y.ptr, dy.ptr, N, F, P, 1, dz.ptr, db.ptr)), rounds)
+    s = [C_.c_int() for _ in range(3)]
+    check(lib.np_debug_dnn_last_epilogue(*(C_.byref(c) for c in s)))
+    mul_ms = median_ms(lambda: check(lib.np_binary(2, y.ptr, 0, dy.ptr, 0, dz.ptr, 1, n, 0, 0)), rounds)
+    tbs = lambda ms: 12.0 * n / ms * 1e-9
+    print("%-42s backward_act (N %d, F %d, P %d, S %d) %9.4f ms %5.2f TB/s (%4.1f %% of %g)   multiply %9.4f ms %5.2f TB/s   act / multiply %6.3f"
+          % (name, N, F, P, s[2].value, act_ms, tbs(act_ms), 100 * tbs(act_ms) / HBM_TBS, HBM_TBS, mul_ms, tbs(mul_ms), act_ms / mul_ms), flush=True)
+    for d in (y, dy, dz, db):
+        d.free()
+
+
+def run_act(what, rounds):
+    import numpy as np
+    D, lib, check, ramp, median_ms = _setup()
+    ramp()
+    if what == "large":
+        _backward_pair(D, lib, check, median_ms, rounds, "large", *LARGE)
+        return
+    i = int(what)
+    xs, ws, ys, _, _ = shapes(i)
+    rng = np.random.default_rng(i)
+    dev = lambda s: D.DeviceArray.from_host(rng.standard_normal(s).astype(np.float32))
+    x, w, bias, y, other, out = dev(xs), dev(ws), dev((ws[0],)), D.DeviceArray(ys), dev(ys), D.DeviceArray(ys)
+    n = int(np.prod(ys))
+    plain = _forward_call(lib, check, i, x, w, y)
+    plain_ms = median_ms(plain, rounds)
+    fused_ms = median_ms(_forward_call(lib, check, i, x, w, y, bias, 1, fused=True), rounds)
+
+    def unfused():
+        plain()
+        check(lib.np_binary(0, y.ptr, 0, other.ptr, 0, out.ptr, 1, n, 0, 0))
+
+    unfused_ms = median_ms(unfused, rounds)
+    print("%-42s forward plain %9.4f ms   bias + relu fused %9.4f ms   fused / plain %6.3f   plain + one elementwise pass %9.4f ms   fused / that %6.3f"
+          % (LAYERS[i][0], plain_ms, fused_ms, fused_ms / plain_ms, unfused_ms, fused_ms / unfused_ms), flush=True)
+    _backward_pair(D, lib, check, median_ms, rounds, LAYERS[i][0], ys[0], ys[1], ys[2] * ys[3])
+
+
 def run_torch(layers, rounds):
     import torch
     if not torch.cuda.is_available():
@@ -170,6 +291,10 @@ if args.profile is not None:
 if args.child:
     if args.child == "torch":
         run_torch([int(s) for s in args.layers.split(",")], args.rounds)
+    elif args.child.startswith("act:"):
+        run_act(args.child.split(":")[1], args.rounds)
+    elif args.child.startswith("fwd:"):
+        run_forward_only(int(args.child.split(":")[1]), args.rounds)
     else:
         run_layer(int(args.child.split(":")[1]), args.rounds)
     sys.exit(0)
@@ -197,14 +322,23 @@ def child(what):
     return proc.returncode == 0
 
 
-say("np_conv2d_forward / _backward_data / _backward_filter, fp32, median of %d rounds; gemm = np_sgemm on dense operands of the same M, N, K" % args.rounds)
-say("%-42s %-8s %6s %9s %7s %9s %8s %9s %8s %7s %4s %4s %4s" % ("layer", "op", "M", "N", "K", "conv ms", "TFLOP/s", "gemm ms", "TFLOP/s", "gemm/conv", "TM", "S",
-                                                                  "form"))
+kind = "act" if args.act else "fwd" if args.forward_only else "layer"
+if args.act:
+    say("np_conv2d_forward_act (a bias and relu) against np_conv2d_forward(_ex), np_conv2d_backward_act (relu, dz and db) against np_binary "
+        "multiply on the same element count; fp32, ms per call, median of %d rounds" % args.rounds)
+elif args.forward_only:
+    say("the forward pass alone, fp32, ms per call, median of %d rounds" % args.rounds)
+else:
+    say("np_conv2d_forward / _backward_data / _backward_filter, fp32, median of %d rounds; gemm = np_sgemm on dense operands of the same M, N, K" % args.rounds)
+    say("%-42s %-8s %6s %9s %7s %9s %8s %9s %8s %7s %4s %4s %4s" % ("layer", "op", "M", "N", "K", "conv ms", "TFLOP/s", "gemm ms", "TFLOP/s", "gemm/conv", "TM",
+                                                                      "S", "form"))
 ok = True
 for i in (int(s) for s in args.layers.split(",")):
-    ok = child("layer:%d" % i)
+    ok = child("%s:%d" % (kind, i))
     if not ok:
         break                                   # nothing more is started on a device after a failure
+if ok and args.act:
+    ok = child("act:large")
 if ok and args.torch:
     if not child("torch"):
         say("torch.nn.functional.conv2d did not run on the device in this installation")
