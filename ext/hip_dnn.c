@@ -89,62 +89,6 @@ static int layer_of(NDArray *x, NDArray *y, NDArray *filters, const nph_geometry
     return 1;
 }
 
-/* a new 4-d GPU array, allocated as the reference allocates its results (NDArray_Empty over an emalloc'd shape, dnn.c:284) */
-static NDArray *empty4_on_gpu(size_t d0, size_t d1, size_t d2, size_t d3) {
-    int *shape = (int *) NPH_ALLOC(sizeof(int) * 4);
-    if (shape == NULL) return NULL;
-    shape[0] = (int) d0, shape[1] = (int) d1, shape[2] = (int) d2, shape[3] = (int) d3;
-    NDArray *rtn = NDArray_Empty(shape, 4, "float32", NDARRAY_DEVICE_GPU);
-    if (NPH_SHAPE_IS_COPIED) NPH_RELEASE(shape);
-    return rtn;
-}
-
-NDArray *NPH_Conv2D_Forward(NDArray *x, NDArray *filters) {
-    nph_layer l;
-    if (x == NULL || filters == NULL || !layer_of(x, NULL, filters, NULL, &l)) return NULL;
-    size_t oh = 0, ow = 0;
-    if (np_conv2d_shape(l.H, l.W, l.kh, l.kw, 0, 0, &oh, &ow) != NP_OK || l.N < 1 || l.C < 1 || l.F < 1) {
-        if (l.N < 1 || l.C < 1 || l.F < 1) np_ext_throw("dnn_conv2d: an operand has no elements");
-        else np_ext_throw_last();
-        return NULL;
-    }
-    NDArray *rtn = empty4_on_gpu(l.N, l.F, oh, ow);
-    if (rtn == NULL) return NULL;
-    if (np_conv2d_forward(NDArray_FDATA(x), NDArray_FDATA(filters), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, 0, 0, NDArray_FDATA(rtn)) != NP_OK) {
-        np_ext_throw_last();
-        NDArray_FREE(rtn);
-        return NULL;
-    }
-    return rtn;
-}
-
-NDArray **NPH_Conv2D_Backward(NDArray *x, NDArray *y, NDArray *filters) {
-    nph_layer l;
-    if (x == NULL || y == NULL || filters == NULL || !layer_of(x, y, filters, NULL, &l)) return NULL;
-    if (NDArray_NUMELEMENTS(x) < 1 || NDArray_NUMELEMENTS(filters) < 1) {
-        np_ext_throw("dnn_conv2d: an operand has no elements");
-        return NULL;
-    }
-    /* the reference's order (dnn.c:365-366): rtn[0] = dW in the filters' shape, rtn[1] = dX in the input's */
-    NDArray *dw = empty4_on_gpu(l.F, l.C, l.kh, l.kw), *dx = empty4_on_gpu(l.N, l.C, l.H, l.W);
-    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 2);
-    int ok = dw != NULL && dx != NULL && rtns != NULL;
-    if (ok && (np_conv2d_backward_filter(NDArray_FDATA(x), NDArray_FDATA(y), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, 0, 0, NDArray_FDATA(dw)) != NP_OK ||
-               np_conv2d_backward_data(NDArray_FDATA(y), NDArray_FDATA(filters), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, 0, 0, NDArray_FDATA(dx)) != NP_OK)) {
-        np_ext_throw_last();
-        ok = 0;
-    }
-    if (!ok) {
-        if (dw != NULL) NDArray_FREE(dw);
-        if (dx != NULL) NDArray_FREE(dx);
-        if (rtns != NULL) NPH_RELEASE(rtns);
-        return NULL;
-    }
-    rtns[0] = dw;
-    rtns[1] = dx;
-    return rtns;
-}
-
 /* NULL: the default */
 static nph_geometry geometry_of(const int stride[2], const int padding[2], const int dilation[2]) {
     nph_geometry g = {1, 1, 0, 0, 1, 1};
@@ -153,61 +97,6 @@ static nph_geometry geometry_of(const int stride[2], const int padding[2], const
     if (dilation != NULL) g.dh = dilation[0], g.dw = dilation[1];
     return g;
 }
-
-NDArray *NPH_Conv2D_ForwardEx(NDArray *x, NDArray *filters, const int stride[2], const int padding[2], const int dilation[2]) {
-    nph_layer l;
-    const nph_geometry g = geometry_of(stride, padding, dilation);
-    if (x == NULL || filters == NULL || !layer_of(x, NULL, filters, &g, &l)) return NULL;
-    size_t oh = 0, ow = 0;
-    if (l.N < 1 || l.C < 1 || l.F < 1) {
-        np_ext_throw("dnn_conv2d: an operand has no elements");
-        return NULL;
-    }
-    if (np_conv2d_shape_ex(l.H, l.W, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw, (size_t) g.sh, (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, &oh, &ow) != NP_OK) {
-        np_ext_throw_last();
-        return NULL;
-    }
-    NDArray *rtn = empty4_on_gpu(l.N, l.F, oh, ow);
-    if (rtn == NULL) return NULL;
-    if (np_conv2d_forward_ex(NDArray_FDATA(x), NDArray_FDATA(filters), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw, (size_t) g.sh,
-                             (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, NDArray_FDATA(rtn)) != NP_OK) {
-        np_ext_throw_last();
-        NDArray_FREE(rtn);
-        return NULL;
-    }
-    return rtn;
-}
-
-NDArray **NPH_Conv2D_BackwardEx(NDArray *x, NDArray *y, NDArray *filters, const int stride[2], const int padding[2], const int dilation[2]) {
-    nph_layer l;
-    const nph_geometry g = geometry_of(stride, padding, dilation);
-    if (x == NULL || y == NULL || filters == NULL || !layer_of(x, y, filters, &g, &l)) return NULL;
-    if (NDArray_NUMELEMENTS(x) < 1 || NDArray_NUMELEMENTS(filters) < 1) {
-        np_ext_throw("dnn_conv2d: an operand has no elements");
-        return NULL;
-    }
-    NDArray *dw = empty4_on_gpu(l.F, l.C, l.kh, l.kw), *dx = empty4_on_gpu(l.N, l.C, l.H, l.W);
-    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 2);
-    int ok = dw != NULL && dx != NULL && rtns != NULL;
-    if (ok && (np_conv2d_backward_filter_ex(NDArray_FDATA(x), NDArray_FDATA(y), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw,
-                                            (size_t) g.sh, (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, NDArray_FDATA(dw)) != NP_OK ||
-               np_conv2d_backward_data_ex(NDArray_FDATA(y), NDArray_FDATA(filters), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw,
-                                          (size_t) g.sh, (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, NDArray_FDATA(dx)) != NP_OK)) {
-        np_ext_throw_last();
-        ok = 0;
-    }
-    if (!ok) {
-        if (dw != NULL) NDArray_FREE(dw);
-        if (dx != NULL) NDArray_FREE(dx);
-        if (rtns != NULL) NPH_RELEASE(rtns);
-        return NULL;
-    }
-    rtns[0] = dw;
-    rtns[1] = dx;
-    return rtns;
-}
-
-/* ---- the layer: a bias and an activation (hip_dnn.h) ---- */
 
 /* 'r', 't', 's', 'n' or 0 -> np_conv_act, -1 for anything else */
 static int activation_of(char activation) {
@@ -220,7 +109,8 @@ static int activation_of(char activation) {
     }
 }
 
-/* the layer's own checks, which come before layer_of()'s; bias may be NULL, and so may out and dy (forward).  0 after a raised error */
+/* the layer's own checks, which come before layer_of()'s; bias may be NULL, and so may out and dy (forward).  A call without a
+ * bias, an out and an activation passes them all.  0 after a raised error */
 static int layer_extras(NDArray *x, NDArray *filters, NDArray *bias, NDArray *out, NDArray *dy, int act) {
     if (act < 0) {
         np_ext_throw(NPH_DNN_MSG_ACTIVATION);
@@ -249,35 +139,42 @@ static int layer_extras(NDArray *x, NDArray *filters, NDArray *bias, NDArray *ou
     return 1;
 }
 
-/* a new 1-d GPU array of n floats */
-static NDArray *empty1_on_gpu(size_t n) {
-    int *shape = (int *) NPH_ALLOC(sizeof(int));
+/* a new GPU array, allocated as the reference allocates its results (NDArray_Empty over an emalloc'd shape, dnn.c:284) */
+static NDArray *empty_on_gpu(int ndim, const size_t *dims) {
+    int *shape = (int *) NPH_ALLOC(sizeof(int) * (size_t) ndim);
     if (shape == NULL) return NULL;
-    shape[0] = (int) n;
-    NDArray *rtn = NDArray_Empty(shape, 1, "float32", NDARRAY_DEVICE_GPU);
+    for (int d = 0; d < ndim; ++d) shape[d] = (int) dims[d];
+    NDArray *rtn = NDArray_Empty(shape, ndim, "float32", NDARRAY_DEVICE_GPU);
     if (NPH_SHAPE_IS_COPIED) NPH_RELEASE(shape);
     return rtn;
 }
 
-NDArray *NPH_Conv2D_LayerForward(NDArray *x, NDArray *filters, NDArray *bias, const int stride[2], const int padding[2], const int dilation[2],
-                                 char activation) {
+/* a layer as the np_conv2d_*_ex calls take it */
+#define NPH_LAYER_ARGS(l, g) \
+    (l).N, (l).C, (l).H, (l).W, (l).F, (l).kh, (l).kw, (size_t) (g)->ph, (size_t) (g)->pw, (size_t) (g)->sh, (size_t) (g)->sw, (size_t) (g)->dh, (size_t) (g)->dw
+
+static const nph_geometry nph_unit_geometry = {1, 1, 0, 0, 1, 1};
+
+/* The forward pass of all three public functions.  g == NULL: the reference-signature call (layer_of).  Without a bias and an
+ * activation np_conv2d_forward_act launches the plain kernels. */
+static NDArray *forward(NDArray *x, NDArray *filters, NDArray *bias, const nph_geometry *g, int act) {
     nph_layer l;
-    const nph_geometry g = geometry_of(stride, padding, dilation);
-    const int act = activation_of(activation);
-    if (x == NULL || filters == NULL || !layer_extras(x, filters, bias, NULL, NULL, act) || !layer_of(x, NULL, filters, &g, &l)) return NULL;
-    size_t oh = 0, ow = 0;
+    if (x == NULL || filters == NULL || !layer_extras(x, filters, bias, NULL, NULL, act) || !layer_of(x, NULL, filters, g, &l)) return NULL;
     if (l.N < 1 || l.C < 1 || l.F < 1) {
         np_ext_throw("dnn_conv2d: an operand has no elements");
         return NULL;
     }
-    if (np_conv2d_shape_ex(l.H, l.W, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw, (size_t) g.sh, (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, &oh, &ow) != NP_OK) {
+    if (g == NULL) g = &nph_unit_geometry;
+    size_t oh = 0, ow = 0;
+    if (np_conv2d_shape_ex(l.H, l.W, l.kh, l.kw, (size_t) g->ph, (size_t) g->pw, (size_t) g->sh, (size_t) g->sw, (size_t) g->dh, (size_t) g->dw, &oh, &ow) != NP_OK) {
         np_ext_throw_last();
         return NULL;
     }
-    NDArray *rtn = empty4_on_gpu(l.N, l.F, oh, ow);
+    const size_t dims[4] = {l.N, l.F, oh, ow};
+    NDArray *rtn = empty_on_gpu(4, dims);
     if (rtn == NULL) return NULL;
-    if (np_conv2d_forward_act(NDArray_FDATA(x), NDArray_FDATA(filters), bias != NULL ? NDArray_FDATA(bias) : NULL, l.N, l.C, l.H, l.W, l.F, l.kh, l.kw,
-                              (size_t) g.ph, (size_t) g.pw, (size_t) g.sh, (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, act, NDArray_FDATA(rtn)) != NP_OK) {
+    if (np_conv2d_forward_act(NDArray_FDATA(x), NDArray_FDATA(filters), bias != NULL ? NDArray_FDATA(bias) : NULL, NPH_LAYER_ARGS(l, g), act,
+                              NDArray_FDATA(rtn)) != NP_OK) {
         np_ext_throw_last();
         NDArray_FREE(rtn);
         return NULL;
@@ -285,20 +182,22 @@ NDArray *NPH_Conv2D_LayerForward(NDArray *x, NDArray *filters, NDArray *bias, co
     return rtn;
 }
 
-NDArray **NPH_Conv2D_LayerBackward(NDArray *x, NDArray *out, NDArray *dy, NDArray *filters, const int stride[2], const int padding[2],
-                                   const int dilation[2], char activation, int use_bias) {
+/* The backward pass of all three public functions: a vector of n_rtn, rtn[0] = dW in the filters' shape and rtn[1] = dX in the
+ * input's, the reference's order (dnn.c:365-366), rtn[2] = db or NULL.  dy goes through np_conv2d_backward_act first where there
+ * is an activation or a bias; dW and dX are the _ex gradients of the result. */
+static NDArray **backward(NDArray *x, NDArray *out, NDArray *dy, NDArray *filters, const nph_geometry *g, int act, int use_bias, int n_rtn) {
     nph_layer l;
-    const nph_geometry g = geometry_of(stride, padding, dilation);
-    const int act = activation_of(activation);
     if (x == NULL || dy == NULL || filters == NULL) return NULL;
-    if (!layer_extras(x, filters, NULL, out, dy, act) || !layer_of(x, dy, filters, &g, &l)) return NULL;
+    if (!layer_extras(x, filters, NULL, out, dy, act) || !layer_of(x, dy, filters, g, &l)) return NULL;
     if (NDArray_NUMELEMENTS(x) < 1 || NDArray_NUMELEMENTS(filters) < 1) {
         np_ext_throw("dnn_conv2d: an operand has no elements");
         return NULL;
     }
+    if (g == NULL) g = &nph_unit_geometry;
     const size_t P = (size_t) NDArray_SHAPE(dy)[2] * (size_t) NDArray_SHAPE(dy)[3];
-    NDArray *dw = empty4_on_gpu(l.F, l.C, l.kh, l.kw), *dx = empty4_on_gpu(l.N, l.C, l.H, l.W), *db = use_bias ? empty1_on_gpu(l.F) : NULL;
-    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 3);
+    const size_t dw_dims[4] = {l.F, l.C, l.kh, l.kw}, dx_dims[4] = {l.N, l.C, l.H, l.W};
+    NDArray *dw = empty_on_gpu(4, dw_dims), *dx = empty_on_gpu(4, dx_dims), *db = use_bias ? empty_on_gpu(1, &l.F) : NULL;
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * (size_t) n_rtn);
     void *dz = NULL;   /* pool scratch, only with an activation: dz = dy otherwise */
     int ok = dw != NULL && dx != NULL && rtns != NULL && (db != NULL || !use_bias);
     if (ok && act != NP_ACT_NONE && np_malloc(&dz, l.N * l.F * P * sizeof(float)) != NP_OK) {
@@ -313,10 +212,8 @@ NDArray **NPH_Conv2D_LayerBackward(NDArray *x, NDArray *out, NDArray *dy, NDArra
         np_ext_throw_last();
         ok = 0;
     }
-    if (ok && (np_conv2d_backward_filter_ex(NDArray_FDATA(x), grad, l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw, (size_t) g.sh,
-                                            (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, NDArray_FDATA(dw)) != NP_OK ||
-               np_conv2d_backward_data_ex(grad, NDArray_FDATA(filters), l.N, l.C, l.H, l.W, l.F, l.kh, l.kw, (size_t) g.ph, (size_t) g.pw, (size_t) g.sh,
-                                          (size_t) g.sw, (size_t) g.dh, (size_t) g.dw, NDArray_FDATA(dx)) != NP_OK)) {
+    if (ok && (np_conv2d_backward_filter_ex(NDArray_FDATA(x), grad, NPH_LAYER_ARGS(l, g), NDArray_FDATA(dw)) != NP_OK ||
+               np_conv2d_backward_data_ex(grad, NDArray_FDATA(filters), NPH_LAYER_ARGS(l, g), NDArray_FDATA(dx)) != NP_OK)) {
         np_ext_throw_last();
         ok = 0;
     }
@@ -330,6 +227,35 @@ NDArray **NPH_Conv2D_LayerBackward(NDArray *x, NDArray *out, NDArray *dy, NDArra
     }
     rtns[0] = dw;
     rtns[1] = dx;
-    rtns[2] = db;
+    if (n_rtn > 2) rtns[2] = db;
     return rtns;
 }
+
+/* ---- the public functions (hip_dnn.h): each fills in its defaults ---- */
+
+NDArray *NPH_Conv2D_Forward(NDArray *x, NDArray *filters) { return forward(x, filters, NULL, NULL, NP_ACT_NONE); }
+
+NDArray **NPH_Conv2D_Backward(NDArray *x, NDArray *y, NDArray *filters) { return backward(x, NULL, y, filters, NULL, NP_ACT_NONE, 0, 2); }
+
+NDArray *NPH_Conv2D_ForwardEx(NDArray *x, NDArray *filters, const int stride[2], const int padding[2], const int dilation[2]) {
+    const nph_geometry g = geometry_of(stride, padding, dilation);
+    return forward(x, filters, NULL, &g, NP_ACT_NONE);
+}
+
+NDArray **NPH_Conv2D_BackwardEx(NDArray *x, NDArray *y, NDArray *filters, const int stride[2], const int padding[2], const int dilation[2]) {
+    const nph_geometry g = geometry_of(stride, padding, dilation);
+    return backward(x, NULL, y, filters, &g, NP_ACT_NONE, 0, 2);
+}
+
+NDArray *NPH_Conv2D_LayerForward(NDArray *x, NDArray *filters, NDArray *bias, const int stride[2], const int padding[2], const int dilation[2],
+                                 char activation) {
+    const nph_geometry g = geometry_of(stride, padding, dilation);
+    return forward(x, filters, bias, &g, activation_of(activation));
+}
+
+NDArray **NPH_Conv2D_LayerBackward(NDArray *x, NDArray *out, NDArray *dy, NDArray *filters, const int stride[2], const int padding[2],
+                                   const int dilation[2], char activation, int use_bias) {
+    const nph_geometry g = geometry_of(stride, padding, dilation);
+    return backward(x, out, dy, filters, &g, activation_of(activation), use_bias, 3);
+}
+

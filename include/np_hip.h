@@ -589,7 +589,10 @@ int np_correlate2d(const float *a, size_t ah, size_t aw, const float *b, size_t 
  * Convention: pointers are checked first, then the shape, then work begins.  NP_ERR_INVALID before any device work: a null
  * pointer; an extent of zero; ph >= kh or pw >= kw; kh > H + 2 ph or kw > W + 2 pw; any of numel(x), numel(w), numel(y),
  * N.oh.ow, C.kh.kw or F.kh.kw at 2^31 or more (refused, never truncated).  Library stream; scratch comes from the caching pool
- * and is released on every path. */
+ * and is released on every path.
+ * These four are the _ex calls below at (sh, sw, dh, dw) = (1, 1, 1, 1) and go through the same checks, so they also refuse a
+ * padded extent H + 2 ph or W + 2 pw of 2^31 or more (the kernels form the row index i + p - ph as an int), and a refusal is
+ * worded as the _ex calls word it: "every extent, stride and dilation must be at least 1", "the effective window". */
 int np_conv2d_shape(size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw, size_t *oh, size_t *ow);
 int np_conv2d_forward(const float *x, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
                       size_t ph, size_t pw, float *y);

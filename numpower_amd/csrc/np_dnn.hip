@@ -470,74 +470,49 @@ __global__ __launch_bounds__(256) void dnn_bias_fold_kernel(const float *__restr
     db[f] = acc;
 }
 
-template <int FORM>
-void launch_fprop_form(int tm, dim3 grid, dim3 block, const ConvArgs &a) {
-    if (tm == kTMSmall) dnn_fprop_kernel<kTMSmall, FORM><<<grid, block, 0, np::stream()>>>(a);
-    else if (tm == kTMMid) dnn_fprop_kernel<kTMMid, FORM><<<grid, block, 0, np::stream()>>>(a);
-    else dnn_fprop_kernel<kTMLarge, FORM><<<grid, block, 0, np::stream()>>>(a);
-}
-
 int pick_tm(size_t F) { return F <= (size_t)kTMSmall ? kTMSmall : F <= (size_t)kTMMid ? kTMMid : kTMLarge; }
 
 constexpr size_t kLim = (size_t)1 << 31;
 // a * b, saturating at kLim (both factors at most kLim)
 size_t mul_lim(size_t a, size_t b) { return (a >= kLim || b >= kLim || a * b >= kLim) ? kLim : a * b; }
 
-int check_spatial(const char *who, size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw) {
-    if (H < 1 || W < 1 || kh < 1 || kw < 1) return np::fail(NP_ERR_INVALID, "%s: every extent must be at least 1", who);
-    if (H >= kLim || W >= kLim || kh >= kLim || kw >= kLim) return np::fail(NP_ERR_INVALID, "%s: an extent is 2^31 or more", who);
-    if (ph >= kh || pw >= kw) return np::fail(NP_ERR_INVALID, "%s: the padding (%zu, %zu) must be smaller than the window (%zu, %zu)", who, ph, pw, kh, kw);
-    if (kh > H + 2 * ph || kw > W + 2 * pw)
-        return np::fail(NP_ERR_INVALID, "%s: the window (%zu, %zu) is larger than the padded image (%zu, %zu)", who, kh, kw, H + 2 * ph, W + 2 * pw);
+// a layer as the C ABI names it; the plain entry points have stride and dilation 1, np_conv2d_shape* N = C = F = 1
+struct LayerShape {
+    size_t N, C, H, W, F, kh, kw, ph, pw, sh, sw, dh, dw;
+};
+
+// the spatial half of the shape -> the output extents, written only when the shape is accepted
+int check_spatial(const char *who, const LayerShape &s, size_t &oh, size_t &ow) {
+    if (s.H < 1 || s.W < 1 || s.kh < 1 || s.kw < 1 || s.sh < 1 || s.sw < 1 || s.dh < 1 || s.dw < 1)
+        return np::fail(NP_ERR_INVALID, "%s: every extent, stride and dilation must be at least 1", who);
+    const size_t keh = mul_lim(s.dh, s.kh - 1) + 1, kew = mul_lim(s.dw, s.kw - 1) + 1;   // the effective window
+    if (s.H >= kLim || s.W >= kLim || s.kh >= kLim || s.kw >= kLim || s.sh >= kLim || s.sw >= kLim || keh >= kLim || kew >= kLim)
+        return np::fail(NP_ERR_INVALID, "%s: an extent, a stride or an effective window is 2^31 or more", who);
+    if (s.ph >= keh || s.pw >= kew)
+        return np::fail(NP_ERR_INVALID, "%s: the padding (%zu, %zu) must be smaller than the effective window (%zu, %zu)", who, s.ph, s.pw, keh, kew);
+    if (keh > s.H + 2 * s.ph || kew > s.W + 2 * s.pw)
+        return np::fail(NP_ERR_INVALID, "%s: the effective window (%zu, %zu) is larger than the padded image (%zu, %zu)", who, keh, kew,
+                        s.H + 2 * s.ph, s.W + 2 * s.pw);
+    // the kernels form the row index oi.sh - ph + p.dh as an int: it must not reach 2^31
+    if (s.H + 2 * s.ph >= kLim || s.W + 2 * s.pw >= kLim) return np::fail(NP_ERR_INVALID, "%s: a padded extent is 2^31 or more", who);
+    oh = (s.H + 2 * s.ph - keh) / s.sh + 1;
+    ow = (s.W + 2 * s.pw - kew) / s.sw + 1;
     return NP_OK;
 }
 
 // the whole shape of a layer; fills the kernel's extents (out and the operand pointers are the caller's)
-int check_layer(const char *who, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw, size_t ph, size_t pw, ConvArgs &a) {
-    if (N < 1 || C < 1 || F < 1) return np::fail(NP_ERR_INVALID, "%s: every extent must be at least 1", who);
-    if (int rc = check_spatial(who, H, W, kh, kw, ph, pw)) return rc;
-    const size_t oh = H + 2 * ph - kh + 1, ow = W + 2 * pw - kw + 1;
-    const size_t P = mul_lim(oh, ow), numel_x = mul_lim(mul_lim(N, C), mul_lim(H, W)), numel_w = mul_lim(mul_lim(F, C), mul_lim(kh, kw));
-    const size_t numel_y = mul_lim(mul_lim(N, F), P), NP = mul_lim(N, P), K = mul_lim(C, mul_lim(kh, kw)), Kt = mul_lim(F, mul_lim(kh, kw));
+int check_layer(const char *who, const LayerShape &s, ConvArgs &a) {
+    if (s.N < 1 || s.C < 1 || s.F < 1) return np::fail(NP_ERR_INVALID, "%s: every extent, stride and dilation must be at least 1", who);
+    size_t oh, ow;
+    if (int rc = check_spatial(who, s, oh, ow)) return rc;
+    const size_t khw = mul_lim(s.kh, s.kw), P = mul_lim(oh, ow), numel_x = mul_lim(mul_lim(s.N, s.C), mul_lim(s.H, s.W));
+    const size_t numel_w = mul_lim(mul_lim(s.F, s.C), khw), numel_y = mul_lim(mul_lim(s.N, s.F), P);
+    const size_t NP = mul_lim(s.N, P), K = mul_lim(s.C, khw), Kt = mul_lim(s.F, khw);
     if (numel_x >= kLim || numel_w >= kLim || numel_y >= kLim || NP >= kLim || K >= kLim || Kt >= kLim)
         return np::fail(NP_ERR_INVALID, "%s: an operand, the result, N.P or the reduction length has 2^31 elements or more", who);
-    a.N = (int)N, a.C = (int)C, a.H = (int)H, a.W = (int)W, a.F = (int)F, a.kh = (int)kh, a.kw = (int)kw, a.ph = (int)ph, a.pw = (int)pw;
-    a.oh = (int)oh, a.ow = (int)ow, a.K = (int)K, a.P = (int)P, a.NP = (int)NP;
-    a.sh = a.sw = a.dh = a.dw = a.lh = a.lw = 1;
-    return NP_OK;
-}
-
-// the _ex shape: stride (sh, sw), dilation (dh, dw); -> the effective window and the output extents
-int check_spatial_ex(const char *who, size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw,
-                     size_t &keh, size_t &kew, size_t &oh, size_t &ow) {
-    if (H < 1 || W < 1 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1)
-        return np::fail(NP_ERR_INVALID, "%s: every extent, stride and dilation must be at least 1", who);
-    keh = mul_lim(dh, kh - 1) + 1, kew = mul_lim(dw, kw - 1) + 1;
-    if (H >= kLim || W >= kLim || kh >= kLim || kw >= kLim || sh >= kLim || sw >= kLim || keh >= kLim || kew >= kLim)
-        return np::fail(NP_ERR_INVALID, "%s: an extent, a stride or an effective window is 2^31 or more", who);
-    if (ph >= keh || pw >= kew)
-        return np::fail(NP_ERR_INVALID, "%s: the padding (%zu, %zu) must be smaller than the effective window (%zu, %zu)", who, ph, pw, keh, kew);
-    if (keh > H + 2 * ph || kew > W + 2 * pw)
-        return np::fail(NP_ERR_INVALID, "%s: the effective window (%zu, %zu) is larger than the padded image (%zu, %zu)", who, keh, kew, H + 2 * ph,
-                        W + 2 * pw);
-    if (H + 2 * ph >= kLim || W + 2 * pw >= kLim) return np::fail(NP_ERR_INVALID, "%s: a padded extent is 2^31 or more", who);
-    oh = (H + 2 * ph - keh) / sh + 1;
-    ow = (W + 2 * pw - kew) / sw + 1;
-    return NP_OK;
-}
-
-int check_layer_ex(const char *who, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw, size_t ph, size_t pw, size_t sh,
-                   size_t sw, size_t dh, size_t dw, ConvArgs &a) {
-    if (N < 1 || C < 1 || F < 1) return np::fail(NP_ERR_INVALID, "%s: every extent, stride and dilation must be at least 1", who);
-    size_t keh, kew, oh, ow;
-    if (int rc = check_spatial_ex(who, H, W, kh, kw, ph, pw, sh, sw, dh, dw, keh, kew, oh, ow)) return rc;
-    const size_t P = mul_lim(oh, ow), numel_x = mul_lim(mul_lim(N, C), mul_lim(H, W)), numel_w = mul_lim(mul_lim(F, C), mul_lim(kh, kw));
-    const size_t numel_y = mul_lim(mul_lim(N, F), P), NP = mul_lim(N, P), K = mul_lim(C, mul_lim(kh, kw)), Kt = mul_lim(F, mul_lim(kh, kw));
-    if (numel_x >= kLim || numel_w >= kLim || numel_y >= kLim || NP >= kLim || K >= kLim || Kt >= kLim)
-        return np::fail(NP_ERR_INVALID, "%s: an operand, the result, N.P or the reduction length has 2^31 elements or more", who);
-    a.N = (int)N, a.C = (int)C, a.H = (int)H, a.W = (int)W, a.F = (int)F, a.kh = (int)kh, a.kw = (int)kw, a.ph = (int)ph, a.pw = (int)pw;
-    a.oh = (int)oh, a.ow = (int)ow, a.K = (int)K, a.P = (int)P, a.NP = (int)NP;
-    a.sh = (int)sh, a.sw = (int)sw, a.dh = (int)dh, a.dw = (int)dw, a.lh = a.lw = 1;
+    a.N = (int)s.N, a.C = (int)s.C, a.H = (int)s.H, a.W = (int)s.W, a.F = (int)s.F, a.kh = (int)s.kh, a.kw = (int)s.kw;
+    a.ph = (int)s.ph, a.pw = (int)s.pw, a.oh = (int)oh, a.ow = (int)ow, a.K = (int)K, a.P = (int)P, a.NP = (int)NP;
+    a.sh = (int)s.sh, a.sw = (int)s.sw, a.dh = (int)s.dh, a.dw = (int)s.dw, a.lh = a.lw = 1;
     return NP_OK;
 }
 
@@ -575,43 +550,31 @@ int plan_wgrad(const char *who, const ConvArgs &a, WgradPlan &pl) {
     return NP_OK;
 }
 
-int launch_fprop(const ConvArgs &a) {
+// the kernel's argument is KernelArgs<FORM>, what the plain instantiations always took; only an EPI one gets the epilogue's operands behind it
+template <int FORM, bool EPI>
+void launch_fprop_form(int tm, dim3 grid, dim3 block, const ConvArgs &a, const float *bias, int act) {
+    FpropArgs<FORM, EPI> p;
+    static_cast<KernelArgs<FORM> &>(p) = a;
+    if constexpr (EPI) p.bias = bias, p.act = act;
+    if (tm == kTMSmall) dnn_fprop_kernel<kTMSmall, FORM, EPI><<<grid, block, 0, np::stream()>>>(p);
+    else if (tm == kTMMid) dnn_fprop_kernel<kTMMid, FORM, EPI><<<grid, block, 0, np::stream()>>>(p);
+    else dnn_fprop_kernel<kTMLarge, FORM, EPI><<<grid, block, 0, np::stream()>>>(p);
+}
+
+// the forward kernel for y and for dX (bias == nullptr, NP_ACT_NONE).  Without a bias and an activation: the plain kernels, the
+// plain bits.  Form 2 is dX of a strided layer and has no epilogue
+int launch_fprop(const ConvArgs &a, const float *bias, int act) {
     const int tm = pick_tm((size_t)a.F);
     const size_t tiles = (((size_t)a.F + tm - 1) / tm) * (((size_t)a.NP + kTN - 1) / kTN);
     if (tiles >= kLim) return np::fail(NP_ERR_INVALID, "np_conv2d: %zu tiles are more than one launch holds", tiles);
     const dim3 grid((unsigned)tiles), block(256);
     const int form = form_of(a);
-    if (form == 0) launch_fprop_form<0>(tm, grid, block, a);
-    else if (form == 1) launch_fprop_form<1>(tm, grid, block, a);
-    else launch_fprop_form<2>(tm, grid, block, a);
-    NP_LAUNCH_CHECK("dnn_fprop_kernel");
-    g_dnn_last_tm = tm;
-    g_dnn_last_slices = 0;
-    g_dnn_last_form = form;
-    g_dnn_last_act = g_dnn_last_has_bias = 0;
-    return NP_OK;
-}
-
-template <int FORM>
-void launch_fprop_epi_form(int tm, dim3 grid, dim3 block, const ConvArgs &a, const float *bias, int act) {
-    EpiArgs<FORM> e;
-    static_cast<KernelArgs<FORM> &>(e) = a;
-    e.bias = bias;
-    e.act = act;
-    if (tm == kTMSmall) dnn_fprop_kernel<kTMSmall, FORM, true><<<grid, block, 0, np::stream()>>>(e);
-    else if (tm == kTMMid) dnn_fprop_kernel<kTMMid, FORM, true><<<grid, block, 0, np::stream()>>>(e);
-    else dnn_fprop_kernel<kTMLarge, FORM, true><<<grid, block, 0, np::stream()>>>(e);
-}
-
-// the forward pass with the layer's epilogue: a bias, an activation or both (form 0 or 1)
-int launch_fprop_epi(const ConvArgs &a, const float *bias, int act) {
-    const int tm = pick_tm((size_t)a.F);
-    const size_t tiles = (((size_t)a.F + tm - 1) / tm) * (((size_t)a.NP + kTN - 1) / kTN);
-    if (tiles >= kLim) return np::fail(NP_ERR_INVALID, "np_conv2d: %zu tiles are more than one launch holds", tiles);
-    const dim3 grid((unsigned)tiles), block(256);
-    const int form = form_of(a);
-    if (form == 0) launch_fprop_epi_form<0>(tm, grid, block, a, bias, act);
-    else launch_fprop_epi_form<1>(tm, grid, block, a, bias, act);
+    const bool epi = bias || act != NP_ACT_NONE;
+    if (form == 2) launch_fprop_form<2, false>(tm, grid, block, a, nullptr, NP_ACT_NONE);
+    else if (form == 1 && epi) launch_fprop_form<1, true>(tm, grid, block, a, bias, act);
+    else if (form == 1) launch_fprop_form<1, false>(tm, grid, block, a, nullptr, NP_ACT_NONE);
+    else if (epi) launch_fprop_form<0, true>(tm, grid, block, a, bias, act);
+    else launch_fprop_form<0, false>(tm, grid, block, a, nullptr, NP_ACT_NONE);
     NP_LAUNCH_CHECK("dnn_fprop_kernel");
     g_dnn_last_tm = tm;
     g_dnn_last_slices = 0;
@@ -696,50 +659,35 @@ int flip_filters(const ConvArgs &l, const float *w, np::Scratch &flipped) {
     return NP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int np_conv2d_shape(size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw, size_t *oh, size_t *ow) {
-    if (!oh || !ow) return np::fail(NP_ERR_INVALID, "np_conv2d_shape: null pointer");
-    if (int rc = check_spatial("np_conv2d_shape", H, W, kh, kw, ph, pw)) return rc;
-    *oh = H + 2 * ph - kh + 1;
-    *ow = W + 2 * pw - kw + 1;
-    return NP_OK;
-}
-
-int np_conv2d_forward(const float *x, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw, size_t ph,
-                      size_t pw, float *y) {
-    // pointers, then the shape, then work: a refused call has touched no device
-    if (!x || !w || !y) return np::fail(NP_ERR_INVALID, "np_conv2d_forward: null pointer");
+// The three passes.  Every entry point below is a pointer check under its own name and one call of these: the plain calls
+// with stride and dilation 1, the plain and _ex forward with no bias and NP_ACT_NONE.  The order is the shape, the activation,
+// ensure_init, then work: a refused call has touched no device.
+int conv_forward(const char *who, const float *x, const float *w, const float *bias, const LayerShape &s, int act, float *y) {
     ConvArgs a = {};
-    if (int rc = check_layer("np_conv2d_forward", N, C, H, W, F, kh, kw, ph, pw, a)) return rc;
+    if (int rc = check_layer(who, s, a)) return rc;
+    if (act < NP_ACT_NONE || act > NP_ACT_SIGMOID) return np::fail(NP_ERR_INVALID, "%s: unknown activation %d", who, act);
     if (int rc = np::ensure_init()) return rc;
     a.x = x;
     a.w = w;
     a.out = y;
-    return launch_fprop(a);
+    return launch_fprop(a, bias, act);
 }
 
-int np_conv2d_backward_data(const float *dy, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
-                            size_t ph, size_t pw, float *dx) {
-    if (!dy || !w || !dx) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_data: null pointer");
+int conv_backward_data(const char *who, const float *dy, const float *w, const LayerShape &s, float *dx) {
     ConvArgs l = {};
-    if (int rc = check_layer("np_conv2d_backward_data", N, C, H, W, F, kh, kw, ph, pw, l)) return rc;
+    if (int rc = check_layer(who, s, l)) return rc;
     if (int rc = np::ensure_init()) return rc;
     np::Scratch flipped;   // released on every path below
     if (int rc = flip_filters(l, w, flipped)) return rc;
-    return launch_fprop(dgrad_layer(l, dy, (const float *)flipped.ptr, dx));
+    return launch_fprop(dgrad_layer(l, dy, (const float *)flipped.ptr, dx), nullptr, NP_ACT_NONE);
 }
 
-int np_conv2d_backward_filter(const float *x, const float *dy, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
-                              size_t ph, size_t pw, float *dw) {
-    if (!x || !dy || !dw) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_filter: null pointer");
+int conv_backward_filter(const char *who, const float *x, const float *dy, const LayerShape &s, float *dw) {
     ConvArgs a = {};
-    if (int rc = check_layer("np_conv2d_backward_filter", N, C, H, W, F, kh, kw, ph, pw, a)) return rc;
+    if (int rc = check_layer(who, s, a)) return rc;
     if (int rc = np::ensure_init()) return rc;
     WgradPlan pl;
-    if (int rc = plan_wgrad("np_conv2d_backward_filter", a, pl)) return rc;
+    if (int rc = plan_wgrad(who, a, pl)) return rc;
     np::Scratch part;   // released on every path below
     if (pl.slices > 1)
         if (int rc = part.alloc(pl.slices * (size_t)a.F * a.K * sizeof(float))) return rc;
@@ -749,81 +697,67 @@ int np_conv2d_backward_filter(const float *x, const float *dy, size_t N, size_t 
     return launch_wgrad(a, pl, (const float *)part.ptr, dw);
 }
 
-int np_debug_dnn_last_path(int *host_tm, int *host_slices) {
-    if (!host_tm || !host_slices) return np::fail(NP_ERR_INVALID, "np_debug_dnn_last_path: null pointer");
-    *host_tm = g_dnn_last_tm;
-    *host_slices = g_dnn_last_slices;
-    return NP_OK;
+}  // namespace
+
+extern "C" {
+
+// ---- the plain calls: stride 1, dilation 1 ----
+
+int np_conv2d_shape(size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw, size_t *oh, size_t *ow) {
+    if (!oh || !ow) return np::fail(NP_ERR_INVALID, "np_conv2d_shape: null pointer");
+    return check_spatial("np_conv2d_shape", {1, 1, H, W, 1, kh, kw, ph, pw, 1, 1, 1, 1}, *oh, *ow);
 }
 
-int np_debug_dnn_last_form(int *host_form) {
-    if (!host_form) return np::fail(NP_ERR_INVALID, "np_debug_dnn_last_form: null pointer");
-    *host_form = g_dnn_last_form;
-    return NP_OK;
+int np_conv2d_forward(const float *x, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw, size_t ph,
+                      size_t pw, float *y) {
+    if (!x || !w || !y) return np::fail(NP_ERR_INVALID, "np_conv2d_forward: null pointer");
+    return conv_forward("np_conv2d_forward", x, w, nullptr, {N, C, H, W, F, kh, kw, ph, pw, 1, 1, 1, 1}, NP_ACT_NONE, y);
 }
+
+int np_conv2d_backward_data(const float *dy, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
+                            size_t ph, size_t pw, float *dx) {
+    if (!dy || !w || !dx) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_data: null pointer");
+    return conv_backward_data("np_conv2d_backward_data", dy, w, {N, C, H, W, F, kh, kw, ph, pw, 1, 1, 1, 1}, dx);
+}
+
+int np_conv2d_backward_filter(const float *x, const float *dy, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
+                              size_t ph, size_t pw, float *dw) {
+    if (!x || !dy || !dw) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_filter: null pointer");
+    return conv_backward_filter("np_conv2d_backward_filter", x, dy, {N, C, H, W, F, kh, kw, ph, pw, 1, 1, 1, 1}, dw);
+}
+
+// ---- _ex: a window stride and a tap dilation ----
 
 int np_conv2d_shape_ex(size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, size_t *oh,
                        size_t *ow) {
     if (!oh || !ow) return np::fail(NP_ERR_INVALID, "np_conv2d_shape_ex: null pointer");
-    size_t keh, kew, h, w;
-    if (int rc = check_spatial_ex("np_conv2d_shape_ex", H, W, kh, kw, ph, pw, sh, sw, dh, dw, keh, kew, h, w)) return rc;
-    *oh = h;
-    *ow = w;
-    return NP_OK;
+    return check_spatial("np_conv2d_shape_ex", {1, 1, H, W, 1, kh, kw, ph, pw, sh, sw, dh, dw}, *oh, *ow);
 }
 
 int np_conv2d_forward_ex(const float *x, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw, size_t ph,
                          size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, float *y) {
     if (!x || !w || !y) return np::fail(NP_ERR_INVALID, "np_conv2d_forward_ex: null pointer");
-    ConvArgs a = {};
-    if (int rc = check_layer_ex("np_conv2d_forward_ex", N, C, H, W, F, kh, kw, ph, pw, sh, sw, dh, dw, a)) return rc;
-    if (int rc = np::ensure_init()) return rc;
-    a.x = x;
-    a.w = w;
-    a.out = y;
-    return launch_fprop(a);
+    return conv_forward("np_conv2d_forward_ex", x, w, nullptr, {N, C, H, W, F, kh, kw, ph, pw, sh, sw, dh, dw}, NP_ACT_NONE, y);
 }
 
 int np_conv2d_backward_data_ex(const float *dy, const float *w, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
                                size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, float *dx) {
     if (!dy || !w || !dx) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_data_ex: null pointer");
-    ConvArgs l = {};
-    if (int rc = check_layer_ex("np_conv2d_backward_data_ex", N, C, H, W, F, kh, kw, ph, pw, sh, sw, dh, dw, l)) return rc;
-    if (int rc = np::ensure_init()) return rc;
-    np::Scratch flipped;   // released on every path below
-    if (int rc = flip_filters(l, w, flipped)) return rc;
-    return launch_fprop(dgrad_layer(l, dy, (const float *)flipped.ptr, dx));
+    return conv_backward_data("np_conv2d_backward_data_ex", dy, w, {N, C, H, W, F, kh, kw, ph, pw, sh, sw, dh, dw}, dx);
 }
 
 int np_conv2d_backward_filter_ex(const float *x, const float *dy, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh, size_t kw,
                                  size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, float *dw_out) {
     if (!x || !dy || !dw_out) return np::fail(NP_ERR_INVALID, "np_conv2d_backward_filter_ex: null pointer");
-    ConvArgs a = {};
-    if (int rc = check_layer_ex("np_conv2d_backward_filter_ex", N, C, H, W, F, kh, kw, ph, pw, sh, sw, dh, dw, a)) return rc;
-    if (int rc = np::ensure_init()) return rc;
-    WgradPlan pl;
-    if (int rc = plan_wgrad("np_conv2d_backward_filter_ex", a, pl)) return rc;
-    np::Scratch part;   // released on every path below
-    if (pl.slices > 1)
-        if (int rc = part.alloc(pl.slices * (size_t)a.F * a.K * sizeof(float))) return rc;
-    a.x = x;
-    a.w = dy;
-    a.out = pl.slices > 1 ? (float *)part.ptr : dw_out;
-    return launch_wgrad(a, pl, (const float *)part.ptr, dw_out);
+    return conv_backward_filter("np_conv2d_backward_filter_ex", x, dy, {N, C, H, W, F, kh, kw, ph, pw, sh, sw, dh, dw}, dw_out);
 }
+
+// ---- _act: the layer's bias and activation ----
 
 int np_conv2d_forward_act(const float *x, const float *w, const float *bias, size_t N, size_t C, size_t H, size_t W, size_t F, size_t kh,
                           size_t kw, size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, int act, float *y) {
     if (!x || !w || !y) return np::fail(NP_ERR_INVALID, "np_conv2d_forward_act: null pointer");
-    ConvArgs a = {};
-    if (int rc = check_layer_ex("np_conv2d_forward_act", N, C, H, W, F, kh, kw, ph, pw, sh, sw, dh, dw, a)) return rc;
-    if (act < NP_ACT_NONE || act > NP_ACT_SIGMOID) return np::fail(NP_ERR_INVALID, "np_conv2d_forward_act: unknown activation %d", act);
-    if (int rc = np::ensure_init()) return rc;
-    a.x = x;
-    a.w = w;
-    a.out = y;
-    if (!bias && act == NP_ACT_NONE) return launch_fprop(a);   // the plain kernels, the plain bits
-    return launch_fprop_epi(a, bias, act);
+    return conv_forward("np_conv2d_forward_act", x, w, bias, {N, C, H, W, F, kh, kw, ph, pw, sh, sw, dh, dw}, act, y);
 }
 
 int np_conv2d_backward_act(const float *y, const float *dy, size_t N, size_t F, size_t P, int act, float *dz, float *db) {
@@ -842,6 +776,21 @@ int np_conv2d_backward_act(const float *y, const float *dy, size_t N, size_t F, 
         if (int rc = part.alloc(pl.slices * F * sizeof(float))) return rc;
     float *out = !db ? nullptr : pl.slices > 1 ? (float *)part.ptr : db;
     return launch_act_grad(pl, y, dy, dz, out, db, F, P, N * P, act);
+}
+
+// ---- the probes: what the last launch chose ----
+
+int np_debug_dnn_last_path(int *host_tm, int *host_slices) {
+    if (!host_tm || !host_slices) return np::fail(NP_ERR_INVALID, "np_debug_dnn_last_path: null pointer");
+    *host_tm = g_dnn_last_tm;
+    *host_slices = g_dnn_last_slices;
+    return NP_OK;
+}
+
+int np_debug_dnn_last_form(int *host_form) {
+    if (!host_form) return np::fail(NP_ERR_INVALID, "np_debug_dnn_last_form: null pointer");
+    *host_form = g_dnn_last_form;
+    return NP_OK;
 }
 
 int np_debug_dnn_last_epilogue(int *act, int *has_bias, int *bias_slices) {

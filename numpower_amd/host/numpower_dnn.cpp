@@ -7,6 +7,8 @@
 // The host library has no CPU convolution: CPU operands get the glue's message.
 // A translation unit of its own: the sanitizer build of numpower_host.cpp (tests/test_host_sanitizers_cpu.py) links
 // against a null device that has no convolution.
+#include <optional>
+
 #include "hip_dnn.h"
 #include "numpower_host.h"
 #include "numpower_operand.h"
@@ -15,7 +17,22 @@ using numpower_host::Operand;
 
 namespace {
 
-bool on_gpu(NDArray *a) { return NDArray_DEVICE(a) == NDARRAY_DEVICE_GPU; }
+// glue(a, b, c, d) for up to four operands, nullptr for one the call does not have.  CPU operands are handed on as they are:
+// they only ever meet the argument checks and the device messages.  Otherwise each operand is made contiguous for the call,
+// in argument order; nullptr at the first that cannot be.
+template <class Glue>
+auto on_contiguous(Glue glue, NDArray *a, NDArray *b, NDArray *c = nullptr, NDArray *d = nullptr) -> decltype(glue(a, b, c, d)) {
+    NDArray *arr[4] = {a, b, c, d};
+    for (NDArray *p : arr)
+        if (p && NDArray_DEVICE(p) != NDARRAY_DEVICE_GPU) return glue(a, b, c, d);
+    std::optional<Operand> held[4];
+    for (int i = 0; i < 4; ++i) {
+        if (!arr[i]) continue;
+        arr[i] = held[i].emplace(arr[i]).arr;
+        if (!arr[i]) return nullptr;
+    }
+    return glue(arr[0], arr[1], arr[2], arr[3]);
+}
 
 }  // namespace
 
@@ -24,46 +41,27 @@ extern "C" {
 NDArray *NDArrayDNN_Conv2D_Forward(NDArray *x, NDArray *filters, int *kernel_size, char activation, int use_bias) {
     (void) kernel_size, (void) activation, (void) use_bias;
     if (!x || !filters) return nullptr;
-    // CPU operands are handed on as they are: they only ever meet the argument checks and the device messages
-    if (!on_gpu(x) || !on_gpu(filters)) return NPH_Conv2D_Forward(x, filters);
-    Operand cx(x);
-    if (!cx.arr) return nullptr;
-    Operand cf(filters);
-    return cf.arr ? NPH_Conv2D_Forward(cx.arr, cf.arr) : nullptr;
+    return on_contiguous([](NDArray *cx, NDArray *cf, NDArray *, NDArray *) { return NPH_Conv2D_Forward(cx, cf); }, x, filters);
 }
 
 NDArray **NDArrayDNN_Conv2D_Backward(NDArray *input, NDArray *y, NDArray *filters, int kernel_size, char activation, int use_bias) {
     (void) kernel_size, (void) activation, (void) use_bias;
     if (!input || !y || !filters) return nullptr;
-    if (!on_gpu(input) || !on_gpu(y) || !on_gpu(filters)) return NPH_Conv2D_Backward(input, y, filters);
-    Operand cx(input);
-    if (!cx.arr) return nullptr;
-    Operand cy(y);
-    if (!cy.arr) return nullptr;
-    Operand cf(filters);
-    return cf.arr ? NPH_Conv2D_Backward(cx.arr, cy.arr, cf.arr) : nullptr;
+    return on_contiguous([](NDArray *cx, NDArray *cy, NDArray *cf, NDArray *) { return NPH_Conv2D_Backward(cx, cy, cf); }, input, y, filters);
 }
 
 // The same layer with a stride, a padding and a dilation ((rows, columns) each, nullptr: 1, 0, 1): what the reference's layer
 // signature names (dnn.c:196-200) and its functions cannot express.
 NDArray *NDArrayDNN_Conv2D_ForwardEx(NDArray *x, NDArray *filters, const int *stride, const int *padding, const int *dilation) {
     if (!x || !filters) return nullptr;
-    if (!on_gpu(x) || !on_gpu(filters)) return NPH_Conv2D_ForwardEx(x, filters, stride, padding, dilation);
-    Operand cx(x);
-    if (!cx.arr) return nullptr;
-    Operand cf(filters);
-    return cf.arr ? NPH_Conv2D_ForwardEx(cx.arr, cf.arr, stride, padding, dilation) : nullptr;
+    return on_contiguous([=](NDArray *cx, NDArray *cf, NDArray *, NDArray *) { return NPH_Conv2D_ForwardEx(cx, cf, stride, padding, dilation); }, x,
+                         filters);
 }
 
 NDArray **NDArrayDNN_Conv2D_BackwardEx(NDArray *input, NDArray *y, NDArray *filters, const int *stride, const int *padding, const int *dilation) {
     if (!input || !y || !filters) return nullptr;
-    if (!on_gpu(input) || !on_gpu(y) || !on_gpu(filters)) return NPH_Conv2D_BackwardEx(input, y, filters, stride, padding, dilation);
-    Operand cx(input);
-    if (!cx.arr) return nullptr;
-    Operand cy(y);
-    if (!cy.arr) return nullptr;
-    Operand cf(filters);
-    return cf.arr ? NPH_Conv2D_BackwardEx(cx.arr, cy.arr, cf.arr, stride, padding, dilation) : nullptr;
+    return on_contiguous([=](NDArray *cx, NDArray *cy, NDArray *cf, NDArray *) { return NPH_Conv2D_BackwardEx(cx, cy, cf, stride, padding, dilation); },
+                         input, y, filters);
 }
 
 // The layer with a bias per filter (1-D (F,), or nullptr) and an activation ('r', 't', 's', 'n' or 0): what a binding with a bias
@@ -71,14 +69,9 @@ NDArray **NDArrayDNN_Conv2D_BackwardEx(NDArray *input, NDArray *y, NDArray *filt
 NDArray *NDArrayDNN_Conv2D_LayerForward(NDArray *x, NDArray *filters, NDArray *bias, const int *stride, const int *padding, const int *dilation,
                                         char activation) {
     if (!x || !filters) return nullptr;
-    if (!on_gpu(x) || !on_gpu(filters) || (bias && !on_gpu(bias))) return NPH_Conv2D_LayerForward(x, filters, bias, stride, padding, dilation, activation);
-    Operand cx(x);
-    if (!cx.arr) return nullptr;
-    Operand cf(filters);
-    if (!cf.arr) return nullptr;
-    if (!bias) return NPH_Conv2D_LayerForward(cx.arr, cf.arr, nullptr, stride, padding, dilation, activation);
-    Operand cb(bias);
-    return cb.arr ? NPH_Conv2D_LayerForward(cx.arr, cf.arr, cb.arr, stride, padding, dilation, activation) : nullptr;
+    return on_contiguous([=](NDArray *cx, NDArray *cf, NDArray *cb, NDArray *) {
+        return NPH_Conv2D_LayerForward(cx, cf, cb, stride, padding, dilation, activation);
+    }, x, filters, bias);
 }
 
 // out: the forward result (may be nullptr without an activation); dy: its gradient.  A malloc'd vector of three: dW, dX and db
@@ -86,17 +79,9 @@ NDArray *NDArrayDNN_Conv2D_LayerForward(NDArray *x, NDArray *filters, NDArray *b
 NDArray **NDArrayDNN_Conv2D_LayerBackward(NDArray *input, NDArray *out, NDArray *dy, NDArray *filters, const int *stride, const int *padding,
                                           const int *dilation, char activation, int use_bias) {
     if (!input || !dy || !filters) return nullptr;
-    if (!on_gpu(input) || !on_gpu(dy) || !on_gpu(filters) || (out && !on_gpu(out)))
-        return NPH_Conv2D_LayerBackward(input, out, dy, filters, stride, padding, dilation, activation, use_bias);
-    Operand cx(input);
-    if (!cx.arr) return nullptr;
-    Operand cy(dy);
-    if (!cy.arr) return nullptr;
-    Operand cf(filters);
-    if (!cf.arr) return nullptr;
-    if (!out) return NPH_Conv2D_LayerBackward(cx.arr, nullptr, cy.arr, cf.arr, stride, padding, dilation, activation, use_bias);
-    Operand co(out);
-    return co.arr ? NPH_Conv2D_LayerBackward(cx.arr, co.arr, cy.arr, cf.arr, stride, padding, dilation, activation, use_bias) : nullptr;
+    return on_contiguous([=](NDArray *cx, NDArray *cy, NDArray *cf, NDArray *co) {
+        return NPH_Conv2D_LayerBackward(cx, co, cy, cf, stride, padding, dilation, activation, use_bias);
+    }, input, dy, filters, out);
 }
 
 }  // extern "C"

@@ -905,12 +905,10 @@ class NDArray:
         act = NDArray._dnn_activation(activation)
         a, _ = NDArray._coerce(x)
         w, _ = NDArray._coerce(filters)
-        if bias is not None or activation is not None:
-            b = None if bias is None else NDArray._coerce(bias)[0]
-            return NDArray._wrap(h.NDArrayDNN_Conv2D_LayerForward(a._p, w._p, None if b is None else b._p, *(geometry or (None, None, None)), act))
-        if geometry is None:
+        if geometry is None and bias is None and activation is None:       # every keyword at its default: the call the PHP method makes
             return NDArray._wrap(h.NDArrayDNN_Conv2D_Forward(a._p, w._p, None, b"r", 1))
-        return NDArray._wrap(h.NDArrayDNN_Conv2D_ForwardEx(a._p, w._p, *geometry))
+        b = None if bias is None else NDArray._coerce(bias)[0]
+        return NDArray._wrap(h.NDArrayDNN_Conv2D_LayerForward(a._p, w._p, None if b is None else b._p, *(geometry or (None, None, None)), act))
 
     @staticmethod
     def dnn_conv2d_backward(x, y, filters, stride=1, padding=0, dilation=1, out=None, activation=None, bias=False):   # numpower.c:4348: NDArrayDNN_Conv2D_Backward(x, y, filters, 3, 'r', 1) -> RETURN_2NDARRAY
@@ -927,18 +925,14 @@ class NDArray:
         a, _ = NDArray._coerce(x)
         g, _ = NDArray._coerce(y)
         w, _ = NDArray._coerce(filters)
-        count = 2
-        if activation is not None or bias or out is not None:
-            o = None if out is None else NDArray._coerce(out)[0]
-            rtns = h.NDArrayDNN_Conv2D_LayerBackward(a._p, None if o is None else o._p, g._p, w._p, *(geometry or (None, None, None)), act, 1 if bias else 0)
-            count = 3 if bias else 2
-        elif geometry is None:
+        if geometry is None and out is None and activation is None and not bias:      # every keyword at its default: the PHP method's call
             rtns = h.NDArrayDNN_Conv2D_Backward(a._p, g._p, w._p, 3, b"r", 1)
         else:
-            rtns = h.NDArrayDNN_Conv2D_BackwardEx(a._p, g._p, w._p, *geometry)
+            o = None if out is None else NDArray._coerce(out)[0]
+            rtns = h.NDArrayDNN_Conv2D_LayerBackward(a._p, None if o is None else o._p, g._p, w._p, *(geometry or (None, None, None)), act, 1 if bias else 0)
         if not rtns:
             _raise_pending(h)
-        out_arrays = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(count))
+        out_arrays = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(3 if bias else 2))
         _libc_free(C.cast(rtns, C.c_void_p))
         return out_arrays
 

@@ -26,6 +26,11 @@ def _header(name, where="include"):
     return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", (ROOT / where / name).read_text(), flags=re.S))
 
 
+def _function(text, opening):
+    body = text[text.index(opening):]
+    return body[:body.index("\n}\n")]
+
+
 def test_abi_is_declared_below_the_ex_block_prototyped_and_exported():
     from numpower_amd import _lib
     text, lib = _header("np_hip.h"), _lib.load()
@@ -112,10 +117,12 @@ def test_every_refusal_comes_back_before_any_device_work():
     assert bwd(None, one, 2, 3, 4, 0, one, None) == _lib.NP_OK         # no activation, no db: dz = dy, nothing to do, no device
 
     src = (ROOT / "numpower_amd" / "csrc" / "np_dnn.hip").read_text()
-    body = src[src.index("int np_conv2d_forward_act("):]
-    body = body[:body.index("\n}\n")]
-    assert body.index("null pointer") < body.index("check_layer_ex(") < body.index("unknown activation") < body.index("ensure_init()") \
-        < body.index("launch_fprop(a)") < body.index("launch_fprop_epi(")
+    body = _function(src, "int np_conv2d_forward_act(")            # pointers, then the one forward body; inside that: shape, activation, work
+    assert body.index("null pointer") < body.index("return conv_forward(") and "<<<" not in body and ".alloc(" not in body
+    body = _function(src, "int conv_forward(")
+    assert body.index("check_layer(") < body.index("unknown activation") < body.index("ensure_init()") < body.index("launch_fprop(a, bias, act)")
+    body = _function(src, "int launch_fprop(")                     # one launcher: no bias and no activation take the plain instantiations
+    assert "const bool epi = bias || act != NP_ACT_NONE;" in body and "launch_fprop_form<0, false>" in body and "launch_fprop_form<2, true>" not in body
     body = src[src.index("int np_conv2d_backward_act("):]
     body = body[:body.index("\n}\n")]
     assert body.index("null pointer") < body.index("at least 1") < body.index("2^31") < body.index("unknown activation") < body.index("ensure_init()") \
@@ -143,14 +150,17 @@ def test_host_and_glue_declare_the_layer_functions():
     assert ("struct NDArray **NPH_Conv2D_LayerBackward(struct NDArray *x, struct NDArray *out, struct NDArray *dy, struct NDArray *filters, "
             "const int stride[2], const int padding[2], const int dilation[2], char activation, int use_bias);") in glue
     src = (ROOT / "ext" / "hip_dnn.c").read_text()
-    assert src.index("NDArray **NPH_Conv2D_BackwardEx(") < src.index("static int activation_of(") < src.index("NDArray *NPH_Conv2D_LayerForward(")
-    fwd = src[src.index("NDArray *NPH_Conv2D_LayerForward("):src.index("NDArray **NPH_Conv2D_LayerBackward(")]
-    assert fwd.index("layer_extras(") < fwd.index("layer_of(") < fwd.index("np_conv2d_shape_ex(") < fwd.index("empty4_on_gpu(") < fwd.index("np_conv2d_forward_act(")
-    bwd = src[src.index("NDArray **NPH_Conv2D_LayerBackward("):]
-    assert bwd.index("layer_extras(") < bwd.index("layer_of(") < bwd.index("empty4_on_gpu(") < bwd.index("np_malloc(&dz") \
+    fwd = _function(src, "NDArray *NPH_Conv2D_LayerForward(")      # a wrapper: the geometry, the activation's code, then the one forward pass
+    assert fwd.index("geometry_of(stride, padding, dilation)") < fwd.index("return forward(x, filters, bias, &g, activation_of(activation));")
+    fwd = _function(src, "static NDArray *forward(")
+    assert fwd.index("layer_extras(") < fwd.index("layer_of(") < fwd.index("np_conv2d_shape_ex(") < fwd.index("empty_on_gpu(") < fwd.index("np_conv2d_forward_act(")
+    bwd = _function(src, "NDArray **NPH_Conv2D_LayerBackward(")
+    assert bwd.index("geometry_of(stride, padding, dilation)") < bwd.index("return backward(x, out, dy, filters, &g, activation_of(activation), use_bias, 3);")
+    bwd = _function(src, "static NDArray **backward(")
+    assert bwd.index("layer_extras(") < bwd.index("layer_of(") < bwd.index("empty_on_gpu(") < bwd.index("np_malloc(&dz") \
         < bwd.index("np_conv2d_backward_act(") < bwd.index("np_conv2d_backward_filter_ex(") < bwd.index("np_conv2d_backward_data_ex(") \
         < bwd.index("np_free(dz)") < bwd.index("if (!ok)") < bwd.index("rtns[0] = dw;") < bwd.index("rtns[1] = dx;") < bwd.index("rtns[2] = db;")
-    extras = src[src.index("static int layer_extras("):src.index("/* a new 1-d GPU array")]
+    extras = src[src.index("static int layer_extras("):src.index("/* a new GPU array")]
     order = [extras.index("NPH_DNN_MSG_" + n) for n in ("ACTIVATION", "BIAS)", "OUT", "BIAS_DEVICE")]
     assert order == sorted(order) and "NDArray_Empty" not in extras and "np_conv2d" not in extras
     tool = (ROOT / "tools" / "apply_with_hip.py").read_text()
@@ -268,12 +278,12 @@ def test_the_defaults_reach_the_old_host_functions(monkeypatch):
 
     assert refused(NDArray.dnn_conv2d_forward, x, w) == ["NDArrayDNN_Conv2D_Forward"]
     assert refused(NDArray.dnn_conv2d_forward, x, w, bias=None, activation=None) == ["NDArrayDNN_Conv2D_Forward"]
-    assert refused(NDArray.dnn_conv2d_forward, x, w, stride=2) == ["NDArrayDNN_Conv2D_ForwardEx"]
+    assert refused(NDArray.dnn_conv2d_forward, x, w, stride=2) == ["NDArrayDNN_Conv2D_LayerForward"]      # any keyword: the layer's function
     assert refused(NDArray.dnn_conv2d_forward, x, w, activation="relu") == ["NDArrayDNN_Conv2D_LayerForward"]
     assert refused(NDArray.dnn_conv2d_forward, x, w, bias=ones(4), stride=2) == ["NDArrayDNN_Conv2D_LayerForward"]
     assert refused(NDArray.dnn_conv2d_backward, x, dy, w) == ["NDArrayDNN_Conv2D_Backward"]
     assert refused(NDArray.dnn_conv2d_backward, x, dy, w, out=None, activation=None, bias=False) == ["NDArrayDNN_Conv2D_Backward"]
-    assert refused(NDArray.dnn_conv2d_backward, x, ones(2, 4, 3, 4), w, stride=2) == ["NDArrayDNN_Conv2D_BackwardEx"]
+    assert refused(NDArray.dnn_conv2d_backward, x, ones(2, 4, 3, 4), w, stride=2) == ["NDArrayDNN_Conv2D_LayerBackward"]
     assert refused(NDArray.dnn_conv2d_backward, x, dy, w, bias=True) == ["NDArrayDNN_Conv2D_LayerBackward"]
     assert refused(NDArray.dnn_conv2d_backward, x, dy, w, out=dy, activation="tanh") == ["NDArrayDNN_Conv2D_LayerBackward"]
     assert refused(NDArray.dnn_conv2d_backward, x, dy, w, activation="tanh") == []                  # refused before any host call

@@ -30,6 +30,11 @@ def _header(name, where="include"):
     return re.sub(r"\s+", " ", re.sub(r"/\*.*?\*/", "", (ROOT / where / name).read_text(), flags=re.S))
 
 
+def _function(text, opening):
+    body = text[text.index(opening):]
+    return body[:body.index("\n}\n")]
+
+
 def test_abi_is_declared_below_the_old_block_prototyped_and_exported():
     from numpower_amd import _lib
     text, lib = _header("np_hip.h"), _lib.load()
@@ -96,11 +101,13 @@ def test_every_refusal_comes_back_before_any_device_work():
     assert lib.np_conv2d_shape_ex(9, 10, 3, 3, 1, 1, 2, 3, 2, 2, C.byref(oh), C.byref(ow)) == _lib.NP_OK and (oh.value, ow.value) == (4, 3)
     assert lib.np_conv2d_shape_ex(224, 224, 7, 7, 3, 3, 2, 2, 1, 1, C.byref(oh), C.byref(ow)) == _lib.NP_OK and (oh.value, ow.value) == (112, 112)
     src = (ROOT / "numpower_amd" / "csrc" / "np_dnn.hip").read_text()
-    for name in EX:                            # the order inside each entry point: pointers, then the shape, then work
-        body = src[src.index("int %s(" % name):]
-        body = body[:body.index("\n}\n")]
+    for name, body_name in zip(EX, ("conv_forward", "conv_backward_data", "conv_backward_filter")):
+        # the order inside each entry point: pointers, then the one body it calls; inside that: the shape, then work
+        wrapper = _function(src, "int %s(" % name)
+        assert wrapper.index("null pointer") < wrapper.index("return %s(" % body_name) and "<<<" not in wrapper and ".alloc(" not in wrapper, name
+        body = _function(src, "int %s(" % body_name)
         work = min(body.index(w) for w in ("<<<", "launch_fprop(", "flip_filters(", "plan_wgrad(", ".alloc(") if w in body)
-        assert body.index("null pointer") < body.index("check_layer_ex(") < body.index("ensure_init()") < work, name
+        assert body.index("check_layer(") < body.index("ensure_init()") < work, name
 
 
 def test_unit_geometry_refuses_what_the_old_calls_refuse():
@@ -139,10 +146,14 @@ def test_host_and_glue_declare_the_ex_functions():
     assert ("struct NDArray **NPH_Conv2D_BackwardEx(struct NDArray *x, struct NDArray *y, struct NDArray *filters, const int stride[2], "
             "const int padding[2], const int dilation[2]);") in glue
     src = (ROOT / "ext" / "hip_dnn.c").read_text()
-    fwd = src[src.index("NDArray *NPH_Conv2D_ForwardEx("):src.index("NDArray **NPH_Conv2D_BackwardEx(")]
-    assert fwd.index("layer_of(") < fwd.index("np_conv2d_shape_ex(") < fwd.index("empty4_on_gpu(") < fwd.index("np_conv2d_forward_ex(")
-    bwd = src[src.index("NDArray **NPH_Conv2D_BackwardEx("):]
-    assert bwd.index("layer_of(") < bwd.index("empty4_on_gpu(") < bwd.index("np_conv2d_backward_filter_ex(") < bwd.index("np_conv2d_backward_data_ex(")
+    fwd = _function(src, "NDArray *NPH_Conv2D_ForwardEx(")         # a wrapper: the geometry, then the one forward pass
+    assert fwd.index("geometry_of(stride, padding, dilation)") < fwd.index("return forward(x, filters, NULL, &g, NP_ACT_NONE);")
+    fwd = _function(src, "static NDArray *forward(")
+    assert fwd.index("layer_of(") < fwd.index("np_conv2d_shape_ex(") < fwd.index("empty_on_gpu(") < fwd.index("np_conv2d_forward_act(")
+    bwd = _function(src, "NDArray **NPH_Conv2D_BackwardEx(")
+    assert bwd.index("geometry_of(stride, padding, dilation)") < bwd.index("return backward(x, NULL, y, filters, &g, NP_ACT_NONE, 0, 2);")
+    bwd = _function(src, "static NDArray **backward(")
+    assert bwd.index("layer_of(") < bwd.index("empty_on_gpu(") < bwd.index("np_conv2d_backward_filter_ex(") < bwd.index("np_conv2d_backward_data_ex(")
     assert bwd.index("rtns[0] = dw;") < bwd.index("rtns[1] = dx;")
     tool = (ROOT / "tools" / "apply_with_hip.py").read_text()
     assert "ForwardEx" not in tool and "BackwardEx" not in tool          # the reference-signature early-outs are what they were

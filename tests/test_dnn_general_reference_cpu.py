@@ -54,11 +54,11 @@ def test_the_evaluator_equals_torch_bit_for_bit_on_the_exact_family(xs, ws, g):
 
 def test_unit_geometry_is_the_unit_family():
     from tests import dnn_family as D
-    x, w, dy = D.exact(np.random.default_rng(5), (2, 3, 6, 7), (4, 3, 3, 2), 1, 1)
+    x, w, dy = D.exact(np.random.default_rng(5), (2, 3, 6, 7), (4, 3, 3, 2), D.Geo(1, 1))
     g = G.geo(1, 1)
-    assert np.array_equal(G.forward(x, w, g), D.forward(x, w, 1, 1))
-    assert np.array_equal(G.grad_w(x, dy, 3, 2, g), D.grad_w(x, dy, 3, 2, 1, 1))
-    assert np.array_equal(G.grad_x(dy, w, 6, 7, g), D.grad_x(dy, w, 6, 7, 1, 1))
+    assert np.array_equal(G.forward(x, w, g), D.forward(x, w, D.Geo(1, 1)))
+    assert np.array_equal(G.grad_w(x, dy, 3, 2, g), D.grad_w(x, dy, 3, 2, D.Geo(1, 1)))
+    assert np.array_equal(G.grad_x(dy, w, 6, 7, g), D.grad_x(dy, w, 6, 7, D.Geo(1, 1)))
 
 
 @pytest.mark.parametrize("xs,ws,g", SHAPES)

@@ -90,7 +90,9 @@ def test_null_and_bad_shape_arguments_are_refused_before_any_device_work():
                           ((1, 2, 5, 5, 3, 6, 3, 0, 0), b"larger than the padded image"), ((1, 2, 5, 5, 3, 3, 10, 0, 2), b"larger than the padded image"),
                           ((1 << 16, 1 << 15, 1, 1, 1, 1, 1, 0, 0), b"2^31"), ((1, 1 << 16, 1, 1, 1 << 15, 1, 1, 0, 0), b"2^31"),
                           ((1 << 16, 1, 1, 1, 1 << 15, 1, 1, 0, 0), b"2^31"), ((1, 1, 1 << 31, 1, 1, 1, 1, 0, 0), b"2^31"),
-                          ((1 << 40, 1 << 40, 1, 1, 1, 1, 1, 0, 0), b"2^31")):
+                          ((1 << 40, 1 << 40, 1, 1, 1, 1, 1, 0, 0), b"2^31"),
+                          # a padded extent H + 2 ph (W + 2 pw) of 2^31 + 4 with every count below 2^31: the row index i + p - ph is an int
+                          ((1, 1, (1 << 31) - 2, 1, 1, 6, 1, 3, 0), b"2^31"), ((1, 1, 1, (1 << 31) - 2, 1, 1, 6, 0, 3), b"2^31")):
             assert call(one, one, *bad, one) == NP_ERR_INVALID and word in lib.np_last_error(), (name, bad)
     oh, ow = C.c_size_t(77), C.c_size_t(77)
     assert lib.np_conv2d_shape(5, 5, 3, 3, 0, 0, None, C.byref(ow)) == NP_ERR_INVALID
@@ -98,13 +100,15 @@ def test_null_and_bad_shape_arguments_are_refused_before_any_device_work():
     assert lib.np_conv2d_shape(5, 7, 3, 2, 2, 1, C.byref(oh), C.byref(ow)) == _lib.NP_OK and (oh.value, ow.value) == (7, 8)
     assert lib.np_conv2d_shape(3, 3, 5, 5, 4, 4, C.byref(oh), C.byref(ow)) == _lib.NP_OK and (oh.value, ow.value) == (7, 7)
     src = (ROOT / "numpower_amd" / "csrc" / "np_dnn.hip").read_text()
-    for name in ENTRY_POINTS:                  # the order inside each entry point: pointers, then the shape, then work
-        body = src[src.index("int %s(" % name):]
-        body = body[:body.index("\n}\n")]
-        work = min(body.index(w) for w in ("<<<", "launch_fprop(", ".alloc(") if w in body)
-        assert body.index("null pointer") < body.index("check_layer(") < body.index("ensure_init()") < work, name
-    checks = src[src.index("int check_spatial("):src.index("int launch_fprop(")]
-    assert checks.count("NP_ERR_INVALID") >= 5 and "<<<" not in checks and "alloc" not in checks
+    for name, body_name in zip(ENTRY_POINTS, ("conv_forward", "conv_backward_data", "conv_backward_filter")):
+        # the order inside each entry point: pointers, then the one body it calls; inside that: the shape, then work
+        wrapper = _function(src, "int %s(" % name)
+        assert wrapper.index("null pointer") < wrapper.index("return %s(" % body_name) and "<<<" not in wrapper and ".alloc(" not in wrapper, name
+        body = _function(src, "int %s(" % body_name)
+        work = min(body.index(w) for w in ("<<<", "launch_fprop(", "flip_filters(", "plan_wgrad(", ".alloc(") if w in body)
+        assert body.index("check_layer(") < body.index("ensure_init()") < work, name
+    checks = src[src.index("int check_spatial("):src.index("ConvArgs dgrad_layer(")]
+    assert "int check_layer(" in checks and checks.count("NP_ERR_INVALID") >= 5 and "<<<" not in checks and "alloc" not in checks
     assert "atomic" not in src.replace("No float atomics", "")
 
 
@@ -153,16 +157,20 @@ def test_each_message_is_raised_with_its_text():
 
 def test_the_glue_checks_before_it_allocates_and_keeps_the_reference_order():
     src = (ROOT / "ext" / "hip_dnn.c").read_text()
-    checks = src[src.index("static int layer_of("):src.index("/* a new 4-d GPU array")]
+    checks = src[src.index("static int layer_of("):src.index("/* NULL: the default */")]
     order = [checks.index("NPH_DNN_MSG_" + n) for n in ("NDIM", "CHANNELS", "WINDOW", "GRADIENT", "DEVICE", "CPU")]
     assert order == sorted(order) and "NDArray_Empty" not in checks and "np_conv2d" not in checks
-    fwd = src[src.index("NDArray *NPH_Conv2D_Forward("):src.index("NDArray **NPH_Conv2D_Backward(")]
-    assert fwd.index("layer_of(") < fwd.index("np_conv2d_shape(") < fwd.index("empty4_on_gpu(") < fwd.index("np_conv2d_forward(")
+    assert "NDArray *NPH_Conv2D_Forward(NDArray *x, NDArray *filters) { return forward(x, filters, NULL, NULL, NP_ACT_NONE); }" in src
+    assert ("NDArray **NPH_Conv2D_Backward(NDArray *x, NDArray *y, NDArray *filters) { return backward(x, NULL, y, filters, NULL, NP_ACT_NONE, 0, 2); }"
+            in src)
+    fwd = _function(src, "static NDArray *forward(")              # the one forward pass, which the call above reaches
+    assert fwd.index("layer_of(") < fwd.index("np_conv2d_shape_ex(") < fwd.index("empty_on_gpu(") < fwd.index("np_conv2d_forward_act(")
     assert "np_ext_throw_last();" in fwd and "NDArray_FREE(rtn);" in fwd
-    bwd = src[src.index("NDArray **NPH_Conv2D_Backward("):]
-    assert bwd.index("layer_of(") < bwd.index("empty4_on_gpu(") < bwd.index("np_conv2d_backward_filter(") < bwd.index("np_conv2d_backward_data(")
+    bwd = _function(src, "static NDArray **backward(")            # and the one backward pass
+    assert bwd.index("layer_of(") < bwd.index("empty_on_gpu(") < bwd.index("np_conv2d_backward_filter_ex(") < bwd.index("np_conv2d_backward_data_ex(")
     assert bwd.index("rtns[0] = dw;") < bwd.index("rtns[1] = dx;") and "np_ext_throw_last();" in bwd
-    assert "empty4_on_gpu(l.F, l.C, l.kh, l.kw)" in bwd and "empty4_on_gpu(l.N, l.C, l.H, l.W)" in bwd      # the filters' own shape, the input's
+    assert "dw_dims[4] = {l.F, l.C, l.kh, l.kw}" in bwd and "dx_dims[4] = {l.N, l.C, l.H, l.W}" in bwd      # the filters' own shape, the input's
+    assert "empty_on_gpu(4, dw_dims)" in bwd and "empty_on_gpu(4, dx_dims)" in bwd
     assert "hip_dnn.c" in (ROOT / "ext" / "config.m4").read_text() and "hip_dnn.c" in (ROOT / "ext" / "README.md").read_text()
 
 

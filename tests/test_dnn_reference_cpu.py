@@ -27,31 +27,33 @@ def _torch_all(x, w, dy, ph, pw):
 @pytest.mark.parametrize("xs,ws,pad", SHAPES)
 def test_the_evaluator_equals_torch_bit_for_bit_on_the_exact_family(xs, ws, pad):
     ph, pw = pad
-    x, w, dy = D.exact(np.random.default_rng(xs[3] + ws[0]), xs, ws, ph, pw)
+    g = D.Geo(ph, pw)
+    x, w, dy = D.exact(np.random.default_rng(xs[3] + ws[0]), xs, ws, g)
     ix, iw, idy = D.as_int(x), D.as_int(w), D.as_int(dy)
-    want = (D.forward(ix, iw, ph, pw), D.grad_w(ix, idy, ws[2], ws[3], ph, pw), D.grad_x(idy, iw, xs[2], xs[3], ph, pw))
-    assert want[0].dtype == np.int64 and want[0].shape == (xs[0], ws[0]) + D.out_hw(xs[2], xs[3], ws[2], ws[3], ph, pw)
+    want = (D.forward(ix, iw, g), D.grad_w(ix, idy, ws[2], ws[3], g), D.grad_x(idy, iw, xs[2], xs[3], g))
+    assert want[0].dtype == np.int64 and want[0].shape == (xs[0], ws[0]) + D.out_hw(xs[2], xs[3], ws[2], ws[3], g)
     for got, ref in zip(_torch_all(x, w, dy, ph, pw), want):
         assert got.shape == ref.shape and np.array_equal(got, ref.astype(np.float32))
-    for got, ref in zip((D.forward(x, w, ph, pw), D.grad_w(x, dy, ws[2], ws[3], ph, pw), D.grad_x(dy, w, xs[2], xs[3], ph, pw)), want):
+    for got, ref in zip((D.forward(x, w, g), D.grad_w(x, dy, ws[2], ws[3], g), D.grad_x(dy, w, xs[2], xs[3], g)), want):
         assert got.dtype == np.float64 and np.array_equal(got, ref)             # the float64 path is the same evaluator
 
 
 @pytest.mark.parametrize("xs,ws,pad", SHAPES)
 def test_the_data_gradient_is_the_forward_pass_over_dy_with_the_flipped_filters(xs, ws, pad):
     ph, pw = pad
-    _, w, dy = D.exact(np.random.default_rng(xs[2] + ws[1]), xs, ws, ph, pw)
+    g = D.Geo(ph, pw)
+    _, w, dy = D.exact(np.random.default_rng(xs[2] + ws[1]), xs, ws, g)
     iw, idy = D.as_int(w), D.as_int(dy)
     flipped = D.flipped(iw)
     assert flipped.shape == (ws[1], ws[0], ws[2], ws[3]) and flipped[0, -1, 0, -1] == iw[-1, 0, -1, 0]
-    assert np.array_equal(D.forward(idy, flipped, ws[2] - 1 - ph, ws[3] - 1 - pw), D.grad_x(idy, iw, xs[2], xs[3], ph, pw))
+    assert np.array_equal(D.forward(idy, flipped, D.Geo(ws[2] - 1 - ph, ws[3] - 1 - pw)), D.grad_x(idy, iw, xs[2], xs[3], g))
 
 
 def test_stored_zeros_meet_an_inf_tap_as_nan():
     x = np.ones((1, 1, 3, 3), np.float32)
     w = np.ones((1, 1, 2, 2), np.float32)
     w[0, 0, 0, 0] = np.inf
-    y = D.forward(x, w, 1, 1)
+    y = D.forward(x, w, D.Geo(1, 1))
     assert np.array_equal(np.isnan(y[0, 0]), np.array([[1, 1, 1, 1], [1, 0, 0, 0], [1, 0, 0, 0], [1, 0, 0, 0]], bool))
     assert np.all(np.isposinf(y[0, 0][1:, 1:]))
     t = torch.nn.functional.conv2d(torch.nn.functional.pad(torch.tensor(x), (1, 1, 1, 1)), torch.tensor(w)).numpy()

@@ -75,7 +75,7 @@ def _abi(hip, op, a, b, xs, ws, ph=0, pw=0):
     (N, Cc, H, W), (F, _, kh, kw) = xs, ws
     oh, ow = C.c_size_t(), C.c_size_t()
     _l.check(lib.np_conv2d_shape(H, W, kh, kw, ph, pw, C.byref(oh), C.byref(ow)))
-    assert (oh.value, ow.value) == D.out_hw(H, W, kh, kw, ph, pw)
+    assert (oh.value, ow.value) == D.out_hw(H, W, kh, kw, D.Geo(ph, pw))
     call, shape = {"y": (lib.np_conv2d_forward, (N, F, oh.value, ow.value)), "dx": (lib.np_conv2d_backward_data, tuple(xs)),
                    "dw": (lib.np_conv2d_backward_filter, tuple(ws))}[op]
     da, db, do = hip.DeviceArray.from_host(a), hip.DeviceArray.from_host(b), hip.DeviceArray(shape)
@@ -93,12 +93,12 @@ def _all_abi(hip, x, w, dy, ph=0, pw=0):
 
 
 def _all_ref(x, w, dy, ph=0, pw=0, blas=False):
-    return (D.forward(x, w, ph, pw, blas), D.grad_w(x, dy, w.shape[2], w.shape[3], ph, pw, blas),
-            D.grad_x(dy, w, x.shape[2], x.shape[3], ph, pw, blas))
+    g = D.Geo(ph, pw)
+    return (D.forward(x, w, g, blas), D.grad_w(x, dy, w.shape[2], w.shape[3], g, blas), D.grad_x(dy, w, x.shape[2], x.shape[3], g, blas))
 
 
 def _check_exact(hip, xs, ws, ph=0, pw=0, seed=0):
-    x, w, dy = D.exact(np.random.default_rng(seed + 131 * xs[3] + ws[0]), xs, ws, ph, pw)
+    x, w, dy = D.exact(np.random.default_rng(seed + 131 * xs[3] + ws[0]), xs, ws, D.Geo(ph, pw))
     want = _all_ref(D.as_int(x), D.as_int(w), D.as_int(dy), ph, pw)
     for name, got, ref in zip(("y", "dW", "dX"), _all_abi(hip, x, w, dy, ph, pw), want):
         assert got.shape == ref.shape, (name, xs, ws, ph, pw)
@@ -228,7 +228,7 @@ def test_an_inf_tap_over_the_padding_gives_nan(hip):
     x[x == 0] = 1.0                                # inside the image the Inf tap meets no zero: NaN comes from the padding alone
     w[1, 2, 0, 0] = np.inf
     for ph, pw in ((1, 1), (2, 3), (0, 2)):
-        want = D.forward(x, w, ph, pw)
+        want = D.forward(x, w, D.Geo(ph, pw))
         got = _abi(hip, "y", x, w, XS, WS, ph, pw)
         nan = np.isnan(want)
         assert nan[:, 1].any() and not nan[:, [0, 2, 3, 4]].any()
@@ -393,7 +393,7 @@ def test_c_abi_refusals_leave_the_outputs_untouched_and_nothing_leaks(hip):
 @pytest.mark.parametrize("xs,ws,ph,pw", [((3, 4, 9, 11), (5, 4, 3, 4), 0, 0), ((2, 3, 8, 8), (33, 3, 3, 3), 1, 1), ((4, 2, 30, 40), (3, 2, 5, 2), 4, 0)])
 def test_adjoint_identities_hold_as_exact_integers(hip, xs, ws, ph, pw):
     """<y, dy> = <x, dX> = <w, dW>, folded in int64 on the host"""
-    x, w, dy = D.exact(np.random.default_rng(ws[0]), xs, ws, ph, pw)
+    x, w, dy = D.exact(np.random.default_rng(ws[0]), xs, ws, D.Geo(ph, pw))
     y, dw, dx = _all_abi(hip, x, w, dy, ph, pw)
     dot = lambda a, b: int(np.sum(D.as_int(a) * D.as_int(b)))
     assert dot(y, dy) == dot(x, dx) == dot(w, dw)

@@ -10,7 +10,9 @@ stride, padding and dilation), through the C ABI and through NDArray.
 3. the form probe: 0 for unit geometry through either entry point, 1 for a strided forward / dW, 2 for dX of a strided layer;
 4. the bound |got - ref64| <= gamma(K) (|a| (*) |b|) on four Gaussian layers (derived, tests/dnn_family.gamma);
 5. NaN footprints: exactly the family's for a cell that is read, nothing for a cell no window reads, dy's dX and dW footprint;
-6. the surface: keyword forms, views and pending chains, every new message, no leak, the defaults bit for bit."""
+6. the surface: keyword forms, views and pending chains, every new message, no leak, the defaults bit for bit;
+7. one host path: the plain call, the _ex call at (1, 1, 1, 1) and np_conv2d_forward_act with NULL / NP_ACT_NONE return the same bits
+   and leave the same probes, on every tile height and with dW in two slices."""
 import ctypes as C
 import gc
 
@@ -501,3 +503,75 @@ def test_adjoint_identities_hold_as_exact_integers(hip, xs, ws, g):
     y, dw, dx = _all_abi(hip, x, w, dy, g)
     dot = lambda a, b: int(np.sum(G.as_int(a) * G.as_int(b)))
     assert dot(y, dy) == dot(x, dx) == dot(w, dw)
+
+
+# ---- 7. one host path: the plain, _ex and _act entry points are one call ----------------------------------------------------------
+
+def _probes():
+    """(TM, S, form) and (act, has_bias, bias_slices) of the last launch"""
+    _l, lib = _lib()
+    v = [C.c_int(-1) for _ in range(3)]
+    _l.check(lib.np_debug_dnn_last_epilogue(*(C.byref(c) for c in v)))
+    return _last() + tuple(c.value for c in v)
+
+
+def _spelled(hip, fn, a, b, shape, *args):
+    """fn(a, b, *args with None standing for the result) on device copies -> (host result, probes).  A strided relu layer runs
+    first: it leaves TM 32, form 1 and act 1 in the probes, which no unit-geometry call without an epilogue leaves."""
+    _l, lib = _lib()
+    da, db, do = hip.DeviceArray.from_host(a), hip.DeviceArray.from_host(b), hip.DeviceArray(shape)
+    d1 = hip.DeviceArray.from_host(np.ones((1, 1, 3, 3), np.float32))
+    try:
+        _l.check(lib.np_conv2d_forward_act(d1.ptr, d1.ptr, None, 1, 1, 3, 3, 1, 3, 3, 0, 0, 2, 2, 1, 1, 1, do.ptr))
+        assert _probes()[:5] == (32, 0, 1, 1, 0)
+        _l.check(fn(da.ptr, db.ptr, *(do.ptr if v is None else v for v in args)))
+        return do.to_host(), _probes()
+    finally:
+        for d in (da, db, do, d1):
+            d.free()
+
+
+# x, w, (ph, pw) -> TM of y and dW, S of dW.  The three tile heights; dW in two slices: 648 (512 without the padding) columns are
+# 21 (16) steps of 32, one tile, want = min(21 // 8, 512, 256) = 2 slices of 11 (8) steps
+SPELLINGS = [((2, 3, 6, 7), (32, 3, 3, 2), (1, 0), 32, 1), ((2, 3, 6, 7), (33, 3, 3, 2), (1, 0), 64, 1), ((2, 3, 6, 7), (65, 3, 3, 2), (1, 0), 128, 1),
+             ((2, 2, 18, 18), (3, 2, 3, 3), (1, 1), 32, 2), ((2, 2, 18, 18), (3, 2, 3, 3), (0, 0), 32, 2)]
+
+
+@pytest.mark.parametrize("xs,ws,pad,tm,slices", SPELLINGS)
+def test_one_call_three_spellings(hip, xs, ws, pad, tm, slices):
+    """The plain call, the _ex call at (1, 1, 1, 1) and np_conv2d_forward_act with NULL / NP_ACT_NONE: the same bits, the same
+    probes, the evaluator's integers; through NDArray the defaults and the keywords written out."""
+    _l, lib = _lib()
+    nd = _nd()
+    g = G.Geo(*pad)
+    (N, Cc, H, W), (F, _, kh, kw) = xs, ws
+    x, w, dy = G.exact(np.random.default_rng(F + H), xs, ws, g)
+    want = dict(zip(("y", "dw", "dx"), (r.astype(np.float32) for r in _all_ref(G.as_int(x), G.as_int(w), G.as_int(dy), g))))
+    ext, unit = (N, Cc, H, W, F, kh, kw) + pad, (1, 1, 1, 1)
+    assert _slices(F, Cc * kh * kw, N * dy.shape[2] * dy.shape[3]) == slices          # the rule at plan_wgrad; the probe is asserted below
+
+    oh, ow, eh, ew = (C.c_size_t() for _ in range(4))
+    _l.check(lib.np_conv2d_shape(H, W, kh, kw, *pad, C.byref(oh), C.byref(ow)))
+    _l.check(lib.np_conv2d_shape_ex(H, W, kh, kw, *pad, *unit, C.byref(eh), C.byref(ew)))
+    assert (oh.value, ow.value) == (eh.value, ew.value) == dy.shape[2:] == G.out_hw(H, W, kh, kw, g)
+
+    spellings = {
+        "y": (x, w, dy.shape, (tm, 0, 0, 0, 0), [(lib.np_conv2d_forward, ext + (None,)), (lib.np_conv2d_forward_ex, ext + unit + (None,)),
+                                           (lambda a, b, *r: lib.np_conv2d_forward_act(a, b, None, *r), ext + unit + (0, None))]),
+        "dx": (dy, w, xs, (_tm(Cc), 0, 0, 0, 0), [(lib.np_conv2d_backward_data, ext + (None,)), (lib.np_conv2d_backward_data_ex, ext + unit + (None,))]),
+        # dW has no epilogue and leaves those two probes as the relu layer before it set them
+        "dw": (x, dy, ws, (tm, slices, 0, 1, 0), [(lib.np_conv2d_backward_filter, ext + (None,)), (lib.np_conv2d_backward_filter_ex, ext + unit + (None,))]),
+    }
+    for op, (a, b, shape, path, calls) in spellings.items():
+        results = [_spelled(hip, fn, a, b, shape, *args) for fn, args in calls]
+        for got, probes in results:
+            assert _same(got, results[0][0]) and probes == results[0][1], op
+            assert probes[:5] == path, (op, probes)                                    # TM, S, the unit form, the activation, the bias
+        assert np.array_equal(results[0][0], want[op]), op
+
+    kw_pad = {} if pad == (0, 0) else {"padding": pad}
+    for kw_f, kw_b in ((kw_pad, kw_pad), (dict(kw_pad, bias=None, activation=None), dict(kw_pad, out=None, activation=None, bias=False))):
+        assert _same(nd.dnn_conv2d_forward(_gpu(x), _gpu(w), **kw_f).cpu().numpy(), want["y"])
+        assert _probes()[:5] == (tm, 0, 0, 0, 0)
+        grads = nd.dnn_conv2d_backward(_gpu(x), _gpu(dy), _gpu(w), **kw_b)
+        assert len(grads) == 2 and _same(grads[0].cpu().numpy(), want["dw"]) and _same(grads[1].cpu().numpy(), want["dx"])

@@ -22,6 +22,7 @@ The closed-form inputs follow the same rule: the emulator on the same input up t
 tests/golden/eig_emulator_recorded.json for the Toeplitz matrix of 500), c n eps above (Toeplitz 1000, Hadamard 1024).
 Each case prints its figures, numpy's fp32 eigh beside them (not a gate), before it asserts."""
 import ctypes as C
+import gc
 import subprocess
 from pathlib import Path
 
@@ -167,6 +168,7 @@ def test_only_the_lower_triangle_is_read(hip, n):
         w3, info3 = _eigvalsh(hip, b)
         assert info3 == 0 and _same(w3, w)
         held.append(_gpu(b))                                       # kept to the end: nothing is freed between the two counts
+        gc.collect()                                               # nor by a collector run that garbage of earlier tests has made due
         live = lib.np_live_allocs()
         with pytest.raises(Error) as e:                            # the NDArray layer does not answer from one triangle
             _nd().eig(held[-1])
