@@ -1,5 +1,5 @@
 /*
- * hip_dnn.c — the device side of NDArrayDNN_Conv2D_Forward / _Backward (hip_dnn.h).  Compiled into a --with-hip tree against the
+ * hip_dnn.c — the device side of NDArrayDNN_Conv2D_Forward / _Backward and of the pooling layers (hip_dnn.h).  Compiled into a --with-hip tree against the
  * reference's headers (-DNUMPOWER_NDARRAY_HEADER='"src/initializers.h"') and into libnumpower_host.so against
  * include/numpower_host.h; it uses only what both declare, with one switch: the reference's arrays take ownership of an
  * emalloc'd shape and its result vectors are emalloc'd, the host library copies shapes and hands out malloc'd vectors.
@@ -257,5 +257,125 @@ NDArray **NPH_Conv2D_LayerBackward(NDArray *x, NDArray *out, NDArray *dy, NDArra
                                    const int dilation[2], char activation, int use_bias) {
     const nph_geometry g = geometry_of(stride, padding, dilation);
     return backward(x, out, dy, filters, &g, activation_of(activation), use_bias, 3);
+}
+
+/* ---- pooling (hip_dnn.h): N.C planes through np_pool2d_forward / np_pool2d_backward ---- */
+
+typedef struct { size_t planes, H, W, kh, kw, ph, pw, sh, sw, oh, ow; int mode; } nph_pool;
+
+/* 'm', 'a', 'v' -> np_pool_mode, -1 for anything else */
+static int pool_mode_of(char mode) {
+    switch (mode) {
+    case 'm': return NP_POOL_MAX;
+    case 'a': return NP_POOL_AVG;
+    case 'v': return NP_POOL_AVG_VALID;
+    default: return -1;
+    }
+}
+
+/* the checks both directions share, in the order of hip_dnn.h; dy == NULL: forward.  0 after a raised error */
+static int pool_of(NDArray *x, NDArray *dy, const int kernel[2], const int stride[2], const int padding[2], char mode, nph_pool *p) {
+    p->mode = pool_mode_of(mode);
+    if (p->mode < 0) {
+        np_ext_throw(NPH_POOL_MSG_MODE);
+        return 0;
+    }
+    if (NDArray_NDIM(x) != 4 || (dy != NULL && NDArray_NDIM(dy) != 4)) {
+        np_ext_throw(NPH_POOL_MSG_NDIM);
+        return 0;
+    }
+    if (kernel == NULL || kernel[0] < 1 || kernel[1] < 1) {
+        np_ext_throw(NPH_POOL_MSG_WINDOW);
+        return 0;
+    }
+    const int sh = stride != NULL ? stride[0] : kernel[0], sw = stride != NULL ? stride[1] : kernel[1];
+    const int ph = padding != NULL ? padding[0] : 0, pw = padding != NULL ? padding[1] : 0;
+    if (sh < 1 || sw < 1) {
+        np_ext_throw(NPH_POOL_MSG_STRIDE);
+        return 0;
+    }
+    if (ph < 0 || pw < 0 || ph > kernel[0] / 2 || pw > kernel[1] / 2) {
+        np_ext_throw(NPH_POOL_MSG_PADDING);
+        return 0;
+    }
+    const int *xs = NDArray_SHAPE(x);
+    if (kernel[0] > xs[2] + 2LL * ph || kernel[1] > xs[3] + 2LL * pw) {
+        np_ext_throw(NPH_POOL_MSG_LARGER);
+        return 0;
+    }
+    const long long oh = (xs[2] + 2LL * ph - kernel[0]) / sh + 1, ow = (xs[3] + 2LL * pw - kernel[1]) / sw + 1;
+    if (dy != NULL) {
+        const int *ys = NDArray_SHAPE(dy);
+        if (ys[0] != xs[0] || ys[1] != xs[1] || ys[2] != oh || ys[3] != ow) {
+            np_ext_throw(NPH_POOL_MSG_GRADIENT);
+            return 0;
+        }
+        if (NDArray_DEVICE(dy) != NDArray_DEVICE(x)) {
+            np_ext_throw(NPH_POOL_MSG_DEVICE);
+            return 0;
+        }
+    }
+    if (NDArray_DEVICE(x) != NDARRAY_DEVICE_GPU) {
+        np_ext_throw(NPH_POOL_MSG_CPU);
+        return 0;
+    }
+    if (xs[0] < 1 || xs[1] < 1 || xs[2] < 1 || xs[3] < 1) {
+        np_ext_throw("dnn_pool2d: an operand has no elements");
+        return 0;
+    }
+    p->planes = (size_t) xs[0] * (size_t) xs[1], p->H = (size_t) xs[2], p->W = (size_t) xs[3];
+    p->kh = (size_t) kernel[0], p->kw = (size_t) kernel[1], p->ph = (size_t) ph, p->pw = (size_t) pw, p->sh = (size_t) sh, p->sw = (size_t) sw;
+    p->oh = (size_t) oh, p->ow = (size_t) ow;
+    return 1;
+}
+
+/* a pooling as the np_pool2d_* calls take it */
+#define NPH_POOL_ARGS(p) (p).planes, (p).H, (p).W, (p).kh, (p).kw, (p).ph, (p).pw, (p).sh, (p).sw
+
+NDArray *NPH_Pool2D_Forward(NDArray *x, const int kernel[2], const int stride[2], const int padding[2], char mode) {
+    nph_pool p;
+    if (x == NULL || !pool_of(x, NULL, kernel, stride, padding, mode, &p)) return NULL;
+    const int *xs = NDArray_SHAPE(x);
+    const size_t dims[4] = {(size_t) xs[0], (size_t) xs[1], p.oh, p.ow};
+    NDArray *rtn = empty_on_gpu(4, dims);
+    if (rtn == NULL) return NULL;
+    if (np_pool2d_forward(NDArray_FDATA(x), NPH_POOL_ARGS(p), p.mode, NDArray_FDATA(rtn), NULL) != NP_OK) {
+        np_ext_throw_last();
+        NDArray_FREE(rtn);
+        return NULL;
+    }
+    return rtn;
+}
+
+NDArray *NPH_Pool2D_Backward(NDArray *x, NDArray *dy, const int kernel[2], const int stride[2], const int padding[2], char mode) {
+    nph_pool p;
+    if (x == NULL || dy == NULL || !pool_of(x, dy, kernel, stride, padding, mode, &p)) return NULL;
+    const int *xs = NDArray_SHAPE(x);
+    const size_t dims[4] = {(size_t) xs[0], (size_t) xs[1], p.H, p.W};
+    NDArray *dx = empty_on_gpu(4, dims);
+    if (dx == NULL) return NULL;
+    const size_t numel_y = p.planes * p.oh * p.ow;
+    void *again = NULL;   /* pool scratch, max only: the forward pass again, y in the first half and idx in the second */
+    int ok = 1;
+    if (p.mode == NP_POOL_MAX && np_malloc(&again, numel_y * (sizeof(float) + sizeof(int32_t))) != NP_OK) {
+        np_ext_throw_last();
+        again = NULL;
+        ok = 0;
+    }
+    int32_t *idx = again != NULL ? (int32_t *) ((float *) again + numel_y) : NULL;
+    if (ok && p.mode == NP_POOL_MAX && np_pool2d_forward(NDArray_FDATA(x), NPH_POOL_ARGS(p), p.mode, (float *) again, idx) != NP_OK) {
+        np_ext_throw_last();
+        ok = 0;
+    }
+    if (ok && np_pool2d_backward(NDArray_FDATA(dy), idx, NPH_POOL_ARGS(p), p.mode, NDArray_FDATA(dx)) != NP_OK) {
+        np_ext_throw_last();
+        ok = 0;
+    }
+    if (again != NULL) np_free(again);   /* released on every path; the pool is stream-ordered: safe right behind the launches that read it */
+    if (!ok) {
+        NDArray_FREE(dx);
+        return NULL;
+    }
+    return dx;
 }
 

@@ -95,6 +95,31 @@ struct NDArray *NPH_Conv2D_LayerForward(struct NDArray *x, struct NDArray *filte
 struct NDArray **NPH_Conv2D_LayerBackward(struct NDArray *x, struct NDArray *out, struct NDArray *dy, struct NDArray *filters, const int stride[2],
                                           const int padding[2], const int dilation[2], char activation, int use_bias);
 
+/* ---- pooling: max and average pool2d (np_pool2d_forward / np_pool2d_backward of include/np_hip.h) ----
+ * The reference has no pooling, so tools/apply_with_hip.py inserts nothing for these two; they are what a binding with a pooling
+ * method calls.  x is (N, C, H, W) and is pooled as N.C planes.  kernel is (kh, kw); stride is (sh, sw), NULL meaning the window;
+ * padding is (ph, pw), NULL meaning 0, with 2 ph <= kh and 2 pw <= kw.  mode: 'm' max, 'a' average with divisor kh.kw (padding
+ * counts), 'v' average over the real cells.  No dilation, no ceil mode.  y (N, C, oh, ow), oh = floor((H + 2 ph - kh) / sh) + 1.
+ * The backward pass keeps no state between calls: it takes the layer's input x, as the convolution's does.  For max it runs the
+ * forward kernel again, y and idx both going to ONE block of pool scratch (the C ABI has no index-only call; y is a quarter of x
+ * or less for a stride of 2), then gathers; the scratch is released on every path.  For the average modes x supplies the shape
+ * only and is not read.
+ * The messages, checked in this order (the gradient's by NPH_Pool2D_Backward alone): */
+#define NPH_POOL_MSG_MODE "dnn_pool2d: unknown mode: 'm' (max), 'a' (average, padding counts), 'v' (average over the real cells)"
+#define NPH_POOL_MSG_NDIM "dnn_pool2d: the input must be 4-dimensional (N, C, H, W), and so must the gradient"
+#define NPH_POOL_MSG_WINDOW "dnn_pool2d: the window must be at least 1 along both axes"
+#define NPH_POOL_MSG_STRIDE "dnn_pool2d: the stride must be at least 1 along both axes"
+#define NPH_POOL_MSG_PADDING "dnn_pool2d: the padding must be at least 0 and at most half the window (2 ph <= kh and 2 pw <= kw)"
+#define NPH_POOL_MSG_LARGER "dnn_pool2d: the window must not be larger than the padded input (H + 2 ph, W + 2 pw)"
+#define NPH_POOL_MSG_GRADIENT "dnn_pool2d_backward: the gradient must have the shape of the forward result (N, C, (H + 2 ph - kh) / sh + 1, (W + 2 pw - kw) / sw + 1)"
+#define NPH_POOL_MSG_DEVICE "dnn_pool2d: the operands must be on the same device"
+#define NPH_POOL_MSG_CPU "dnn_pool2d: operands are on the CPU; numpower_amd only computes on the GPU (call ->gpu() first)"
+
+/* y (N, C, oh, ow), a new GPU array */
+struct NDArray *NPH_Pool2D_Forward(struct NDArray *x, const int kernel[2], const int stride[2], const int padding[2], char mode);
+/* dx (N, C, H, W), a new GPU array; dy: the gradient of the forward result, of its shape.  Cells that no window covers get +0 */
+struct NDArray *NPH_Pool2D_Backward(struct NDArray *x, struct NDArray *dy, const int kernel[2], const int stride[2], const int padding[2], char mode);
+
 #ifdef __cplusplus
 }
 #endif

@@ -667,6 +667,40 @@ int np_conv2d_forward_act(const float *x, const float *w, const float *bias, siz
                           size_t kh, size_t kw, size_t ph, size_t pw, size_t sh, size_t sw, size_t dh, size_t dw, int act, float *y);
 int np_conv2d_backward_act(const float *y, const float *dy, size_t N, size_t F, size_t P, int act, float *dz, float *db);
 
+/* ---- pooling layers: max and average pool2d (np_pool.hip; DESIGN.md "dnn_pool2d") ------------
+ * x is (planes, H, W) row-major fp32, contiguous, planes = N.C.  The window is (kh, kw), the stride (sh, sw) >= 1 and the
+ * zero-width padding (ph, pw) satisfies 2 ph <= kh and 2 pw <= kw, so every window holds at least one real cell.
+ * Out of scope: no dilation and no ceil mode.
+ *   oh = floor((H + 2 ph - kh) / sh) + 1, ow = floor((W + 2 pw - kw) / sw) + 1
+ * Window (i, j) covers rows i.sh - ph ... i.sh - ph + kh - 1 clipped to [0, H) and columns likewise: its real cells.
+ *   NP_POOL_MAX        the real cells are scanned in row-major order from best = -Inf, idx = the first real cell; a cell is
+ *                      taken when v > best || v != v.  So the first of equal maxima wins, -0.0 and +0.0 are equal, a NaN in
+ *                      the window gives NaN and the index is that of the last NaN.  Padding is never a candidate.
+ *                      idx[plane, i, j] = u.W + v is an int32 within the plane; writing idx is optional (NULL).
+ *   NP_POOL_AVG        one chain of plain fp32 adds from +0.0f over the real cells in row-major order, then one correctly
+ *                      rounded fp32 division by (float) divisor, divisor = kh.kw: padding counts.  No multiplication by a
+ *                      reciprocal.
+ *   NP_POOL_AVG_VALID  the same with divisor = the number of real cells.
+ * Backward: dx[plane, u, v] is a gather, never a scatter.  The lane that owns (u, v) walks the windows (i, j) that cover it with
+ * i ascending, then j ascending, and adds its terms from +0.0f with plain fp32 adds.  The max term is dy[i,j] where
+ * idx[i,j] == u.W + v; the average term is dy[i,j] / (float) divisor(i,j), rounded on its own before the add.  Cells that no
+ * window covers (stride > window, or the floor remainder) get +0.0f.  No float atomics; results are bit-identical from run to
+ * run, and a plane's result does not depend on how many planes are in the call.
+ * NaN reach: a NaN in x reaches exactly the outputs whose window holds it; a NaN in dy[i,j] reaches exactly the dx cells that
+ * term is added to.
+ * y, idx and dx may not overlap an input.  The calls run on the library stream and need no scratch; np_pool2d_shape needs no
+ * device.
+ * Convention as above: pointers are checked first, then the shape, then work begins.  NP_ERR_INVALID before any device work: a
+ * null pointer, idx == NULL for a max backward included (idx is ignored by the average modes); a zero extent, window or stride;
+ * an unknown mode; 2 ph > kh or 2 pw > kw; kh > H + 2 ph or kw > W + 2 pw; kh.kw at 2^24 or more; H.W, numel(x), numel(y), a
+ * stride, H + 2 ph or W + 2 pw at 2^31 or more: refused, never truncated. */
+typedef enum np_pool_mode { NP_POOL_MAX = 0, NP_POOL_AVG = 1, NP_POOL_AVG_VALID = 2 } np_pool_mode;
+int np_pool2d_shape(size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw, size_t sh, size_t sw, size_t *oh, size_t *ow);
+int np_pool2d_forward(const float *x, size_t planes, size_t H, size_t W, size_t kh, size_t kw, size_t ph, size_t pw,
+                      size_t sh, size_t sw, int mode, float *y, int32_t *idx);   /* idx: NULL, or planes.oh.ow ints (max only) */
+int np_pool2d_backward(const float *dy, const int32_t *idx, size_t planes, size_t H, size_t W, size_t kh, size_t kw,
+                       size_t ph, size_t pw, size_t sh, size_t sw, int mode, float *dx);   /* idx needed for max, ignored otherwise */
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

@@ -153,6 +153,13 @@ int np_debug_dnn_last_form(int *host_form);
  * plain kernels, the data gradient included) and the number of slices S of the last np_conv2d_backward_act call that produced
  * a db (1: written directly, no fold kernel).  (0, 0, 0) before any launch. */
 int np_debug_dnn_last_epilogue(int *act, int *has_bias, int *bias_slices);
+/* tests / tools: the kernel forms the last np_pool2d_forward and the last np_pool2d_backward of the process launched: forward
+ * 1 = direct (one lane per output, planes of more than 8192 cells), 2 = staged (whole planes through LDS, H.W <= 8192);
+ * backward 1 = gather (one lane per dx cell).  (0, 0) before any launch; NP_ERR_INVALID on a null pointer.  Plain process globals. */
+int np_debug_pool_last_path(int *forward_form, int *backward_form);
+/* testing / A-B: form = 1 sends every shape through the direct forward form, form = 0 (the default) chooses by the extents.
+ * The two forms return the same bits.  Process-global. */
+int np_debug_pool_forward_form(int form);
 /* tests / tools: which kernel families the last np_reduce_axis or np_reduce_all(_dev) call of the process launched, the calls it
  * makes on its own partials included: the OR of the NP_REDUCE_PATH_ bits below (0 = none yet).  A plain process global, cleared
  * at the top of those entry points; calls the library makes itself (split-K GEMM folds, chain partials) overwrite it too. */

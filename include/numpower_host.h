@@ -406,6 +406,16 @@ NDArray *NDArrayDNN_Conv2D_LayerForward(NDArray *x, NDArray *filters, NDArray *b
                                         char activation);
 NDArray **NDArrayDNN_Conv2D_LayerBackward(NDArray *input, NDArray *out, NDArray *dy, NDArray *filters, const int *stride, const int *padding,
                                           const int *dilation, char activation, int use_bias);
+/* Pooling (host/numpower_dnn.cpp; the reference has none): y (N, C, oh, ow) of a GPU input x (N, C, H, W), pooled as N.C planes.
+ * kernel (kh, kw); stride (sh, sw), NULL meaning the window; padding (ph, pw), NULL meaning 0, with 2 ph <= kh and 2 pw <= kw;
+ * mode 'm' max (the first of equal maxima, a NaN wins), 'a' average with divisor kh.kw (padding counts), 'v' average over the real
+ * cells.  oh = floor((H + 2 ph - kh) / sh) + 1; no dilation, no ceil mode.  _Backward takes the layer's input x and dy, the
+ * gradient of the result, and returns dx (N, C, H, W): a gather in a fixed order, no float atomics; cells no window covers get +0.
+ * Views are made contiguous; NPH_Pool2D_Forward / _Backward over np_pool2d_forward / _backward do the work.  Errors (ext/hip_dnn.h,
+ * NPH_POOL_MSG_*): an unknown mode, operands that are not 4-dimensional, a window, stride or padding out of range, a window larger
+ * than the padded input, a gradient of the wrong shape, operands on different devices, and CPU operands. */
+NDArray *NDArrayDNN_Pool2D_Forward(NDArray *x, const int *kernel, const int *stride, const int *padding, char mode);
+NDArray *NDArrayDNN_Pool2D_Backward(NDArray *x, NDArray *dy, const int *kernel, const int *stride, const int *padding, char mode);
 
 #ifdef __cplusplus
 }

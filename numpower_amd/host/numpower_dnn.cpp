@@ -5,6 +5,8 @@
 // functions; here strided views of the operands are first made contiguous (numpower_host_contiguous).  kernel_size, activation
 // and use_bias are the reference's parameters and are ignored, as the reference ignores the last two on both of its paths.
 // The host library has no CPU convolution: CPU operands get the glue's message.
+// NDArrayDNN_Pool2D_Forward / _Backward at the end are the pooling layers (np_pool2d_forward / _backward), which
+// the reference does not have; the same glue file does their work.
 // A translation unit of its own: the sanitizer build of numpower_host.cpp (tests/test_host_sanitizers_cpu.py) links
 // against a null device that has no convolution.
 #include <optional>
@@ -82,6 +84,21 @@ NDArray **NDArrayDNN_Conv2D_LayerBackward(NDArray *input, NDArray *out, NDArray 
     return on_contiguous([=](NDArray *cx, NDArray *cy, NDArray *cf, NDArray *co) {
         return NPH_Conv2D_LayerBackward(cx, co, cy, cf, stride, padding, dilation, activation, use_bias);
     }, input, dy, filters, out);
+}
+
+// Pooling (np_pool2d_forward / _backward): x (N, C, H, W); kernel (kh, kw); stride nullptr: the window; padding
+// nullptr: 0; mode 'm' max, 'a' average with divisor kh.kw, 'v' average over the real cells.  The reference has no pooling.
+NDArray *NDArrayDNN_Pool2D_Forward(NDArray *x, const int *kernel, const int *stride, const int *padding, char mode) {
+    if (!x) return nullptr;
+    return on_contiguous([=](NDArray *cx, NDArray *, NDArray *, NDArray *) { return NPH_Pool2D_Forward(cx, kernel, stride, padding, mode); }, x,
+                         nullptr);
+}
+
+// dx (N, C, H, W) for dy = the gradient of that result; x is the layer's input (max reads it again, the averages take its shape).
+NDArray *NDArrayDNN_Pool2D_Backward(NDArray *x, NDArray *dy, const int *kernel, const int *stride, const int *padding, char mode) {
+    if (!x || !dy) return nullptr;
+    return on_contiguous([=](NDArray *cx, NDArray *cy, NDArray *, NDArray *) { return NPH_Pool2D_Backward(cx, cy, kernel, stride, padding, mode); }, x,
+                         dy);
 }
 
 }  // extern "C"

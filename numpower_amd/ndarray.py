@@ -159,6 +159,8 @@ def _load_host():
     sig["NDArrayDNN_Conv2D_BackwardEx"] = (C.POINTER(_P), [_P, _P, _P, ip, ip, ip])
     sig["NDArrayDNN_Conv2D_LayerForward"] = (_P, [_P, _P, _P, ip, ip, ip, C.c_char])
     sig["NDArrayDNN_Conv2D_LayerBackward"] = (C.POINTER(_P), [_P, _P, _P, _P, ip, ip, ip, C.c_char, C.c_int])
+    sig["NDArrayDNN_Pool2D_Forward"] = (_P, [_P, ip, ip, ip, C.c_char])
+    sig["NDArrayDNN_Pool2D_Backward"] = (_P, [_P, _P, ip, ip, ip, C.c_char])
     sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
     sig["NDArray_Eig"] = (C.POINTER(_P), [_P])
     sig["NDArray_Qr"] = (C.POINTER(_P), [_P])
@@ -935,6 +937,47 @@ class NDArray:
         out_arrays = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(3 if bias else 2))
         _libc_free(C.cast(rtns, C.c_void_p))
         return out_arrays
+
+    _DNN_POOL_MODES = {"max": b"m", "avg": b"a", "avg_valid": b"v"}
+
+    @staticmethod
+    def _dnn_pool_geometry(kernel_size, stride, padding, mode):
+        """-> (kernel, stride or None, padding, mode's code): C int pairs; stride None means the window"""
+        def pair(v, what):
+            if isinstance(v, (int, np.integer)) and not isinstance(v, bool):
+                return int(v), int(v)
+            if isinstance(v, (tuple, list)) and len(v) == 2 and all(isinstance(e, (int, np.integer)) and not isinstance(e, bool) for e in v):
+                return int(v[0]), int(v[1])
+            raise Error("dnn_pool2d: %s must be an int or a pair of ints" % what)
+
+        if not isinstance(mode, str) or mode not in NDArray._DNN_POOL_MODES:
+            raise Error("dnn_pool2d: mode must be 'max', 'avg' or 'avg_valid', not %r" % (mode,))
+        k, p = pair(kernel_size, "kernel_size"), pair(padding, "padding")
+        s = None if stride is None else pair(stride, "stride")
+        return (C.c_int * 2)(*k), None if s is None else (C.c_int * 2)(*s), (C.c_int * 2)(*p), NDArray._DNN_POOL_MODES[mode]
+
+    @staticmethod
+    def dnn_pool2d_forward(x, kernel_size, stride=None, padding=0, mode="max"):      # the reference has no pooling
+        """y (N, C, oh, ow) of x (N, C, H, W), each (n, c) plane pooled on its own.  kernel_size, stride and
+        padding take an int or a (rows, columns) pair; stride None means the window; 2 . padding <= kernel_size.
+        oh = floor((H + 2 ph - kh) / sh) + 1: no dilation, no ceil mode.  mode 'max': the first of equal maxima, a NaN in the
+        window gives NaN, padding is never a candidate; 'avg': the sum of the real cells / (kh . kw), padding counts; 'avg_valid':
+        / the number of real cells.  One chain of fp32 adds in row-major order and one correctly rounded division."""
+        h = _load_host()
+        k, s, p, code = NDArray._dnn_pool_geometry(kernel_size, stride, padding, mode)
+        a, _ = NDArray._coerce(x)
+        return NDArray._wrap(h.NDArrayDNN_Pool2D_Forward(a._p, k, s, p, code))
+
+    @staticmethod
+    def dnn_pool2d_backward(x, dy, kernel_size, stride=None, padding=0, mode="max"):
+        """dx (N, C, H, W) for dy = the gradient of dnn_pool2d_forward(x, kernel_size, stride, padding, mode).  x is the layer's
+        INPUT: 'max' finds the maxima again (no state is kept between the calls), the averages take its shape only.  A gather in
+        a fixed order, windows by rows then columns: bit-identical from run to run.  Cells that no window covers get 0."""
+        h = _load_host()
+        k, s, p, code = NDArray._dnn_pool_geometry(kernel_size, stride, padding, mode)
+        a, _ = NDArray._coerce(x)
+        g, _ = NDArray._coerce(dy)
+        return NDArray._wrap(h.NDArrayDNN_Pool2D_Backward(a._p, g._p, k, s, p, code))
 
     def copy(self):          # PHP_METHOD copy: NDArray_Copy on the array's own device
         return NDArray._wrap(_load_host().NDArray_Copy(self._p, C.cast(self._p, _P).contents.device))

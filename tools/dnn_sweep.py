@@ -22,10 +22,18 @@ np_conv2d_backward_act (relu, dz and db) against an elementwise multiply on arra
 12 B / element: two reads and a write), with the ratio and the fraction of 8 TB/s; and the same pair at one large case of about
 10^8 elements.  Writes profiles/dnn/conv2d_act_sweep.log.
 --forward-only times the forward pass alone, one line per layer: for alternating two builds of the library in one session.
+--pool is the leg of the pooling layers (np_pool.hip: np_pool2d_forward, np_pool2d_backward), which are streaming kernels: per
+layer (POOL_LAYERS) and mode, in one child, the forward pass (y alone), for max the forward pass that also writes idx, the gather
+of the backward pass, and for max the backward pass as the glue runs it (the forward pass again into scratch, then the gather).
+Each operation alternates, round by round in one session, with the library's float4 device copy (np_memcpy_d2d) moving the SAME
+number of bytes, read plus written: 4 (numel(x) + numel(y)), plus 4 numel(y) where an idx is written or read.  Reported: ms, achieved
+TB/s and the ratio copy / pool (1.00 = the copy's rate, the platform ceiling for streaming kernels), medians of the rounds.  The
+operand sets are rotated (--sets) so that together they pass the 256 MiB Infinity Cache.  Writes profiles/dnn/pool2d_sweep.log.
 
 Usage: python tools/dnn_sweep.py [--layers 0,1,...] [--rounds N] [--limit S] [--torch] [--out FILE]
        python tools/dnn_sweep.py --act [--layers ...]         the bias / activation leg
        python tools/dnn_sweep.py --forward-only [--layers ...]
+       python tools/dnn_sweep.py --pool [--layers ...]        the pooling leg
        python tools/dnn_sweep.py --profile LAYER     three calls of each operation and nothing else, for a run under the kernel profiler"""
 import argparse
 import statistics
@@ -48,8 +56,19 @@ LAYERS = [("3x3 64->64 at 56^2, batch 32", (32, 64, 56, 56), (64, 3, 3), (1, 1))
           ("1x1/2 256->512 at 56^2, batch 32", (32, 256, 56, 56), (512, 1, 1), (0, 0), (2, 2, 1, 1)),
           ("3x3 dil 2 128->128 at 28^2 pad 2, batch 32", (32, 128, 28, 28), (128, 3, 3), (2, 2), (1, 1, 2, 2))]
 
+# name, (N, C, H, W), (kh, kw), (sh, sw), (ph, pw), modes
+POOL_LAYERS = [("2x2/2 64 ch at 112^2, batch 32", (32, 64, 112, 112), (2, 2), (2, 2), (0, 0), ("max", "avg")),
+               ("3x3/2 pad 1 64 ch at 112^2, batch 32", (32, 64, 112, 112), (3, 3), (2, 2), (1, 1), ("max", "avg")),
+               ("2x2/2 256 ch at 56^2, batch 32", (32, 256, 56, 56), (2, 2), (2, 2), (0, 0), ("max", "avg")),
+               ("3x3/2 pad 1 256 ch at 56^2, batch 32", (32, 256, 56, 56), (3, 3), (2, 2), (1, 1), ("max", "avg")),
+               ("7x7 global average 2048 ch at 7^2, batch 256", (256, 2048, 7, 7), (7, 7), (7, 7), (0, 0), ("avg",)),
+               ("3x3/1 pad 1 256 ch at 28^2, batch 32", (32, 256, 28, 28), (3, 3), (1, 1), (1, 1), ("max", "avg"))]
+POOL_MODE = {"max": 0, "avg": 1, "avg_valid": 2}
+
 ap = argparse.ArgumentParser()
-ap.add_argument("--layers", default=",".join(str(i) for i in range(len(LAYERS))))
+ap.add_argument("--pool", action="store_true")
+ap.add_argument("--sets", type=int, default=0, help="--pool: operand sets to rotate through (0: enough to pass 256 MiB)")
+ap.add_argument("--layers", default=None)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--limit", type=int, default=120, help="seconds each child process may take")
 ap.add_argument("--torch", action="store_true")
@@ -59,8 +78,11 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--profile", type=int, default=None)
 ap.add_argument("--child", default=None, help="internal: 'layer:<i>' or 'torch'")
 args = ap.parse_args()
+if args.layers is None:
+    args.layers = ",".join(str(i) for i in range(len(POOL_LAYERS if args.pool else LAYERS)))
 if args.out is None:
-    args.out = str(ROOT / "profiles" / "dnn" / ("conv2d_act_sweep.log" if args.act else "conv2d_forward_only.log" if args.forward_only else "conv2d_sweep.log"))
+    args.out = str(ROOT / "profiles" / "dnn" / ("pool2d_sweep.log" if args.pool else "conv2d_act_sweep.log" if args.act else
+                                               "conv2d_forward_only.log" if args.forward_only else "conv2d_sweep.log"))
 LARGE = (256, 128, 3136)                        # (N, F, P) of the large case of --act: 1.03e8 elements
 HBM_TBS = 8.0
 
@@ -251,6 +273,97 @@ def run_act(what, rounds):
     _backward_pair(D, lib, check, median_ms, rounds, LAYERS[i][0], ys[0], ys[1], ys[2] * ys[3])
 
 
+def run_pool(i, rounds, sets):
+    """one pooling layer: every operation alternates with a float4 copy of the same bytes, round by round"""
+    import ctypes as C_
+    import numpy as np
+    D, lib, check, ramp, _ = _setup()
+    from numpower_amd._lib import Timer
+    t = Timer()
+    name, (N, Cc, H, W), (kh, kw), (sh, sw), (ph, pw), modes = POOL_LAYERS[i]
+    planes, oh, ow = N * Cc, (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+    nx, ny = planes * H * W, planes * oh * ow
+    if sets < 1:
+        sets = max(2, -(-(256 << 20) // (4 * nx)) + 1)
+    rng = np.random.default_rng(i)
+    host_x, host_dy = rng.standard_normal(nx).astype(np.float32), rng.standard_normal(ny).astype(np.float32)
+    xs = [D.DeviceArray.from_host(host_x) for _ in range(sets)]
+    cs, cd = [D.DeviceArray((nx + 2 * ny,)) for _ in range(sets)], [D.DeviceArray((nx + 2 * ny,)) for _ in range(sets)]      # the copy's own operands
+    for c in cs:
+        check(lib.np_memset0(c.ptr, 4 * (nx + 2 * ny)))
+    dxs = [D.DeviceArray((nx,)) for _ in range(sets)]
+    dys = [D.DeviceArray.from_host(host_dy) for _ in range(sets)]
+    ys, idxs, scratch = [D.DeviceArray((ny,)) for _ in range(sets)], [D.DeviceArray((ny,)) for _ in range(sets)], D.DeviceArray((2 * ny,))
+    dims = (planes, H, W, kh, kw, ph, pw, sh, sw)
+    ramp()
+    turn = [0]
+
+    def rotating(fn):
+        def call():
+            turn[0] = (turn[0] + 1) % sets
+            fn(turn[0])
+        return call
+
+    def copy_of(total_bytes):
+        half = total_bytes // 2 // 16 * 16        # a copy of B / 2 bytes reads B / 2 and writes B / 2
+        assert half <= 4 * (nx + 2 * ny)
+        return rotating(lambda k: check(lib.np_memcpy_d2d(cd[k].ptr, cs[k].ptr, half)))
+
+    def timed(fn, reps):
+        t.start()
+        for _ in range(reps):
+            fn()
+        t.stop()
+        return t.elapsed_ms() / reps
+
+    for mode in modes:
+        m = POOL_MODE[mode]
+        for k in range(sets):                     # every idx holds its plane's maxima before a gather reads it
+            check(lib.np_pool2d_forward(xs[k].ptr, *dims, 0, ys[k].ptr, idxs[k].ptr))
+        ops = [("forward", rotating(lambda k: check(lib.np_pool2d_forward(xs[k].ptr, *dims, m, ys[k].ptr, None))), 4 * (nx + ny))]
+        if H * W <= 8192:                         # the staged form took it: the direct form on the same layer, through the A-B switch
+
+            def forced_direct(k):
+                check(lib.np_debug_pool_forward_form(1))
+                try:
+                    check(lib.np_pool2d_forward(xs[k].ptr, *dims, m, ys[k].ptr, None))
+                finally:
+                    check(lib.np_debug_pool_forward_form(0))
+
+            ops.append(("forward, direct form forced", rotating(forced_direct), 4 * (nx + ny)))
+        if mode == "max":
+            ops.append(("forward + idx", rotating(lambda k: check(lib.np_pool2d_forward(xs[k].ptr, *dims, m, ys[k].ptr, idxs[k].ptr))), 4 * (nx + 2 * ny)))
+            ops.append(("gather", rotating(lambda k: check(lib.np_pool2d_backward(dys[k].ptr, idxs[k].ptr, *dims, m, dxs[k].ptr))), 4 * (nx + 2 * ny)))
+
+            def layer_backward(k):                # what NPH_Pool2D_Backward launches: y and idx again into scratch, then the gather
+                check(lib.np_pool2d_forward(xs[k].ptr, *dims, m, scratch.ptr, scratch.ptr + 4 * ny))
+                check(lib.np_pool2d_backward(dys[k].ptr, scratch.ptr + 4 * ny, *dims, m, dxs[k].ptr))
+
+            ops.append(("backward (recomputed idx)", rotating(layer_backward), 4 * (nx + 2 * ny) + 4 * (nx + 2 * ny)))
+        else:
+            ops.append(("gather = backward", rotating(lambda k: check(lib.np_pool2d_backward(dys[k].ptr, None, *dims, m, dxs[k].ptr))), 4 * (nx + ny)))
+        for label, fn, nbytes in ops:
+            copy = copy_of(nbytes)
+            for f in (fn, copy):                  # warm
+                for _ in range(3):
+                    f()
+            D.sync()
+            t0 = time.time()
+            fn()
+            D.sync()
+            reps = max(5, min(200, int(0.05 / max(time.time() - t0, 1e-5))))
+            pool_ms, copy_ms = [], []
+            for _ in range(rounds):               # alternating in one session
+                pool_ms.append(timed(fn, reps))
+                copy_ms.append(timed(copy, reps))
+            pm, cm = statistics.median(pool_ms), statistics.median(copy_ms)
+            form = [C_.c_int(), C_.c_int()]
+            check(lib.np_debug_pool_last_path(C_.byref(form[0]), C_.byref(form[1])))
+            print("%-44s %-9s %-28s forms %d %d %7.1f MB %9.4f ms %5.2f TB/s   copy %9.4f ms %5.2f TB/s   copy / pool %5.2f   (min %5.2f max %5.2f)"
+                  % (name, mode, label, form[0].value, form[1].value, nbytes * 1e-6, pm, nbytes / pm * 1e-9, cm, nbytes / cm * 1e-9, cm / pm,
+                     min(c / p for c, p in zip(copy_ms, pool_ms)), max(c / p for c, p in zip(copy_ms, pool_ms))), flush=True)
+
+
 def run_torch(layers, rounds):
     import torch
     if not torch.cuda.is_available():
@@ -293,6 +406,8 @@ if args.child:
         run_torch([int(s) for s in args.layers.split(",")], args.rounds)
     elif args.child.startswith("act:"):
         run_act(args.child.split(":")[1], args.rounds)
+    elif args.child.startswith("pool:"):
+        run_pool(int(args.child.split(":")[1]), args.rounds, args.sets)
     elif args.child.startswith("fwd:"):
         run_forward_only(int(args.child.split(":")[1]), args.rounds)
     else:
@@ -310,7 +425,7 @@ def say(line=""):
 def child(what):
     """-> True when the child ended well; its output joins the log either way"""
     try:
-        proc = subprocess.run([sys.executable, __file__, "--child", what, "--layers", args.layers, "--rounds", str(args.rounds)],
+        proc = subprocess.run([sys.executable, __file__, "--child", what, "--layers", args.layers, "--rounds", str(args.rounds), "--sets", str(args.sets)],
                               capture_output=True, text=True, timeout=args.limit)
     except subprocess.TimeoutExpired:
         say("%s: no result inside %d s" % (what, args.limit))
@@ -322,8 +437,11 @@ def child(what):
     return proc.returncode == 0
 
 
-kind = "act" if args.act else "fwd" if args.forward_only else "layer"
-if args.act:
+kind = "pool" if args.pool else "act" if args.act else "fwd" if args.forward_only else "layer"
+if args.pool:
+    say("np_pool2d_forward / np_pool2d_backward (forms of the last forward and backward launch: forward 1 direct, 2 staged; backward 1 gather) against np_memcpy_d2d (the float4 copy) of the same "
+        "bytes read + written, alternating round by round; fp32, ms per call, medians of %d rounds" % args.rounds)
+elif args.act:
     say("np_conv2d_forward_act (a bias and relu) against np_conv2d_forward(_ex), np_conv2d_backward_act (relu, dz and db) against np_binary "
         "multiply on the same element count; fp32, ms per call, median of %d rounds" % args.rounds)
 elif args.forward_only:
