@@ -93,6 +93,10 @@ int np_sgemm_debug_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, 
  * (1e300 = does not apply).  tests/test_abi_and_host_cpu.py pins the choices that matter (no reference counterpart:
  * linalg.c:75-79 hands every product to cblas / cuBLAS). */
 int np_sgemm_debug_plan(size_t M, size_t N, size_t K, size_t batch, int cus, double *out);
+/* debug: the same decision for ONE dense M x N x K product whose rows are not float4-loadable (K % 4 or N % 4 != 0, or operands off
+ * 16 bytes).  out[5]: cfg, tail_rows, S of the tiled plan of the product as it is; stream-K taken instead (0/1); padded copies and
+ * the aligned kernel taken instead of either (0/1).  Host arithmetic, like np_sgemm_debug_plan. */
+int np_sgemm_debug_plan_unaligned(size_t M, size_t N, size_t K, int cus, double *out);
 /* A/B switches of single kernels of np_elementwise.hip / np_fused_chain.hip, same bits either way; a plain setter, 0 = defaults.  7000: chains on
  * the interpreter only (no compiled chain); 7001: chains that name an array twice as every other chain (compiled or streaming), 7002: never
  * looked for; 7004: compiled first-axis chains with 4 rows in flight; 8000: a long row operand in the plain work order; 8100 / 8101: the 2-D
@@ -224,6 +228,55 @@ int np_debug_chain_reduce_last_path(unsigned *host_mask);
 #define NP_SGEMM_PATH_LANES(L) ((unsigned)(__builtin_ctz((unsigned)(L)) + 1) << 20)   /* L = 1, 2, 4 .. 64 */
 #define NP_SGEMM_PATH_MV(MV) ((unsigned)(__builtin_ctz((unsigned)(MV)) + 1) << 24)    /* MV = 1, 2, 4, 8, 16 */
 int np_sgemm_debug_last_path(unsigned *host_mask);
+/* Everything behind NP_SGEMM_PATH_TILED, launch by launch: one record of NP_SGEMM_LAUNCH_WORDS unsigned words per kernel launch
+ * the last outermost product call (the entry points above, and np_sgemm_debug_sub_ld) made behind launch_sgemm_ld, in launch
+ * order, cleared where the mask is cleared.  The first NP_SGEMM_LAUNCH_KEPT launches are kept; *host_count is the number of
+ * launches made, exact also when it is larger than that or than `capacity` (records).  min(count, kept, capacity) records are
+ * written.  The fold of a split-K plan is np_reduce_axis's launch and shows as NP_SGEMM_PATH_FOLD in the mask, not here.  Host
+ * stores at the launch sites, like the mask: no device work, no synchronisation; one thread at a time.  A record:
+ *   word 0  NP_SGEMM_LAUNCH_FAMILY: the kernel
+ *   word 1  NP_SGEMM_LAUNCH_TILE: bm | bn << 16, the tile of C one workgroup owns (0 for pad_copy_kernel)
+ *   word 2  NP_SGEMM_LAUNCH_BK: the K-tile depth bk | (shape + 1) << 16, shape = the index np_sgemm_set_variant names for
+ *           sgemm_dmas_kernel (0 .. 5: the instantiated DmasShape, 5 = 64 x 64 on eight waves) and sgemm_kq_kernel (0 .. 6); 0 in
+ *           the high half for the kernels without one
+ *   word 3  NP_SGEMM_LAUNCH_FLAGS: the template arguments and launch forms, NP_SGEMM_LAUNCH_F_ bits
+ *   word 4  NP_SGEMM_LAUNCH_S: sgemm_dmas_kernel: the S K-chunks per tile after the launcher's clamp; sgemm_kq_kernel launched
+ *           chunk-major: GemmArgs::k_chunks, the K-chunks inside grid.x; pad_copy_kernel: the row length of the padded copy; else 1
+ *           (the K-chunks of a split-K plan run as the batch: grid.z)
+ *   word 5  NP_SGEMM_LAUNCH_GRID_X, word 6 NP_SGEMM_LAUNCH_GRID_Z: gridDim.x and gridDim.z (gridDim.y is 1 everywhere)
+ *   word 7  NP_SGEMM_LAUNCH_K_LAST: the length of the remainder chunk that rides as the last batch entry (0 = none) */
+#define NP_SGEMM_LAUNCH_WORDS 8u
+#define NP_SGEMM_LAUNCH_KEPT 16u
+#define NP_SGEMM_LAUNCH_FAMILY 0
+#define NP_SGEMM_LAUNCH_TILE 1
+#define NP_SGEMM_LAUNCH_BK 2
+#define NP_SGEMM_LAUNCH_FLAGS 3
+#define NP_SGEMM_LAUNCH_S 4
+#define NP_SGEMM_LAUNCH_GRID_X 5
+#define NP_SGEMM_LAUNCH_GRID_Z 6
+#define NP_SGEMM_LAUNCH_K_LAST 7
+#define NP_SGEMM_KERNEL_TILE 1u      /* sgemm_kernel<BM, BN, BK, MINW, VEC, EDGE> (the register-staged tiles) */
+#define NP_SGEMM_KERNEL_PIPE 2u      /* sgemm_pipe_kernel<128, 128, VEC, EDGE, MODE>; NP_SGEMM_LAUNCH_F_PIPE_MODE1 for MODE = 1 */
+#define NP_SGEMM_KERNEL_DMA 3u       /* sgemm_dma_kernel<EDGE, KTAIL, PRIO, BUF> (256 x 128) */
+#define NP_SGEMM_KERNEL_STREAMK 4u   /* sgemm_streamk_kernel<EDGE, KTAIL, PRIO, BUF>; grid.x = the G workgroups */
+#define NP_SGEMM_KERNEL_DMAS 5u      /* sgemm_dmas_kernel<DmasShape, EDGE, KTAIL> */
+#define NP_SGEMM_KERNEL_KQ 6u        /* sgemm_kq_kernel<TM, TN, STAGES, EDGE, VEC> */
+#define NP_SGEMM_KERNEL_PAD_COPY 7u  /* pad_copy_kernel */
+#define NP_SGEMM_KERNEL_TILE_SUB 8u  /* sgemm_kernel<128, 128, 16, 2, VEC, EDGE, SUB = true> (np::sgemm_sub_ld) */
+#define NP_SGEMM_LAUNCH_F_VEC 0x001u          /* float4 loads of A and B */
+#define NP_SGEMM_LAUNCH_F_EDGE 0x002u         /* the guarded M / N (register-staged tiles: and K) edges */
+#define NP_SGEMM_LAUNCH_F_KTAIL 0x004u        /* the last K-tile's fix-up */
+#define NP_SGEMM_LAUNCH_F_PRIO 0x008u         /* priority alternation */
+#define NP_SGEMM_LAUNCH_F_BUF 0x010u          /* the buffer-addressed K loop */
+#define NP_SGEMM_LAUNCH_F_SUB 0x020u          /* C -= A . B */
+#define NP_SGEMM_LAUNCH_F_SWIZZLE 0x040u      /* GemmArgs::swizzle != 0: tiles walked in XCD-aware bands */
+#define NP_SGEMM_LAUNCH_F_CHUNK_MAJOR 0x080u  /* sgemm_kq_kernel: GemmArgs::k_chunks != 0, the K-chunks folded into grid.x */
+#define NP_SGEMM_LAUNCH_F_PIPE_MODE1 0x100u   /* sgemm_pipe_kernel<.., MODE = 1> */
+int np_sgemm_debug_last_launches(unsigned *host_records, unsigned capacity, unsigned *host_count);
+/* tests: C (M x N, rows ldc apart) -= A (M x K, rows lda apart) . B (K x N, rows ldb apart) — np::sgemm_sub_ld, the trailing update of
+ * the LU and the Cholesky, on its own: one launch of the subtracting 128 x 128 tile kernel on the library stream.  Checked like
+ * np_sgemm_debug_ld; clears and fills the two probes above like a product call (the mask reads 0: no np_sgemm path ran). */
+int np_sgemm_debug_sub_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, const float *B, size_t ldb, float *C, size_t ldc);
 
 #ifdef __cplusplus
 }

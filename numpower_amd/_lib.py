@@ -169,7 +169,10 @@ PROTOTYPES = {
     "np_sgemm_debug_kloop_stats": (C.c_int, [C.POINTER(C.c_ulonglong)]),
     "np_sgemm_debug_ld": (C.c_int, [C.c_size_t] * 3 + [_f32p, C.c_size_t, _f32p, C.c_size_t, _f32p, C.c_size_t]),
     "np_sgemm_debug_plan": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
+    "np_sgemm_debug_plan_unaligned": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
     "np_sgemm_debug_last_path": (C.c_int, [C.POINTER(C.c_uint)]),
+    "np_sgemm_debug_last_launches": (C.c_int, [C.POINTER(C.c_uint), C.c_uint, C.POINTER(C.c_uint)]),
+    "np_sgemm_debug_sub_ld": (C.c_int, [C.c_size_t] * 3 + [_f32p, C.c_size_t, _f32p, C.c_size_t, _f32p, C.c_size_t]),
     "np_elementwise_set_variant": (C.c_int, [C.c_int]),
     "np_layout_set_variant": (C.c_int, [C.c_int]),
     "np_reduce_set_variant": (C.c_int, [C.c_int]),

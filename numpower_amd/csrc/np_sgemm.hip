@@ -2458,8 +2458,32 @@ int g_variant = 0;
 unsigned g_last_path = 0;
 thread_local int g_path_depth = 0;
 inline void note_path(unsigned bits) { g_last_path |= bits; }
+// np_sgemm_debug_last_launches: one record (np_hip_debug.h: NP_SGEMM_LAUNCH_*) per kernel launch behind launch_sgemm_ld, in
+// launch order; the first NP_SGEMM_LAUNCH_KEPT are kept, the count runs on.  Host stores at the launch sites, like note_path.
+unsigned g_launches[NP_SGEMM_LAUNCH_KEPT][NP_SGEMM_LAUNCH_WORDS];
+unsigned g_launch_count = 0;
+inline void note_launch(unsigned family, unsigned bm, unsigned bn, unsigned bk, int shape, unsigned flags, unsigned S, dim3 grid,
+                        unsigned K_last) {
+    const unsigned at = __atomic_fetch_add(&g_launch_count, 1u, __ATOMIC_RELAXED);   // (concurrent callers: never an index past the array)
+    if (at < NP_SGEMM_LAUNCH_KEPT) {
+        unsigned *r = g_launches[at];
+        r[NP_SGEMM_LAUNCH_FAMILY] = family;
+        r[NP_SGEMM_LAUNCH_TILE] = bm | bn << 16;
+        r[NP_SGEMM_LAUNCH_BK] = bk | (unsigned)(shape + 1) << 16;
+        r[NP_SGEMM_LAUNCH_FLAGS] = flags;
+        r[NP_SGEMM_LAUNCH_S] = S;
+        r[NP_SGEMM_LAUNCH_GRID_X] = grid.x;
+        r[NP_SGEMM_LAUNCH_GRID_Z] = grid.z;
+        r[NP_SGEMM_LAUNCH_K_LAST] = K_last;
+    }
+}
+inline unsigned launch_flags(bool vec, bool edge, bool ktail, bool prio, bool buf, const GemmArgs &g) {
+    return (vec ? NP_SGEMM_LAUNCH_F_VEC : 0u) | (edge ? NP_SGEMM_LAUNCH_F_EDGE : 0u) | (ktail ? NP_SGEMM_LAUNCH_F_KTAIL : 0u) |
+           (prio ? NP_SGEMM_LAUNCH_F_PRIO : 0u) | (buf ? NP_SGEMM_LAUNCH_F_BUF : 0u) | (g.swizzle ? NP_SGEMM_LAUNCH_F_SWIZZLE : 0u) |
+           (g.k_chunks ? NP_SGEMM_LAUNCH_F_CHUNK_MAJOR : 0u);
+}
 struct PathScope {
-    PathScope() { if (g_path_depth++ == 0) g_last_path = 0; }
+    PathScope() { if (g_path_depth++ == 0) { g_last_path = 0; g_launch_count = 0; } }
     ~PathScope() { --g_path_depth; }
 };
 // sgemm_dma_kernel<.., PRIO>: K-tiles per priority phase; np_sgemm_set_variant(-(100 + p)) sets it (p = 0: off).
@@ -2528,6 +2552,7 @@ int launch_sgemm_tile(GemmArgs g, unsigned batch, bool vec) {
     else
         sgemm_kernel<BM, BN, BK, MINW, false, true><<<grid, 256, 0, s>>>(g);
     NP_LAUNCH_CHECK("sgemm_kernel");
+    note_launch(NP_SGEMM_KERNEL_TILE, BM, BN, BK, -1, launch_flags(vec, edge || !vec, false, false, false, g), 1, grid, g.K_last);
     return NP_OK;
 }
 
@@ -2545,6 +2570,8 @@ int launch_sgemm_pipe(GemmArgs g, unsigned batch, bool vec) {
     else
         sgemm_pipe_kernel<BM, BN, false, true, MODE><<<grid, 256, 0, s>>>(g);
     NP_LAUNCH_CHECK("sgemm_pipe_kernel");
+    note_launch(NP_SGEMM_KERNEL_PIPE, BM, BN, 16, -1,
+                launch_flags(vec, edge || !vec, false, false, false, g) | (MODE == 1 ? NP_SGEMM_LAUNCH_F_PIPE_MODE1 : 0u), 1, grid, g.K_last);
     return NP_OK;
 }
 
@@ -2683,6 +2710,7 @@ int launch_cfg(int cfg, GemmArgs g, unsigned batch, bool vec, bool whole = false
         else
             sgemm_dma_kernel<false, false><<<grid, 256, 0, s>>>(g);
         NP_LAUNCH_CHECK("sgemm_dma_kernel");
+        note_launch(NP_SGEMM_KERNEL_DMA, 256, 128, 16, -1, launch_flags(vec, edge, ktail, g.prio_period != 0, buf, g), 1, grid, g.K_last);
         note_progress_launch(g);
         return NP_OK;
     }
@@ -2877,8 +2905,10 @@ int launch_padded(const GemmArgs &g, const Plan &p, size_t Kp, size_t Np) {
     auto blocks = [&](size_t items) { return (unsigned)std::min<size_t>((items + 255) / 256, cap); };
     pad_copy_kernel<<<blocks((size_t)g.M * Kp / 4), 256, 0, s>>>(g.A, g.lda, g.M, g.K, (float *)wa.ptr, (unsigned)Kp, g.M);
     NP_LAUNCH_CHECK("pad_copy_kernel");
+    note_launch(NP_SGEMM_KERNEL_PAD_COPY, 0, 0, 0, -1, 0, (unsigned)Kp, dim3(blocks((size_t)g.M * Kp / 4)), 0);
     pad_copy_kernel<<<blocks(Kp * Np / 4), 256, 0, s>>>(g.B, g.ldb, g.K, g.N, (float *)wb.ptr, (unsigned)Np, (unsigned)Kp);
     NP_LAUNCH_CHECK("pad_copy_kernel");
+    note_launch(NP_SGEMM_KERNEL_PAD_COPY, 0, 0, 0, -1, 0, (unsigned)Np, dim3(blocks(Kp * Np / 4)), 0);
     GemmArgs q = g;
     q.A = (const float *)wa.ptr;
     q.B = (const float *)wb.ptr;
@@ -2975,6 +3005,7 @@ int launch_streamk(GemmArgs g, unsigned G) {
     else
         sgemm_streamk_kernel<false, false><<<G, 256, 0, s>>>(g, sk);
     NP_LAUNCH_CHECK("sgemm_streamk_kernel");
+    note_launch(NP_SGEMM_KERNEL_STREAMK, 256, 128, 16, -1, launch_flags(false, edge, ktail, g.prio_period != 0, buf, g), 1, dim3(G), 0);
     return NP_OK;
 }
 
@@ -3051,6 +3082,8 @@ int launch_dmas(int shape, GemmArgs g, unsigned batch, unsigned S) {
     else if (shape == 3) launch_dmas_shape<DmasShape3>(g, d, grid, edge, ktail, s);
     else launch_dmas_shape<DmasShape5>(g, d, grid, edge, ktail, s);
     NP_LAUNCH_CHECK("sgemm_dmas_kernel");
+    note_launch(NP_SGEMM_KERNEL_DMAS, bm, bn, bk, shape == 2 && g_mid_waves && S == 1 && (edge || ktail) ? 5 : shape,
+                launch_flags(false, edge, ktail, false, false, g), S, grid, 0);
     return NP_OK;
 }
 // ---- launch of sgemm_kq_kernel ----
@@ -3093,6 +3126,7 @@ int launch_kq(int shape, GemmArgs g, unsigned batch, bool vec) {
     const bool edge = g.M % bm || g.N % bn;
     launch_kq_any(shape, g, grid, edge, vec, np::stream(), std::make_integer_sequence<int, kKqShapeCount>{});
     NP_LAUNCH_CHECK("sgemm_kq_kernel");
+    note_launch(NP_SGEMM_KERNEL_KQ, bm, bn, 64, shape, launch_flags(vec, edge || !vec, false, false, false, g), g.k_chunks ? g.k_chunks : 1, grid, g.K_last);
     return NP_OK;
 }
 int g_force_kq = -1;   // np_sgemm_set_variant(-(2000 + shape)): every product the k-quartered kernel takes goes through it (A/B, tests); -999: off
@@ -3103,6 +3137,22 @@ int g_force_dmas_shape = -1, g_force_dmas_S = 1;   // np_sgemm_set_variant(-(100
 // batch, so that every piece — a single matrix included — runs the kernel configuration the whole batch would have
 // run, and the pipelined result is bit-identical to the one-call form (np::sgemm_batched_piece)
 thread_local size_t g_plan_batch = 0;   // (per host thread, like g_progress)
+
+// One dense product whose rows are not float4-loadable: do padded copies + the aligned kernel (launch_padded) beat the product as it
+// is, modelled at t_as_is?  *pp = the plan of the padded product, *t_pad its modelled time with the two copies.
+bool padded_copies_win(size_t M, size_t N, size_t K, bool sk_allowed, double t_as_is, Plan *pp, double *t_pad) {
+    const size_t Kp = (K + 15) / 16 * 16, Np = (N + 3) / 4 * 4;
+    *pp = plan_sgemm(M, Np, Kp, 1, true, true);
+    *t_pad = pp->t;
+    if (sk_allowed) {
+        unsigned G = 0;
+        const double t = streamk_model(M, Np, Kp, &G);
+        if (t < 0.99 * *t_pad) *t_pad = t;
+    }
+    // two pad launches: read + write of both operands
+    *t_pad += 2.0 * (double)((M * Kp + Kp * Np) * sizeof(float)) / 4e12 + 2 * 3e-6;
+    return *t_pad < t_as_is || g_force_pad;
+}
 
 int launch_planned(GemmArgs g, size_t launch_batch, bool vec) {
     const size_t M = g.M, N = g.N, K = g.K;
@@ -3130,20 +3180,14 @@ int launch_planned(GemmArgs g, size_t launch_batch, bool vec) {
     const bool take_sk = t_sk < 1e299 && (g_streamk > 0 || t_sk < 0.99 * p.t);
     if (!vec && batch == 1 && g_splitk && dense_c && N >= 1) {   // padded copies + the aligned kernel: still the faster form for the largest products
         const size_t Kp = (K + 15) / 16 * 16, Np = (N + 3) / 4 * 4;
-        Plan pp = plan_sgemm(M, Np, Kp, 1, true, true);
-        double t_pad = pp.t;
-        if (sk_allowed) {
-            unsigned G = 0;
-            const double t = streamk_model(M, Np, Kp, &G);
-            if (t < 0.99 * t_pad) t_pad = t;
-        }
-        // two pad launches: read + write of both operands
-        t_pad += 2.0 * (double)((M * Kp + Kp * Np) * sizeof(float)) / 4e12 + 2 * 3e-6;
+        Plan pp;
+        double t_pad;
         const double t_as_is = take_sk ? t_sk : p.t;
+        const bool pads = padded_copies_win(M, N, K, sk_allowed, t_as_is, &pp, &t_pad);
         if (debug)
             fprintf(stderr, "[np_sgemm] %zux%zux%zu pad candidate: cfg %d tail_rows %u S %u model %.1f us vs unpadded cfg %d tail %u S %u %.1f us\n",
                     M, N, K, pp.cfg, pp.tail_rows, pp.S, t_pad * 1e6, p.cfg, p.tail_rows, p.S, t_as_is * 1e6);
-        if (t_pad < t_as_is || g_force_pad) {
+        if (pads) {
             if (debug)
                 fprintf(stderr, "[np_sgemm] %zux%zux%zu -> padded to K %zu N %zu: cfg %d tail_rows %u S %u model %.1f us (unpadded %.1f)\n",
                         M, N, K, Kp, Np, pp.cfg, pp.tail_rows, pp.S, pp.t * 1e6, p.t * 1e6);
@@ -3624,6 +3668,7 @@ int sgemm_sub_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, const
     else
         sgemm_kernel<BM, BN, BK, 2, false, true, true><<<grid, 256, 0, s>>>(g);
     NP_LAUNCH_CHECK("sgemm_kernel (subtracting)");
+    note_launch(NP_SGEMM_KERNEL_TILE_SUB, BM, BN, BK, -1, launch_flags(vec, edge || !vec, false, false, false, g) | NP_SGEMM_LAUNCH_F_SUB, 1, grid, 0);
     return NP_OK;
 }
 
@@ -3659,6 +3704,31 @@ int np_sgemm_debug_plan(size_t M, size_t N, size_t K, size_t batch, int cus, dou
     out[5] = t_sk < 1e299 ? t_sk * 1e6 : 1e300;
     out[6] = mid.cfg; out[7] = mid.S; out[8] = mid.t < 1e299 ? mid.t * 1e6 : 1e300;
     out[9] = other.cfg; out[10] = other.t < 1e299 ? other.t * 1e6 : 1e300;
+    return NP_OK;
+}
+
+// debug: the same for ONE dense product whose rows are NOT float4-loadable (K % 4 or N % 4 != 0, or operands off 16 bytes), as
+// launch_planned decides it: out[0..2] = cfg / tail_rows / S of the tiled plan of the product as it is, out[3] 1 if stream-K is taken
+// instead, out[4] 1 if padded copies + the aligned kernel (launch_padded) are taken instead of either.
+int np_sgemm_debug_plan_unaligned(size_t M, size_t N, size_t K, int cus, double *out) {
+    if (!out || !M || !N || !K || cus < 0) return np::fail(NP_ERR_INVALID, "np_sgemm_debug_plan_unaligned: bad argument");
+    if (cus == 0)
+        if (int rc = np::ensure_init()) return rc;
+    g_plan_cus = cus;
+    const bool dma_ok = dma_takes(M, N, K, 1, false), sk_allowed = g_streamk >= 0;
+    unsigned G = 0;
+    double t_sk = 1e300;
+    if (sk_allowed && dma_ok) t_sk = streamk_model(M, N, K, &G) / 0.93;
+    const Plan p = plan_sgemm(M, N, K, 1, dma_ok, false, false, true, t_sk);
+    const bool take_sk = t_sk < 1e299 && (g_streamk > 0 || t_sk < 0.99 * p.t);
+    bool pads = false;
+    if (g_splitk) {
+        Plan pp;
+        double t_pad;
+        pads = padded_copies_win(M, N, K, sk_allowed, take_sk ? t_sk : p.t, &pp, &t_pad);
+    }
+    g_plan_cus = 0;
+    out[0] = p.cfg; out[1] = p.tail_rows; out[2] = p.S; out[3] = take_sk; out[4] = pads;
     return NP_OK;
 }
 
@@ -3782,6 +3852,23 @@ int np_sgemm_debug_last_path(unsigned *host_mask) {
     if (!host_mask) return np::fail(NP_ERR_INVALID, "np_sgemm_debug_last_path: null pointer");
     *host_mask = g_last_path;
     return NP_OK;
+}
+
+int np_sgemm_debug_last_launches(unsigned *host_records, unsigned capacity, unsigned *host_count) {
+    if (!host_count || (capacity && !host_records)) return np::fail(NP_ERR_INVALID, "np_sgemm_debug_last_launches: null pointer");
+    const unsigned kept = g_launch_count < NP_SGEMM_LAUNCH_KEPT ? g_launch_count : NP_SGEMM_LAUNCH_KEPT;
+    for (unsigned i = 0; i < kept && i < capacity; ++i)
+        for (unsigned w = 0; w < NP_SGEMM_LAUNCH_WORDS; ++w) host_records[i * NP_SGEMM_LAUNCH_WORDS + w] = g_launches[i][w];
+    *host_count = g_launch_count;
+    return NP_OK;
+}
+
+int np_sgemm_debug_sub_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, const float *B, size_t ldb, float *C, size_t ldc) {
+    if (!A || !B || !C || M == 0 || N == 0 || K == 0 || lda < K || ldb < N || ldc < N)
+        return np::fail(NP_ERR_INVALID, "np_sgemm_debug_sub_ld: needs operands, M, N, K >= 1, lda >= K, ldb >= N, ldc >= N");
+    PathScope scope;
+    if (int rc = np::ensure_init()) return rc;
+    return np::sgemm_sub_ld(M, N, K, A, lda, B, ldb, C, ldc);
 }
 
 int np_sgemm_debug_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, const float *B, size_t ldb, float *C, size_t ldc) {

@@ -14,6 +14,9 @@ that drops or doubles the element at a chunk edge, or the last K % 4 elements of
   framed    the host image of an operand at float offset 0 .. 3 inside a NaN-filled allocation; canary: the same for C, a -777
             frame around a NaN interior (an element the kernel does not write stays NaN, one it writes outside shows).
 
+tiled_launches() restates the HOST arithmetic of the launchers behind launch_sgemm_ld (which instantiation, which grid, which
+S) and returns the records np_sgemm_debug_last_launches must report; expected_sub() is the exact C0 - A . B of np::sgemm_sub_ld.
+
 path() / gemv_path() restate the dispatcher of np_sgemm.hip (launch_thin_nv, launch_fewrows, launch_skinny, the thin-left branch,
 np_sgemv) as arithmetic on a device of `cus` CUs and return the NP_SGEMM_PATH_ mask of include/np_hip_debug.h that
 np_sgemm_debug_last_path must report: the GPU tests name the mask of every case, the CPU tier checks the names against this
@@ -316,3 +319,347 @@ def path(m, n, k, cus=256, q=59, aligned=True):
     if m <= 16 and k <= 64 and n >= 65536:
         return THIN_LEFT | MV(4 if m <= 4 else 8 if m <= 8 else 16)
     return TILED
+
+
+# ---- the subtracting epilogue -----------------------------------------------------------------------------------------------------
+def expected_sub(C0, A, B):
+    """C0 - A . B as fp32 for integer C0, A, B with |C0| + |A| . |B| < 2^24: the accumulator (an integer below 2^24 in every order)
+    and the one subtraction at the end, or a subtraction per step, are all exact."""
+    C64 = np.asarray(C0, np.float64)
+    if not (np.isfinite(C64).all() and (C64 == np.rint(C64)).all()):
+        raise ValueError("expected_sub: C0 must be finite integers")
+    bound = np.abs(C64) + np.abs(np.asarray(A, np.float64)) @ np.abs(np.asarray(B, np.float64))
+    if bound.size and bound.max() >= EXACT_LIMIT:
+        raise ValueError("expected_sub: |C0| + |A| . |B| reaches %d: outside the exact fp32 range (2^24)" % int(bound.max()))
+    return (C64 - expected(A, B).astype(np.float64)).astype(np.float32)
+
+
+# ---- the launchers behind launch_sgemm_ld as arithmetic ---------------------------------------------------------------------------
+# NP_SGEMM_KERNEL_ / NP_SGEMM_LAUNCH_F_ of include/np_hip_debug.h (tests/test_gemm_reference_cpu.py checks them against the header)
+K_TILE, K_PIPE, K_DMA, K_STREAMK, K_DMAS, K_KQ, K_PAD_COPY, K_TILE_SUB = range(1, 9)
+KERNELS = {"TILE": K_TILE, "PIPE": K_PIPE, "DMA": K_DMA, "STREAMK": K_STREAMK, "DMAS": K_DMAS, "KQ": K_KQ, "PAD_COPY": K_PAD_COPY,
+           "TILE_SUB": K_TILE_SUB}
+F_VEC, F_EDGE, F_KTAIL, F_PRIO, F_BUF, F_SUB, F_SWIZZLE, F_CHUNK_MAJOR, F_PIPE_MODE1 = (1 << i for i in range(9))
+LAUNCH_FLAGS = {"VEC": F_VEC, "EDGE": F_EDGE, "KTAIL": F_KTAIL, "PRIO": F_PRIO, "BUF": F_BUF, "SUB": F_SUB, "SWIZZLE": F_SWIZZLE,
+                "CHUNK_MAJOR": F_CHUNK_MAJOR, "PIPE_MODE1": F_PIPE_MODE1}
+LAUNCH_WORDS, LAUNCH_KEPT = 8, 16
+DMAS_BM, DMAS_BN, DMAS_MAX_S, DMAS_BK = (128, 128, 64, 128, 128, 64), (128, 64, 64, 128, 64, 64), (16, 8, 4, 16, 8, 4), (16, 32, 32, 32, 32, 32)
+KQ_SHAPES = ((3, 3), (2, 2), (4, 4), (3, 2), (4, 2), (4, 3), (5, 3))       # TM, TN in 16-row / 16-column blocks
+CFG_TILES = ((256, 128), (128, 128), (64, 64), (128, 128), (128, 64), (64, 64)) + tuple((16 * a, 16 * b) for a, b in KQ_SHAPES)
+FIRST_MID_CFG, FIRST_KQ_CFG = 3, 6
+STREAMK_MAX_GRID = 1024
+
+
+class Launch(tuple):
+    """One record of np_sgemm_debug_last_launches: (family, bm, bn, bk, shape, flags, s, grid_x, grid_z, k_last); shape -1 = none."""
+    __slots__ = ()
+    FIELDS = ("family", "bm", "bn", "bk", "shape", "flags", "s", "grid_x", "grid_z", "k_last")
+
+    def __new__(cls, family, bm, bn, bk, shape, flags, s, grid_x, grid_z, k_last):
+        return tuple.__new__(cls, (int(family), int(bm), int(bn), int(bk), int(shape), int(flags), int(s), int(grid_x), int(grid_z), int(k_last)))
+
+    family, bm, bn, bk, shape, flags, s, grid_x, grid_z, k_last = (property(lambda self, i=i: self[i]) for i in range(10))
+
+    @classmethod
+    def decode(cls, words):
+        w = [int(x) for x in words]
+        return cls(w[0], w[1] & 0xffff, w[1] >> 16, w[2] & 0xffff, (w[2] >> 16) - 1, w[3], w[4], w[5], w[6], w[7])
+
+    def __repr__(self):
+        kernel = {v: n for n, v in KERNELS.items()}.get(self.family, "?%d" % self.family)
+        flags = "|".join(n for n, b in LAUNCH_FLAGS.items() if self.flags & b) or "0"
+        return "%s(%dx%dx%d shape %d, %s, S %d, grid %d x %d, K_last %d)" % (kernel, self.bm, self.bn, self.bk, self.shape, flags, self.s,
+                                                                            self.grid_x, self.grid_z, self.k_last)
+
+    def instantiation(self):
+        """What names the template instantiation: kernel, tile, shape and the template-argument flags."""
+        keep = F_VEC | F_EDGE | F_KTAIL | F_PRIO | F_BUF | F_SUB | F_PIPE_MODE1
+        return (self.family, self.bm, self.bn, self.bk, self.shape, self.flags & keep)
+
+
+class Knobs:
+    """The process-wide switches of np_sgemm.hip a launcher reads, at their defaults (include/np_hip_debug.h)."""
+
+    def __init__(self, **kw):
+        self.cus = 256
+        self.kloop = 1             # -31: 0, -32: 2, -33: 1
+        self.prio_period = 16      # -(100 + p); p != 16 applies at every K
+        self.prio_min_k = 2048
+        self.mid_waves = True      # -18 / -19
+        self.mid_swizzle = True    # -16 / -17
+        self.chunk_major = True    # -25 / -26
+        self.variant = 0           # g_variant: 0, 1 .. 7, 47
+        for name, value in kw.items():
+            if not hasattr(self, name):
+                raise TypeError("Knobs: no %s" % name)
+            setattr(self, name, value)
+        if "prio_period" in kw and "prio_min_k" not in kw:
+            self.prio_min_k = 2048 if self.prio_period == 16 else 0
+
+
+class _G:
+    """GemmArgs + what launch_sgemm_ld derives: the fields the launchers' conditions read."""
+
+    def __init__(self, m, n, k, lda, ldb, ldc, batch=1, sa=0, sb=0, a_aligned=True, b_aligned=True):
+        self.M, self.N, self.K, self.lda, self.ldb, self.ldc, self.batch = m, n, k, lda, ldb, ldc, batch
+        self.sa, self.sb, self.a_aligned, self.b_aligned = sa, sb, a_aligned, b_aligned
+        self.K_last = self.n_store = self.k_chunks = 0
+        self.swizzle = 0
+
+    def copy(self, **kw):
+        g = _G.__new__(_G)
+        g.__dict__.update(self.__dict__)
+        g.__dict__.update(kw)
+        return g
+
+    def vec(self):
+        return (self.K % 4 == 0 and self.lda % 4 == 0 and self.N % 4 == 0 and self.ldb % 4 == 0 and self.a_aligned and self.b_aligned
+                and self.sa % 4 == 0 and self.sb % 4 == 0)
+
+
+def _flags(vec=False, edge=False, ktail=False, prio=False, buf=False, swizzle=False, chunk_major=False):
+    return ((F_VEC if vec else 0) | (F_EDGE if edge else 0) | (F_KTAIL if ktail else 0) | (F_PRIO if prio else 0) | (F_BUF if buf else 0)
+            | (F_SWIZZLE if swizzle else 0) | (F_CHUNK_MAJOR if chunk_major else 0))
+
+
+def _kloop_takes(g, batch, ktail, in_default_set, kn):
+    return bool((kn.kloop == 2 or (kn.kloop == 1 and in_default_set)) and not ktail and g.a_aligned and g.b_aligned and g.lda % 4 == 0
+                and g.ldb % 4 == 0 and g.lda < 1 << 22 and g.ldb < 1 << 22 and (batch == 1 or (g.sa % 4 == 0 and g.sb % 4 == 0)))
+
+
+def _launch_tile(g, batch, vec, bm, bn, bk, family=K_TILE, extra=0):
+    """launch_sgemm_tile / launch_sgemm_pipe / np::sgemm_sub_ld: <VEC, EDGE> = (1, 0), (1, 1) or (0, 1)."""
+    edge = bool(g.M % bm or g.N % bn or g.K % bk or g.K_last % bk)
+    return Launch(family, bm, bn, bk, -1, _flags(vec, edge or not vec, swizzle=g.swizzle) | extra, 1, _cdiv(g.M, bm) * _cdiv(g.N, bn), batch, g.K_last)
+
+
+def _launch_dma(g, batch, vec, kn):
+    """launch_cfg(0): sgemm_dma_kernel<EDGE, KTAIL, PRIO, BUF>."""
+    tiles_m, tiles_n = _cdiv(g.M, 256), _cdiv(g.N, 128)
+    swizzle = g.swizzle or (kn.variant == 0 and tiles_m >= 8)
+    edge = bool(g.M % 256 or g.N % 128 or g.n_store)
+    ktail = bool(g.K % 16 or g.K_last % 16 or g.N % 4)
+    prio = bool(not edge and not ktail and kn.prio_period and g.K >= kn.prio_min_k)
+    buf = _kloop_takes(g, batch, ktail, prio, kn)
+    return Launch(K_DMA, 256, 128, 16, -1, _flags(vec, edge, ktail, prio, buf, swizzle), 1, tiles_m * tiles_n, batch, g.K_last)
+
+
+def streamk_grid(m, n, k, cus=256):
+    """streamk_model's grid: two workgroups per CU, else one, with ranges of at least 24 K-tiles; the SHORTER modelled time wins,
+    which needs the model's two efficiencies (kCfg[0].eff = 0.93 shared by two, eff1 = 0.89) and its 8 us + 3 us per fold.
+    0 where stream-K does not apply."""
+    tm, tn, nk = _cdiv(m, 256), _cdiv(n, 128), _cdiv(k, 16)
+    iters = tm * tn * nk
+    ragged = 1.02 if (m % 256 or n % 128 or k % 16) else 1.0
+    best, grid = 1e300, 0
+    for per_cu in (2, 1):
+        G = min(per_cu * cus, STREAMK_MAX_GRID)
+        per_wg = _cdiv(iters, G)
+        if per_wg < 24:
+            continue
+        eff = 0.93 / 2.0 if per_cu == 2 else 0.89
+        t_kt = 2.0 * 256.0 * 128.0 * 16.0 / (eff * (157.3e12 / 256.0))
+        folds = 1.0 if per_wg >= nk else float(_cdiv(nk, per_wg) - 1)
+        t = per_wg * t_kt * ragged + 8e-6 + 3e-6 * folds
+        if t < best:
+            best, grid = t, G
+    return grid
+
+
+def streamk_range_starts(m, n, k, G):
+    """Where sgemm_streamk_kernel cuts its K-tiles among G workgroups: workgroup w runs [iters . w / G, iters . (w + 1) / G) (floor),
+    iters = tiles . K-tiles, tile-major.  Returns (starts, K-tiles per tile); a start that is no multiple of the K-tile count lies
+    inside a tile: the partial before it ends there and the next one begins — a range edge."""
+    nk = _cdiv(k, 16)
+    iters = _cdiv(m, 256) * _cdiv(n, 128) * nk
+    G = min(G, iters)
+    return [iters * w // G for w in range(G)], nk
+
+
+def _launch_streamk(g, G, kn):
+    """launch_streamk on G workgroups."""
+    tiles_m, tiles_n, nk = _cdiv(g.M, 256), _cdiv(g.N, 128), _cdiv(g.K, 16)
+    G = min(G, tiles_m * tiles_n * nk)
+    edge = bool(g.M % 256 or g.N % 128 or g.n_store)
+    ktail = bool(g.K % 16 or g.N % 4)
+    buf = _kloop_takes(g, 1, ktail, False, kn)
+    prio = bool(not edge and not ktail and kn.prio_period)
+    return Launch(K_STREAMK, 256, 128, 16, -1, _flags(False, edge, ktail, prio, buf), 1, G, 1, 0)
+
+
+def dmas_plan(shape, m, n, k, batch, S, cus=256):
+    """launch_dmas's own arithmetic: (S after the clamp loop, chunk length Kc, tiles) or None where it returns 1 (does not apply)."""
+    if shape < 0 or shape > 5 or shape == 4 or n < 4 or k < 4:
+        return None
+    bm, bn, bk = DMAS_BM[shape], DMAS_BN[shape], DMAS_BK[shape]
+    tiles = _cdiv(m, bm) * _cdiv(n, bn)
+    if S < 1 or S & (S - 1) or S > DMAS_MAX_S[shape]:
+        return None
+    Kc = _cdiv(_cdiv(k, S), bk) * bk
+    while S > 1 and (Kc < 64 or (S - 1) * Kc >= k):
+        S >>= 1
+        Kc = _cdiv(_cdiv(k, S), bk) * bk
+    if S > 1 and (tiles * S * batch > cus * (1 if shape == 3 else 2) or tiles * batch > 256):
+        return None
+    return S, (Kc if S > 1 else _cdiv(k, bk) * bk), tiles
+
+
+def _launch_dmas(shape, g, batch, S, kn):
+    if g.K_last:
+        return None
+    plan = dmas_plan(shape, g.M, g.N, g.K, batch, S, kn.cus)
+    if plan is None:
+        return None
+    S, _, tiles = plan
+    bm, bn, bk = DMAS_BM[shape], DMAS_BN[shape], DMAS_BK[shape]
+    swizzle = bool(kn.mid_swizzle and S == 1 and _cdiv(g.M, bm) >= 8 and tiles >= 64)
+    edge = bool(g.M % bm or g.N % bn or g.n_store)
+    ktail = bool(g.K % bk or g.N % 4)
+    ran = 5 if shape == 2 and kn.mid_waves and S == 1 and (edge or ktail) else shape      # the DmasShape5 swap
+    return Launch(K_DMAS, bm, bn, bk, ran, _flags(False, edge, ktail, swizzle=swizzle), S, tiles * S, batch, 0)
+
+
+def _launch_kq(shape, g, batch, vec, kn):
+    if shape < 0 or shape >= len(KQ_SHAPES) or g.K < 4 or (g.K_last and g.K_last < 4) or g.n_store:
+        return None
+    bm, bn = 16 * KQ_SHAPES[shape][0], 16 * KQ_SHAPES[shape][1]
+    tiles_m, tiles = _cdiv(g.M, bm), _cdiv(g.M, bm) * _cdiv(g.N, bn)
+    if (g.M * g.lda + g.K) * 4 >= 1 << 32 or (g.K * g.ldb + g.N) * 4 >= 1 << 32:
+        return None
+    swizzle = tiles_m >= 8 and tiles >= 64
+    grid_x, grid_z, k_chunks = tiles, batch, g.k_chunks
+    if k_chunks:
+        if k_chunks != batch:
+            k_chunks = 0
+        else:
+            swizzle, grid_x, grid_z = False, tiles * batch, 1
+    edge = bool(g.M % bm or g.N % bn)
+    return Launch(K_KQ, bm, bn, 64, shape, _flags(vec, edge or not vec, swizzle=swizzle, chunk_major=bool(k_chunks)), k_chunks or 1, grid_x, grid_z,
+                  g.K_last)
+
+
+def _launch_cfg(cfg, g, batch, vec, kn):
+    """launch_cfg: the k-quartered tiles fall back on the 64 x 64 LDS-DMA tiles, those on the register-staged kernel of their size."""
+    if cfg >= FIRST_KQ_CFG:
+        rec = _launch_kq(cfg - FIRST_KQ_CFG, g, batch, vec, kn)
+        if rec is not None:
+            return rec
+        cfg = FIRST_MID_CFG + 2
+    if cfg >= FIRST_MID_CFG:
+        rec = _launch_dmas(cfg - FIRST_MID_CFG, g, batch, 1, kn)
+        if rec is not None:
+            return rec
+        cfg = 1 if cfg == FIRST_MID_CFG else 2
+    if cfg == 0:
+        return _launch_dma(g, batch, vec, kn)
+    return _launch_tile(g, batch, vec, *((128, 128) if cfg == 1 else (64, 64)), 16)
+
+
+def split_chunk_length(cfg, k, chunks):
+    """The chunk length Kc behind a split-K plan of `chunks` chunks: plan_sgemm tries S = 2 .. 8, 16, 32 .. and rounds ceil(K / S) up
+    to the K-tile (16; the k-quartered tiles 64); the plan keeps ceil(K / Kc) chunks.  Refuses where two S give that count with
+    different lengths (the cost model would have to say which)."""
+    unit = 64 if cfg >= FIRST_KQ_CFG else 16
+    found = set()
+    S = 2
+    while S <= 256:
+        Kc = _cdiv(_cdiv(k, S), unit) * unit
+        if _cdiv(k, Kc) == chunks:
+            found.add(Kc)
+        S = S + 1 if S < 8 else S * 2
+    if len(found) != 1:
+        raise ValueError("split_chunk_length: %d chunks of K = %d: candidates %s" % (chunks, k, sorted(found)))
+    return found.pop()
+
+
+def _launch_plan(cfg, tail_rows, S, g, batch, vec, kn, Kc=None):
+    """launch_plan -> (records, folded)."""
+    if tail_rows == 0 and cfg >= FIRST_MID_CFG and S > 1:
+        rec = _launch_dmas(cfg - FIRST_MID_CFG, g, batch, S, kn)
+        if rec is not None:
+            return [rec], False
+    if tail_rows == 0:
+        return [_launch_cfg(cfg, g, batch, vec, kn)], False
+    bm = CFG_TILES[cfg][0]
+    tm = _cdiv(g.M, bm)
+    m1 = (tm - tail_rows) * bm
+    m2 = g.M - m1
+    records = []
+    if m1:
+        records.append(_launch_cfg(cfg, g.copy(M=m1), 1, vec, kn))
+    if Kc is None:
+        Kc = split_chunk_length(cfg, g.K, S)
+    full, rem = divmod(g.K, Kc)
+    chunks = full + (1 if rem else 0)
+    part = g.copy(M=m2, K=Kc, K_last=rem, sa=Kc, sb=Kc * g.ldb, k_chunks=chunks if cfg >= FIRST_KQ_CFG and kn.chunk_major else 0)
+    records.append(_launch_cfg(cfg, part, chunks, vec and rem % 4 == 0, kn))
+    return records, True
+
+
+def _pad_copy(items, row_length, kn):
+    return Launch(K_PAD_COPY, 0, 0, 0, -1, 0, row_length, min(_cdiv(items, 256), kn.cus * 16), 1, 0)
+
+
+def tiled_launches(kind, m, n, k, batch=1, lda=None, ldb=None, ldc=None, sa=None, sb=None, a_aligned=True, b_aligned=True, shape=None, S=1,
+                   variant=None, plan=None, knobs=None):
+    """The records np_sgemm_debug_last_launches must report for one product call behind launch_sgemm_ld, or None where the forced
+    launcher returns 1 (the form does not apply and the call goes on to another kernel).  Returns (records, folded).
+
+      "dma"        np_sgemm_set_variant(7) / (47: knobs.variant): launch_cfg(0), sgemm_dma_kernel — sgemm_pipe_kernel where N < 4 or K < 4
+      "streamk"    (-4): launch_streamk on streamk_model's grid; None where the model gives none
+      "dmas"       (-(1000 + 100 shape + S)): launch_dmas
+      "kq"         (-(2000 + shape)): launch_kq on a whole product
+      "kq_chunks"  (-(30000 + 1000 shape + S)): the forced K-chunked plan on k-quartered tile `shape`, through launch_plan
+      "tile"       variant 1 .. 6: launch_sgemm_tile / launch_sgemm_pipe
+      "sub"        np::sgemm_sub_ld
+      "padded"     (-6, -3): launch_padded for K < 512, where the only plan of the padded product is one sgemm_dma_kernel launch
+      "plan"       the planner's choice plan = (cfg, tail_rows, S, stream-K taken) as np_sgemm_debug_plan reports it
+    """
+    kn = knobs or Knobs()
+    lda, ldb, ldc = lda or k, ldb or n, ldc or n
+    sa = (m * lda if batch > 1 else 0) if sa is None else sa
+    sb = (k * ldb if batch > 1 else 0) if sb is None else sb
+    g = _G(m, n, k, lda, ldb, ldc, batch, sa, sb, a_aligned, b_aligned)
+    vec = g.vec()
+    if kind == "sub":
+        sub_vec = k % 4 == 0 and lda % 4 == 0 and n % 4 == 0 and ldb % 4 == 0 and a_aligned and b_aligned
+        return [_launch_tile(g, 1, sub_vec, 128, 128, 16, K_TILE_SUB, F_SUB)], False
+    if kind == "dma":
+        g.swizzle = 4 if kn.variant == 47 else 0
+        if n >= 4 and k >= 4:
+            return [_launch_dma(g, batch, vec, kn)], False
+        return [_launch_tile(g, batch, vec, 128, 128, 16, K_PIPE, F_PIPE_MODE1)], False
+    if kind == "tile":
+        if variant in (5, 6):
+            return [_launch_tile(g, batch, vec, 128, 128, 16, K_PIPE, F_PIPE_MODE1 if variant == 6 else 0)], False
+        bm, bn, bk = {1: (128, 128, 16), 2: (128, 128, 32), 3: (128, 128, 16), 4: (64, 64, 16)}[variant]
+        return [_launch_tile(g, batch, vec, bm, bn, bk)], False
+    if kind == "dmas":
+        rec = _launch_dmas(shape, g, batch, S, kn)
+        return None if rec is None else ([rec], False)
+    if kind == "kq":
+        rec = _launch_kq(shape, g, batch, vec, kn)
+        return None if rec is None else ([rec], False)
+    if kind == "kq_chunks":
+        if not (S >= 2 and batch == 1 and k >= 512 and ldb == n and ldc == n):
+            return None
+        Kc = _cdiv(_cdiv(k, S), 64) * 64
+        chunks = _cdiv(k, Kc)
+        if chunks < 2 or k - (chunks - 1) * Kc < 4:
+            return None
+        return _launch_plan(FIRST_KQ_CFG + shape, _cdiv(m, 16 * KQ_SHAPES[shape][0]), chunks, g, 1, vec, kn, Kc)
+    if kind == "streamk":
+        G = streamk_grid(m, n, k, kn.cus)
+        return ([_launch_streamk(g, G, kn)], False) if G else None
+    if kind == "padded":
+        Kp, Np = _cdiv(k, 16) * 16, _cdiv(n, 4) * 4
+        if vec or batch != 1 or k >= 512 or streamk_grid(m, Np, Kp, kn.cus):
+            raise ValueError("tiled_launches: the padded form restated here is one matrix, not float4-loadable, K < 512, no stream-K")
+        q = g.copy(K=Kp, N=Np, lda=Kp, ldb=Np, n_store=n, a_aligned=True, b_aligned=True)
+        return [_pad_copy(m * Kp // 4, Kp, kn), _pad_copy(Kp * Np // 4, Np, kn), _launch_dma(q, 1, True, kn)], False
+    if kind == "plan":
+        cfg, tail_rows, chunks, streamk = plan
+        if streamk:
+            return [_launch_streamk(g, streamk_grid(m, n, k, kn.cus), kn)], False
+        return _launch_plan(int(cfg), int(tail_rows), int(chunks), g, batch, vec, kn)
+    raise ValueError("tiled_launches: unknown kind %r" % (kind,))

@@ -235,3 +235,165 @@ def test_sgemm_probe_is_declared_exported_and_prototyped():
     assert lib.np_sgemm_debug_last_path(None) != 0
     mask = C.c_uint(0xffffffff)
     assert lib.np_sgemm_debug_last_path(C.byref(mask)) == 0 and mask.value == 0
+
+
+# ---- the tiled kernels: tests/test_gpu_gemm_tiled_exact.py without a device --------------------------------------------------------------
+def _tiled_expectations():
+    """(case, offsets, records, mask) for every case of the GPU module at (0, 0) and (3, 3), under the case's own setters (the
+    planner-chosen ones ask np_sgemm_debug_plan, which reads them)."""
+    from numpower_amd import _lib
+    from tests import test_gpu_gemm_tiled_exact as t
+    from tests.gemm_exact import VARIANT_DEFAULTS
+    lib = _lib.load()
+    out = []
+    for c in t.all_cases():
+        try:
+            for code in t.codes_of(c):
+                assert lib.np_sgemm_set_variant(code) == 0, (c, code)
+            for off in ((0, 0),) if c.get("offsets") == "aligned" else ((0, 0), (3, 3)):
+                records, mask = t.expectation(c, lib, *off)
+                out.append((c, off, records, mask))
+        finally:
+            for code in VARIANT_DEFAULTS:
+                assert lib.np_sgemm_set_variant(code) == 0
+    return out
+
+
+def test_the_records_the_tiled_gpu_module_names_follow_from_the_launchers():
+    from tests import test_gpu_gemm_tiled_exact as t
+    keep = gf.F_VEC | gf.F_EDGE | gf.F_KTAIL | gf.F_PRIO | gf.F_BUF
+    seen = set()
+    for c, off, records, mask in _tiled_expectations():
+        assert 1 <= len(records) <= gf.LAUNCH_KEPT and mask in (0, gf.TILED, gf.TILED | gf.FOLD), c
+        if "flags" in c and off == (0, 0):
+            assert records[0].flags & keep == c["flags"], (c, records)
+        if off == (3, 3) and c["kind"] != "padded":
+            assert not any(r.flags & (gf.F_VEC | gf.F_BUF) for r in records), (c, records)       # no float4 rows, no buffer loop off 16 bytes
+        if "seam" in c:
+            assert c["seam"] in gf.k_seams(c["k"])
+            if c["kind"] == "streamk":       # on a range edge of the kernel's own floor(iters . w / G) split, inside a tile
+                starts, nk = gf.streamk_range_starts(c["m"], c["n"], c["k"], records[0].grid_x)
+                assert c["seam"] % 16 == 0 and c["seam"] // 16 in {s % nk for s in starts if s % nk}, (c, starts[:4])
+        if c["kind"] == "kq_chunks" and not c.get("refused"):
+            assert mask == gf.TILED | gf.FOLD and records[-1].k_last >= 4 and records[-1].grid_x * records[-1].grid_z % c["S"] == 0, (c, records)
+            major = c.get("knobs", {}).get("chunk_major", True)
+            assert bool(records[-1].flags & gf.F_CHUNK_MAJOR) == major and (records[-1].s == c["S"]) == major
+        seen.update(r.instantiation() for r in records)
+    T, E, KT, P, BF, SUB, M1 = gf.F_VEC, gf.F_EDGE, gf.F_KTAIL, gf.F_PRIO, gf.F_BUF, gf.F_SUB, gf.F_PIPE_MODE1
+    # sgemm_dma_kernel / sgemm_streamk_kernel <EDGE, KTAIL, PRIO, BUF>: the 8 of each (VEC is no template argument of theirs)
+    eight = {E | KT, E | BF, E, KT, P | BF, P, BF, 0}
+    for family in (gf.K_DMA, gf.K_STREAMK):
+        assert {i[5] & ~T for i in seen if i[0] == family} == eight, family
+    # sgemm_dmas_kernel: 5 tile shapes x EDGE x KTAIL, and every S
+    assert {(i[4], i[5]) for i in seen if i[0] == gf.K_DMAS} >= {(s, f) for s in (0, 1, 2, 3, 5) for f in (0, E, KT, E | KT)}
+    # sgemm_kq_kernel: 7 shapes x (VEC, VEC | EDGE, EDGE)
+    assert {(i[4], i[5]) for i in seen if i[0] == gf.K_KQ} == {(s, f) for s in range(7) for f in (T, T | E, E)}
+    # the register-staged tiles: 4 launch_sgemm_tile forms (two share <128, 128, 16> and differ in MINW) and the two pipe modes x 3
+    assert {(i[1], i[3], i[5]) for i in seen if i[0] == gf.K_TILE} == {(b, k, f) for b, k in ((128, 16), (128, 32), (64, 16)) for f in (T, T | E, E)}
+    assert {i[5] for i in seen if i[0] == gf.K_PIPE} == {f | m for f in (T, T | E, E) for m in (0, M1)}
+    assert {i[5] for i in seen if i[0] == gf.K_TILE_SUB} == {f | SUB for f in (T, T | E, E)} and any(i[0] == gf.K_PAD_COPY for i in seen)
+    # every S of the mid tiles, as launched
+    by_shape = {}
+    for c, off, records, mask in _tiled_expectations():
+        for r in records:
+            if r.family == gf.K_DMAS:
+                by_shape.setdefault(r.shape, set()).add(r.s)
+    assert by_shape[0] == {1, 2, 4, 8, 16} and by_shape[3] == {1, 2, 4, 8, 16} and by_shape[1] == {1, 2, 4, 8} and by_shape[2] >= {2, 4} and by_shape[5] >= {1}
+    # a forced K-chunk plan wants a remainder of at least 4: shorter ones never reach launch_kq
+    assert gf.tiled_launches("kq_chunks", 33, 35, 1281, shape=1, S=5) is None and gf.tiled_launches("kq_chunks", 48, 48, 1923, shape=0, S=7) is None
+
+
+def test_launcher_arithmetic_by_hand():
+    """A few records worked out by hand from np_sgemm.hip."""
+    L = gf.Launch
+    T, E, KT, P, BF = gf.F_VEC, gf.F_EDGE, gf.F_KTAIL, gf.F_PRIO, gf.F_BUF
+    kn7 = gf.Knobs(variant=7)
+    assert gf.tiled_launches("dma", 257, 130, 50, knobs=kn7) == ([L(gf.K_DMA, 256, 128, 16, -1, E | KT, 1, 4, 1, 0)], False)
+    assert gf.tiled_launches("dma", 4096, 4096, 4096) == ([L(gf.K_DMA, 256, 128, 16, -1, T | P | BF | gf.F_SWIZZLE, 1, 512, 1, 0)], False)
+    assert gf.tiled_launches("dma", 200, 3, 50, knobs=kn7)[0][0].family == gf.K_PIPE
+    # stream-K: 4 tiles x 1537 K-tiles = 6148 on 256 workgroups (512 would leave ranges of 13 < 24)
+    assert gf.streamk_range_starts(512, 256, 24592, 256)[0][:3] == [0, 24, 48] and gf.streamk_range_starts(512, 256, 24592, 256)[0][64] == 1537
+    assert gf.streamk_grid(512, 256, 24592) == 256 and gf.streamk_grid(768, 384, 208) == 0 and gf.streamk_grid(513, 257, 11008) == 256
+    assert gf.tiled_launches("streamk", 512, 256, 24592) == ([L(gf.K_STREAMK, 256, 128, 16, -1, P, 1, 256, 1, 0)], False)
+    # launch_dmas: the clamp loop (77 x 65 x 130 from S = 16: chunks of 16, 32, 48 are under 64; S = 2, Kc = 80) and residency
+    assert gf.dmas_plan(0, 77, 65, 130, 1, 16) == (2, 80, 1) and gf.dmas_plan(2, 768, 768, 256, 1, 4) is None
+    assert gf.dmas_plan(0, 129, 130, 1025, 1, 16) == (8, 144, 4) and gf.dmas_plan(4, 64, 64, 64, 1, 1) is None
+    assert gf.tiled_launches("dmas", 129, 130, 65, shape=2, S=1)[0][0].shape == 5            # ragged, whole K: eight waves
+    assert gf.tiled_launches("dmas", 64, 64, 64, shape=2, S=1)[0][0].shape == 2
+    # launch_plan: 33 x 35 x 2049 in 5 chunks of 448, remainder 257, 2 x 2 tiles of 32 x 32
+    records, folded = gf.tiled_launches("kq_chunks", 33, 35, 2049, shape=1, S=5)
+    assert folded and records == [L(gf.K_KQ, 32, 32, 64, 1, E | gf.F_CHUNK_MAJOR, 5, 20, 1, 257)]
+    records, _ = gf.tiled_launches("kq_chunks", 33, 35, 2049, shape=1, S=5, knobs=gf.Knobs(chunk_major=False))
+    assert records == [L(gf.K_KQ, 32, 32, 64, 1, E, 1, 4, 5, 257)]
+    assert gf.split_chunk_length(0, 2052, 2) == 1040 and gf.split_chunk_length(6, 10000, 8) == 1280
+    words = [5, 128 | 64 << 16, 32 | 2 << 16, E | KT, 4, 24, 3, 0]
+    assert L.decode(words) == L(gf.K_DMAS, 128, 64, 32, 1, E | KT, 4, 24, 3, 0) and "DMAS(128x64x32 shape 1, EDGE|KTAIL, S 4" in repr(L.decode(words))
+
+
+def test_split_k_plans_pinned():
+    """With the mid and k-quartered plans off (-14, -20, -22) cfg 0 .. 2 plan alone.  The smallest square-ish shapes whose plan
+    splits every tile row with a remainder chunk, and one that splits only a tail of rows, as the GPU module uses them."""
+    from numpower_amd import _lib
+    from tests import test_gpu_gemm_tiled_exact as t
+    from tests.gemm_exact import VARIANT_DEFAULTS
+    lib = _lib.load()
+    try:
+        for code in t.SPLITK_CODES:
+            assert lib.np_sgemm_set_variant(code) == 0
+        pinned = {(64, 64, 516): (2, 1, 4, 144, 84), (128, 128, 2052): None, (1216, 1728, 1028): (2, 1, 8, 144, 20)}
+        for c in t.SPLITK_ALL_ROWS + t.SPLITK_TAIL_ROWS:
+            cfg, tail_rows, chunks, streamk = t.plan_of(lib, c["m"], c["n"], c["k"], 1)
+            rows = -(-c["m"] // gf.CFG_TILES[cfg][0])
+            Kc = gf.split_chunk_length(cfg, c["k"], chunks)
+            assert not streamk and cfg <= 2 and chunks >= 2 and c["k"] % Kc, (c, cfg, tail_rows, chunks)
+            if pinned[c["m"], c["n"], c["k"]]:
+                assert (cfg, tail_rows, chunks, Kc, c["k"] % Kc) == pinned[c["m"], c["n"], c["k"]]
+            records, mask = t.expectation(c, lib)
+            assert mask == gf.TILED | gf.FOLD and records[-1].k_last == c["k"] % Kc and records[-1].grid_z == chunks
+            if c in t.SPLITK_ALL_ROWS:
+                assert tail_rows == rows and len(records) == 1
+            else:
+                assert 0 < tail_rows < rows and len(records) == 2 and records[0].grid_z == 1 and records[0].k_last == 0
+    finally:
+        for code in VARIANT_DEFAULTS:
+            assert lib.np_sgemm_set_variant(code) == 0
+
+
+def test_subtracting_expectation_against_int64():
+    for m, n, k in ((5, 4, 64), (129, 127, 17), (200, 72, 64)):
+        A, B = gf.operands(m, n, k, 3, 64, 64)
+        c0 = np.random.default_rng(1).integers(-1000, 1001, size=(m, n)).astype(np.float32)
+        want = gf.expected_sub(c0, A, B)
+        exact = c0.astype(np.int64) - A.astype(np.int64) @ B.astype(np.int64)
+        assert want.dtype == np.float32 and (want.astype(np.int64) == exact).all() and np.abs(exact).max() < gf.EXACT_LIMIT
+        acc = c0.copy()                                                    # a subtraction per step, in fp32: the same bits
+        for kk in range(k):
+            acc -= np.multiply.outer(A[:, kk], B[kk])
+        assert _same(acc, want) and _same(c0 - A @ B, want)
+    with pytest.raises(ValueError):
+        gf.expected_sub(np.full((1, 1), 2.0 ** 24 - 4, np.float32), np.full((1, 1), 2, np.float32), np.full((1, 1), 2, np.float32))
+    with pytest.raises(ValueError):
+        gf.expected_sub(np.full((1, 1), 0.5, np.float32), np.ones((1, 1), np.float32), np.ones((1, 1), np.float32))
+
+
+def test_launch_probe_is_declared_exported_and_prototyped():
+    from numpower_amd import _lib
+    header = (ROOT / "include" / "np_hip_debug.h").read_text()
+    lib = _lib.load()
+    assert "int np_sgemm_debug_last_launches(unsigned *host_records, unsigned capacity, unsigned *host_count);" in header
+    assert "int np_sgemm_debug_sub_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, const float *B, size_t ldb, float *C, size_t ldc);" in header
+    assert "int np_sgemm_debug_plan_unaligned(size_t M, size_t N, size_t K, int cus, double *out);" in header
+    for name in ("np_sgemm_debug_last_launches", "np_sgemm_debug_sub_ld", "np_sgemm_debug_plan_unaligned"):
+        assert hasattr(lib, name) and name in _lib.PROTOTYPES and name not in (ROOT / "include" / "np_hip.h").read_text()
+    kernels = {k: int(v) for k, v in re.findall(r"#define NP_SGEMM_KERNEL_(\w+) (\d+)u", header)}
+    flags = {k: int(v, 16) for k, v in re.findall(r"#define NP_SGEMM_LAUNCH_F_(\w+) (0x[0-9a-f]+)u", header)}
+    assert kernels == gf.KERNELS and flags == gf.LAUNCH_FLAGS
+    assert "#define NP_SGEMM_LAUNCH_WORDS %du" % gf.LAUNCH_WORDS in header and "#define NP_SGEMM_LAUNCH_KEPT %du" % gf.LAUNCH_KEPT in header
+    assert gf.LAUNCH_KEPT >= 8
+    words = dict(re.findall(r"#define NP_SGEMM_LAUNCH_(FAMILY|TILE|BK|FLAGS|S|GRID_X|GRID_Z|K_LAST) (\d)\n", header))
+    assert [int(words[w]) for w in ("FAMILY", "TILE", "BK", "FLAGS", "S", "GRID_X", "GRID_Z", "K_LAST")] == list(range(8))
+    # without a device, before any product: null pointers are refused, no launch is recorded; the wrapper checks its arguments
+    count = C.c_uint(77)
+    assert lib.np_sgemm_debug_last_launches(None, 0, None) != 0 and lib.np_sgemm_debug_last_launches(None, 4, C.byref(count)) != 0
+    assert lib.np_sgemm_debug_last_launches(None, 0, C.byref(count)) == 0 and count.value == 0
+    assert lib.np_sgemm_debug_sub_ld(0, 4, 4, None, 4, None, 4, None, 4) != 0 and lib.np_sgemm_debug_sub_ld(4, 4, 4, 16, 3, 16, 4, 16, 4) != 0

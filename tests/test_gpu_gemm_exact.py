@@ -12,142 +12,25 @@ specials() kind at three K positions (first, last, one on a chunk / step boundar
 
 Masks are written for the 256 CUs of the MI355X: the launchers size their K-chunks by np::num_cus().  The names are checked
 against the dispatcher's arithmetic (gemm_family.path / gemv_path) in tests/test_gemm_reference_cpu.py, and again here."""
-import contextlib
 import ctypes as C
 
-import numpy as np
 import pytest
 
 from numpower_amd import _lib
 from tests import gemm_family as gf
+from tests.gemm_exact import ALL_OFFSETS, DIAGONAL, Dev, exact_operands, run, sgemm_variant, with_specials
 from tests.gemm_family import (FEWROWS, FEWROWS_SPLITK1, FEWROWS_SPLITK2, FOLD, GEMV_CHUNKS, GEMV_FEWROWS_CHUNKS, GEMV_SHORT_ROWS,
                                GEMV_STAGED, GEMV_WAVE, GEMV_WAVE_VEC, LANES, MV, PEELED, SKINNY, THIN_CHUNKS, THIN_K_CHUNKS,
                                THIN_LANES, THIN_LEFT, THIN_MFMA16, THIN_MFMA32, THIN_MFMA32X2, TILED)
 
 pytestmark = pytest.mark.gpu
 
-DIAGONAL = ((0, 0), (3, 3))
-ALL_OFFSETS = tuple((a, b) for a in range(4) for b in range(4))
 THIN_Q_DEFAULT = 59          # g_thin_underfilled_to_planner
-
-
-class Dev:
-    def __init__(self, hip):
-        self.L = _lib.load()
-        cus = C.c_int()
-        _lib.check(self.L.np_debug_cus(C.byref(cus)))
-        assert cus.value == 256, "the masks of this module are written for 256 CUs; np_debug_cus reports %d" % cus.value
-
-    def upload(self, image):
-        buf = _lib.DeviceBuffer(image.nbytes)
-        assert buf.ptr % 16 == 0
-        _lib.check(self.L.np_memcpy_h2d(buf.ptr, image.ctypes.data, image.nbytes))
-        return buf
-
-    def download(self, buf, count):
-        out = np.empty(count, np.float32)
-        _lib.check(self.L.np_memcpy_d2h(out.ctypes.data, buf.ptr, out.nbytes))
-        return out
-
-    def last_path(self):
-        mask = C.c_uint()
-        _lib.check(self.L.np_sgemm_debug_last_path(C.byref(mask)))
-        return mask.value
 
 
 @pytest.fixture(scope="module")
 def dev(hip):
     return Dev(hip)
-
-
-@contextlib.contextmanager
-def sgemm_variant(dev, code, back):
-    _lib.check(dev.L.np_sgemm_set_variant(code))
-    try:
-        yield
-    finally:
-        _lib.check(dev.L.np_sgemm_set_variant(back))
-
-
-class Placed:
-    """One operand uploaded at each float offset asked for, once."""
-
-    def __init__(self, dev, array):
-        self.dev, self.array, self.at = dev, array, {}
-
-    def ptr(self, offset):
-        if offset not in self.at:
-            image, start = gf.framed(self.array, offset)
-            self.at[offset] = (self.dev.upload(image), start)
-        buf, start = self.at[offset]
-        return buf.ptr + 4 * start
-
-    def free(self):
-        for buf, _ in self.at.values():
-            buf.free()
-
-
-def run(dev, A, B, want, mask, offsets=DIAGONAL, gemv=False, cls=None, label=""):
-    """C = A . B (np_sgemm) or y = A . x (np_sgemv, B a vector) at every offset pair: bits against `want` (where cls is given: the
-    class of every element against cls, bits wherever the class is not NaN), the frame, a second call, the whole mask, np_sync.
-    mask: a value, a function of the two offsets where it depends on the alignment, or a frozenset of values where the planner's
-    own model decides between them."""
-    m, k = A.shape
-    n = 1 if gemv else B.shape[1]
-    pa, pb = Placed(dev, A), Placed(dev, B)
-    image, start = gf.canary(m * n)
-    cbuf = dev.upload(image)
-    try:
-        for oa, ob in offsets:
-            tag = "%s %s offsets A %d, B %d" % (label, (m, n, k), oa, ob)
-            a_ptr, b_ptr = pa.ptr(oa), pb.ptr(ob)
-            runs = []
-            for _ in range(2):
-                _lib.check(dev.L.np_memcpy_h2d(cbuf.ptr, image.ctypes.data, image.nbytes))
-                if gemv:
-                    _lib.check(dev.L.np_sgemv(m, k, a_ptr, b_ptr, cbuf.ptr + 4 * start))
-                else:
-                    _lib.check(dev.L.np_sgemm(m, n, k, a_ptr, b_ptr, cbuf.ptr + 4 * start))
-                got_mask = dev.last_path()
-                assert dev.L.np_sync() == 0, tag
-                host = dev.download(cbuf, image.size)
-                assert gf.frame_intact(host, start, m * n), tag + ": wrote outside C"
-                runs.append(host[start:start + m * n].reshape(want.shape).copy())
-                expect_mask = mask(oa, ob) if callable(mask) else mask
-                if isinstance(expect_mask, frozenset):
-                    assert got_mask in expect_mask, "%s: ran %s, the case names one of %s" % (
-                        tag, gf.describe(got_mask), sorted(map(gf.describe, expect_mask)))
-                else:
-                    assert got_mask == expect_mask, "%s: ran %s, the case names %s" % (tag, gf.describe(got_mask), gf.describe(expect_mask))
-            got = runs[0]
-            assert (gf.bits(got) == gf.bits(runs[1])).all(), tag + ": two calls differ"
-            if cls is None:
-                bad = np.argwhere(gf.bits(got) != gf.bits(want))
-                assert bad.size == 0, "%s: %d elements differ, first at %s: got %r, exact %r" % (
-                    tag, len(bad), tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])])
-            else:
-                assert (gf.classify(got) == cls).all(), "%s: class map differs at %s" % (tag, np.argwhere(gf.classify(got) != cls)[:4].tolist())
-                keep = cls != gf.NAN
-                assert (gf.bits(got)[keep] == gf.bits(want)[keep]).all(), tag + ": a finite / infinite element differs"
-    finally:
-        cbuf.free()
-        pa.free()
-        pb.free()
-
-
-_OPERANDS = {}
-
-
-def exact_operands(m, n, k, seed=7):
-    """A, B, A . B for one shape; A is the first m rows of the largest A generated for (k, seed) so far, B one draw per (k, n)."""
-    amp = gf.amp_for(k)
-    key = (n, k, seed)
-    if key not in _OPERANDS or _OPERANDS[key][0].shape[0] < m:
-        _OPERANDS.clear()                      # one (n, k) at a time: the big shapes are hundreds of MB
-        _OPERANDS[key] = gf.operands(m, n, k, seed, amp, amp)
-    A, B = _OPERANDS[key]
-    A = A[:m]
-    return A, B, gf.expected(A, B)
 
 
 def product(dev, m, n, k, mask, offsets=DIAGONAL, label=""):
@@ -162,21 +45,6 @@ def matvec(dev, m, n, mask, offsets=DIAGONAL, label=""):
     A, _ = gf.operands(m, 1, n, 11, amp, amp)
     x = gf.vector(n, 12, amp)
     run(dev, A, x, gf.expected(A, x), mask, offsets, gemv=True, label=label)
-
-
-def with_specials(dev, m, n, k, mask, seam, gemv=False, label=""):
-    """Every specials() kind at the first, the last and one boundary position of K, at the row / column edges."""
-    seams = gf.k_seams(k)
-    assert seam in seams and 0 < seam < k - 1
-    amp = gf.amp_for(k)
-    A, B = gf.operands(m, n, k, 21, amp, amp)
-    if gemv:
-        B = B[:, 0].copy()
-    base = gf.expected(A, B)
-    for ks, i, j in ((seams[0], 0, 0), (seams[-1], m - 1, n - 1), (seam, m - 1, 0)):
-        for kind in gf.SPECIAL_KINDS:
-            A2, B2, cls, want = gf.specials(A, B, kind, ks, i, j, ks2=(ks + k // 2) % k, base=base)
-            run(dev, A2, B2, want, mask, ((0, 0),), gemv=gemv, cls=cls, label="%s special %d at k = %d" % (label, kind, ks))
 
 
 # ---- sgemm_thin_kernel: every L ---------------------------------------------------------------------------------------------
