@@ -1,5 +1,5 @@
 /*
- * hip_dnn.c — the device side of NDArrayDNN_Conv2D_Forward / _Backward and of the pooling layers (hip_dnn.h).  Compiled into a --with-hip tree against the
+ * hip_dnn.c — the device side of NDArrayDNN_Conv2D_Forward / _Backward, of the pooling layers and of softmax / cross-entropy (hip_dnn.h).  Compiled into a --with-hip tree against the
  * reference's headers (-DNUMPOWER_NDARRAY_HEADER='"src/initializers.h"') and into libnumpower_host.so against
  * include/numpower_host.h; it uses only what both declare, with one switch: the reference's arrays take ownership of an
  * emalloc'd shape and its result vectors are emalloc'd, the host library copies shapes and hands out malloc'd vectors.
@@ -377,5 +377,164 @@ NDArray *NPH_Pool2D_Backward(NDArray *x, NDArray *dy, const int kernel[2], const
         return NULL;
     }
     return dx;
+}
+
+/* ---- softmax, log-softmax and cross-entropy (hip_dnn.h): np_softmax_forward / _backward and np_cross_entropy ---- */
+
+typedef struct { size_t outer, cols, inner; int mode; } nph_softmax;
+
+/* 's', 'l' -> np_softmax_mode, -1 for anything else */
+static int softmax_mode_of(char mode) {
+    switch (mode) {
+    case 's': return NP_SOFTMAX;
+    case 'l': return NP_LOG_SOFTMAX;
+    default: return -1;
+    }
+}
+
+/* the checks both directions share, in the order of hip_dnn.h; dy == NULL: forward.  0 after a raised error */
+static int softmax_of(NDArray *x, NDArray *dy, int axis, char mode, nph_softmax *s) {
+    s->mode = softmax_mode_of(mode);
+    if (s->mode < 0) {
+        np_ext_throw(NPH_SOFTMAX_MSG_MODE);
+        return 0;
+    }
+    const int ndim = NDArray_NDIM(x);
+    if (ndim < 1 || axis < -ndim || axis >= ndim) {
+        np_ext_throw(NPH_SOFTMAX_MSG_AXIS);
+        return 0;
+    }
+    if (axis < 0) axis += ndim;
+    const int *xs = NDArray_SHAPE(x);
+    if (dy != NULL) {
+        int same = NDArray_NDIM(dy) == ndim;
+        for (int d = 0; same && d < ndim; ++d) same = NDArray_SHAPE(dy)[d] == xs[d];
+        if (!same) {
+            np_ext_throw(NPH_SOFTMAX_MSG_GRADIENT);
+            return 0;
+        }
+        if (NDArray_DEVICE(dy) != NDArray_DEVICE(x)) {
+            np_ext_throw(NPH_SOFTMAX_MSG_DEVICE);
+            return 0;
+        }
+    }
+    if (NDArray_DEVICE(x) != NDARRAY_DEVICE_GPU) {
+        np_ext_throw(NPH_SOFTMAX_MSG_CPU);
+        return 0;
+    }
+    s->outer = 1, s->inner = 1, s->cols = (size_t) xs[axis];
+    for (int d = 0; d < axis; ++d) s->outer *= (size_t) xs[d];
+    for (int d = axis + 1; d < ndim; ++d) s->inner *= (size_t) xs[d];
+    if (s->outer < 1 || s->cols < 1 || s->inner < 1) {
+        np_ext_throw("softmax: an operand has no elements");
+        return 0;
+    }
+    return 1;
+}
+
+/* a new GPU array of a's shape */
+static NDArray *empty_like_on_gpu(NDArray *a) {
+    const int ndim = NDArray_NDIM(a);
+    int *shape = (int *) NPH_ALLOC(sizeof(int) * (size_t) ndim);
+    if (shape == NULL) return NULL;
+    for (int d = 0; d < ndim; ++d) shape[d] = NDArray_SHAPE(a)[d];
+    NDArray *rtn = NDArray_Empty(shape, ndim, "float32", NDARRAY_DEVICE_GPU);
+    if (NPH_SHAPE_IS_COPIED) NPH_RELEASE(shape);
+    return rtn;
+}
+
+NDArray *NPH_Softmax_Forward(NDArray *x, int axis, char mode) {
+    nph_softmax s;
+    if (x == NULL || !softmax_of(x, NULL, axis, mode, &s)) return NULL;
+    NDArray *rtn = empty_like_on_gpu(x);
+    if (rtn == NULL) return NULL;
+    if (np_softmax_forward(NDArray_FDATA(x), s.outer, s.cols, s.inner, s.mode, NDArray_FDATA(rtn)) != NP_OK) {
+        np_ext_throw_last();
+        NDArray_FREE(rtn);
+        return NULL;
+    }
+    return rtn;
+}
+
+NDArray *NPH_Softmax_Backward(NDArray *y, NDArray *dy, int axis, char mode) {
+    nph_softmax s;
+    if (y == NULL || dy == NULL || !softmax_of(y, dy, axis, mode, &s)) return NULL;
+    NDArray *dx = empty_like_on_gpu(y);
+    if (dx == NULL) return NULL;
+    if (np_softmax_backward(NDArray_FDATA(y), NDArray_FDATA(dy), s.outer, s.cols, s.inner, s.mode, NDArray_FDATA(dx)) != NP_OK) {
+        np_ext_throw_last();
+        NDArray_FREE(dx);
+        return NULL;
+    }
+    return dx;
+}
+
+/* the checks of the cross-entropy, in the order of hip_dnn.h: *kind is the np_xent_target.  0 after a raised error */
+static int xent_of(NDArray *logits, NDArray *target, char reduction, int *kind) {
+    if (NDArray_NDIM(logits) != 2) {
+        np_ext_throw(NPH_XENT_MSG_LOGITS);
+        return 0;
+    }
+    const int *ls = NDArray_SHAPE(logits), *ts = NDArray_SHAPE(target);
+    if (NDArray_NDIM(target) == 1 && ts[0] == ls[0]) *kind = NP_XENT_INDEX;
+    else if (NDArray_NDIM(target) == 2 && ts[0] == ls[0] && ts[1] == ls[1]) *kind = NP_XENT_PROB;
+    else {
+        np_ext_throw(NPH_XENT_MSG_TARGET);
+        return 0;
+    }
+    if (reduction != 'n' && reduction != 's' && reduction != 'm') {
+        np_ext_throw(NPH_XENT_MSG_REDUCTION);
+        return 0;
+    }
+    if (NDArray_DEVICE(target) != NDArray_DEVICE(logits)) {
+        np_ext_throw(NPH_XENT_MSG_DEVICE);
+        return 0;
+    }
+    if (NDArray_DEVICE(logits) != NDARRAY_DEVICE_GPU) {
+        np_ext_throw(NPH_XENT_MSG_CPU);
+        return 0;
+    }
+    if (ls[0] < 1 || ls[1] < 1) {
+        np_ext_throw("dnn_cross_entropy: an operand has no elements");
+        return 0;
+    }
+    return 1;
+}
+
+NDArray *NPH_CrossEntropy(NDArray *logits, NDArray *target, char reduction, int with_grad, NDArray **dlogits) {
+    int kind = 0;
+    if (dlogits != NULL) *dlogits = NULL;
+    if (logits == NULL || target == NULL || !xent_of(logits, target, reduction, &kind)) return NULL;
+    const size_t rows = (size_t) NDArray_SHAPE(logits)[0], cols = (size_t) NDArray_SHAPE(logits)[1];
+    NDArray *loss_rows = empty_on_gpu(1, &rows);
+    if (loss_rows == NULL) return NULL;
+    NDArray *grad = (with_grad && dlogits != NULL) ? empty_like_on_gpu(logits) : NULL;
+    if (with_grad && dlogits != NULL && grad == NULL) {
+        NDArray_FREE(loss_rows);
+        return NULL;
+    }
+    const float scale = reduction == 'm' ? 1.0f / (float) rows : 1.0f;
+    if (np_cross_entropy(NDArray_FDATA(logits), NDArray_FDATA(target), rows, cols, kind, scale, NDArray_FDATA(loss_rows),
+                         grad != NULL ? NDArray_FDATA(grad) : NULL) != NP_OK) {
+        np_ext_throw_last();
+        NDArray_FREE(loss_rows);
+        if (grad != NULL) NDArray_FREE(grad);
+        return NULL;
+    }
+    NDArray *rtn = loss_rows;
+    if (reduction != 'n') {      /* the library's sum of the rows' losses; the mean divides it once */
+        float total = 0.0f;
+        const int summed = np_reduce_all(NP_SUM, NDArray_FDATA(loss_rows), rows, &total) == NP_OK;
+        if (!summed) np_ext_throw_last();
+        if (reduction == 'm') total = total / (float) rows;
+        NDArray_FREE(loss_rows);
+        rtn = summed ? NDArray_CreateFromFloatScalar(total) : NULL;
+        if (rtn == NULL) {
+            if (grad != NULL) NDArray_FREE(grad);
+            return NULL;
+        }
+    }
+    if (grad != NULL) *dlogits = grad;
+    return rtn;
 }
 

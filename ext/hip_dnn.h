@@ -120,6 +120,34 @@ struct NDArray *NPH_Pool2D_Forward(struct NDArray *x, const int kernel[2], const
 /* dx (N, C, H, W), a new GPU array; dy: the gradient of the forward result, of its shape.  Cells that no window covers get +0 */
 struct NDArray *NPH_Pool2D_Backward(struct NDArray *x, struct NDArray *dy, const int kernel[2], const int stride[2], const int padding[2], char mode);
 
+/* ---- softmax, log-softmax and cross-entropy (np_softmax_forward / _backward, np_cross_entropy of include/np_hip.h) ----
+ * The reference has none of them, so tools/apply_with_hip.py inserts nothing; they are what a binding with these methods calls.
+ * x has any ndim >= 1 and is seen as (outer, cols, inner) around `axis` (negative axes count from the end).  mode: 's' softmax,
+ * 'l' log-softmax.  The backward pass works from the OUTPUT y of the forward pass and the gradient dy of that output.
+ * The cross-entropy takes 2-D logits (rows, cols) and a target that is either (rows) class indices stored as fp32 or
+ * (rows, cols) probabilities.  reduction: 'n' none: the (rows) losses, scale 1; 's' sum: the library's sum of those losses (np_reduce_all),
+ * scale 1; 'm' mean: that sum divided once by (float) rows, scale = 1.0f / (float) rows.  With with_grad, *dlogits receives
+ * (softmax - target) . scale from the same launch.  A sum or a mean is returned as a 0-dimensional array.
+ * The messages, checked in this order (the gradient's by NPH_Softmax_Backward alone; the logits', target's and reduction's by
+ * NPH_CrossEntropy alone): */
+#define NPH_SOFTMAX_MSG_MODE "softmax: unknown mode: 's' (softmax), 'l' (log-softmax)"
+#define NPH_SOFTMAX_MSG_AXIS "softmax: the axis is out of range for the operand's dimensions"
+#define NPH_SOFTMAX_MSG_GRADIENT "softmax_backward: the gradient must have the shape of the output"
+#define NPH_XENT_MSG_LOGITS "dnn_cross_entropy: the logits must be 2-dimensional (rows, classes)"
+#define NPH_XENT_MSG_TARGET "dnn_cross_entropy: the target must be (rows) class indices or (rows, classes) probabilities"
+#define NPH_XENT_MSG_REDUCTION "dnn_cross_entropy: unknown reduction: 'n' (none), 's' (sum), 'm' (mean)"
+#define NPH_SOFTMAX_MSG_DEVICE "softmax: the operands must be on the same device"
+#define NPH_SOFTMAX_MSG_CPU "softmax: operands are on the CPU; numpower_amd only computes on the GPU (call ->gpu() first)"
+#define NPH_XENT_MSG_DEVICE "dnn_cross_entropy: the operands must be on the same device"
+#define NPH_XENT_MSG_CPU "dnn_cross_entropy: operands are on the CPU; numpower_amd only computes on the GPU (call ->gpu() first)"
+
+/* y, a new GPU array of x's shape */
+struct NDArray *NPH_Softmax_Forward(struct NDArray *x, int axis, char mode);
+/* dx, a new GPU array of y's shape */
+struct NDArray *NPH_Softmax_Backward(struct NDArray *y, struct NDArray *dy, int axis, char mode);
+/* the loss; *dlogits (when with_grad != 0 and dlogits != NULL) a new GPU array of the logits' shape, NULL after an error */
+struct NDArray *NPH_CrossEntropy(struct NDArray *logits, struct NDArray *target, char reduction, int with_grad, struct NDArray **dlogits);
+
 #ifdef __cplusplus
 }
 #endif

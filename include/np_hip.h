@@ -701,6 +701,52 @@ int np_pool2d_forward(const float *x, size_t planes, size_t H, size_t W, size_t 
 int np_pool2d_backward(const float *dy, const int32_t *idx, size_t planes, size_t H, size_t W, size_t kh, size_t kw,
                        size_t ph, size_t pw, size_t sh, size_t sw, int mode, float *dx);   /* idx needed for max, ignored otherwise */
 
+/* ---- softmax, log-softmax and cross-entropy (np_softmax.hip; DESIGN.md "softmax") ------------
+ * The operand is a contiguous fp32 array seen as (outer, cols, inner); the softmax runs over cols; inner == 1 is the row case.
+ *   Row statistics  m is the row maximum (a NaN never wins the comparison).  d_i = x_i - m is one fp32 subtract.
+ *                   e_i = fast_exp(d_i), the fast_exp that NDArray.exp uses: exp(0) == 1 and exp(-Inf) == 0 exactly.
+ *   Row sum         s = sum of e_i: a chain or tree of plain fp32 adds from +0.0f.  Its order depends on (cols, inner) and the
+ *                   kernel form alone; it never depends on outer, on the row's position or on pointer alignment.  The
+ *                   streaming and strided forms keep a running maximum over chunks of 8 elements: when a chunk raises it, the
+ *                   sum so far is multiplied by one fast_exp of the step before the chunk's own chain is added.
+ *   Softmax         y_i = e_i / s, one correctly rounded division.  No reciprocal.
+ *   Log-softmax     y_i = d_i - logf(s).
+ *   Special values  as torch's CPU softmax behaves: a row that holds a NaN or a +Inf, or that is entirely -Inf, comes out NaN in
+ *                   every element; no other row is touched.  A -Inf among finite values gives +0.0f for softmax and -Inf for
+ *                   log-softmax.
+ *   Softmax backward, from the output       dx_i = y_i . (dy_i - sum_j dy_j . y_j)
+ *   Log-softmax backward, from the output   dx_i = dy_i - fast_exp(y_i) . sum_j dy_j
+ *   Backward sums   fixed-order fp32 sums from +0.0f under the same rule as s; every product is rounded on its own.  No float
+ *                   atomics.
+ *   Cross-entropy, index targets   target holds `rows` class indices as fp32 (the library has one element type).
+ *                   loss_rows[r] = logf(s) - d_label: bit for bit -np_softmax_forward(..., NP_LOG_SOFTMAX)[r, label], the same
+ *                   row-statistics code in the same form (a zero loss is +0.0f where the negation would be -0.0f).
+ *   Invalid labels  a label that is not an integer in [0, cols), a NaN included, makes that row's loss NaN and every element of
+ *                   its gradient NaN.  Nothing is read out of bounds and no sticky device error is raised.
+ *   Cross-entropy, probability targets   target is (rows, cols).  loss_r = sum_j t_j . (logf(s) - d_j), summed from +0.0f in
+ *                   ascending j by the lane that owns the elements (the whole row in the short-row form), lanes then joined as
+ *                   for s.  Terms with t_j == 0 are skipped, so a one-hot row over -Inf logits is finite, and a one-hot target
+ *                   gives the same bits as the index form.
+ *   Gradient        when dlogits != NULL: dlogits_i = (p_i - t_i) . scale, one fp32 subtract and then one multiply; p_i is bit
+ *                   for bit what np_softmax_forward returns; t is assumed to sum to 1; for index targets t is the one-hot of
+ *                   the label.
+ *   One launch      loss and gradient come from ONE read of the logits, in one launch (the streaming form reads a row twice).
+ *   Aliasing        outputs may not overlap inputs, with one exception: dx may alias dy (dx == dy).
+ *   Sizes           all size_t.  cols >= 2^31 is refused with a message, never truncated; outer.cols.inner beyond 2^31
+ *                   elements works.
+ *   Determinism     the work runs on the library stream and needs no scratch.  Results are bit-identical from run to run; a
+ *                   row alone gives the same bits as the same row inside a larger outer.
+ *   Alignment       any 4-byte-aligned pointer is accepted and gives the same bits as a 16-byte-aligned one.
+ * Convention as above: pointers are checked first, then the extents, the mode, the aliasing, then work begins.  NP_ERR_INVALID
+ * before any device work: a null pointer (dlogits may be NULL), a zero extent, an unknown mode or target kind, cols at 2^31 or
+ * more, overlapping operands. */
+typedef enum np_softmax_mode { NP_SOFTMAX = 0, NP_LOG_SOFTMAX = 1 } np_softmax_mode;
+typedef enum np_xent_target { NP_XENT_INDEX = 0, NP_XENT_PROB = 1 } np_xent_target;
+int np_softmax_forward(const float *x, size_t outer, size_t cols, size_t inner, int mode, float *y);
+int np_softmax_backward(const float *y, const float *dy, size_t outer, size_t cols, size_t inner, int mode, float *dx);
+int np_cross_entropy(const float *logits, const float *target, size_t rows, size_t cols, int target_kind, float scale,
+                     float *loss_rows, float *dlogits /* may be NULL */);
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

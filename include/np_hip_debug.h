@@ -164,6 +164,16 @@ int np_debug_pool_last_path(int *forward_form, int *backward_form);
 /* testing / A-B: form = 1 sends every shape through the direct forward form, form = 0 (the default) chooses by the extents.
  * The two forms return the same bits.  Process-global. */
 int np_debug_pool_forward_form(int form);
+/* tests / tools: the kernel form the last np_softmax_forward, np_softmax_backward or np_cross_entropy of the process launched:
+ * 1 = short rows (slabs of whole rows through LDS), 2 = a wave per row, 3 = a workgroup per row, 4 = streaming (two reads),
+ * 5 = strided (inner > 1, a lane per column).  0 before any launch; NP_ERR_INVALID on a null pointer.  A plain process global. */
+int np_debug_softmax_last_path(int *form);
+/* testing / A-B: form = 1 .. 5 sends every call through that form, -1 (the default) chooses by (cols, inner).  A call whose shape
+ * the forced form cannot serve is refused (NP_ERR_INVALID) before any device work.  Process-global. */
+int np_debug_softmax_force_form(int form);
+/* the boundaries, n >= 5: bounds[0 .. 2] = the largest cols of the short, wave and workgroup forms, bounds[3] = the words of
+ * one staged slab, bounds[4] = the most rows a slab holds (rows per slab = min(bounds[4], bounds[3] / (cols | 1))) */
+int np_debug_softmax_bounds(size_t bounds[], int n);
 /* tests / tools: which kernel families the last np_reduce_axis or np_reduce_all(_dev) call of the process launched, the calls it
  * makes on its own partials included: the OR of the NP_REDUCE_PATH_ bits below (0 = none yet).  A plain process global, cleared
  * at the top of those entry points; calls the library makes itself (split-K GEMM folds, chain partials) overwrite it too. */

@@ -416,6 +416,18 @@ NDArray **NDArrayDNN_Conv2D_LayerBackward(NDArray *input, NDArray *out, NDArray 
  * than the padded input, a gradient of the wrong shape, operands on different devices, and CPU operands. */
 NDArray *NDArrayDNN_Pool2D_Forward(NDArray *x, const int *kernel, const int *stride, const int *padding, char mode);
 NDArray *NDArrayDNN_Pool2D_Backward(NDArray *x, NDArray *dy, const int *kernel, const int *stride, const int *padding, char mode);
+/* Softmax, log-softmax and cross-entropy (host/numpower_dnn.cpp; the reference has none): GPU operands of any ndim >= 1, the
+ * softmax along `axis` (negative axes count from the end); mode 's' softmax, 'l' log-softmax.  _Backward works from the forward
+ * OUTPUT y and its gradient dy.  NDArrayDNN_CrossEntropy takes logits (rows, classes) and a target of (rows) class indices
+ * stored as fp32 or (rows, classes) probabilities; reduction 'n' none ((rows) losses), 's' sum, 'm' mean (0-dimensional
+ * results); with_grad: *dlogits receives (softmax - target) . scale, scale = 1 / rows for the mean and 1 otherwise, from the same
+ * launch.  An invalid label gives NaN for its row alone.  Views are made contiguous; NPH_Softmax_Forward / _Backward and
+ * NPH_CrossEntropy over np_softmax_forward / _backward and np_cross_entropy do the work.  Errors (ext/hip_dnn.h,
+ * NPH_SOFTMAX_MSG_*, NPH_XENT_MSG_*): an unknown mode, an axis out of range, a gradient of another shape, logits that are not
+ * 2-dimensional, a target of neither shape, an unknown reduction, operands on different devices, and CPU operands. */
+NDArray *NDArrayDNN_Softmax_Forward(NDArray *x, int axis, char mode);
+NDArray *NDArrayDNN_Softmax_Backward(NDArray *y, NDArray *dy, int axis, char mode);
+NDArray *NDArrayDNN_CrossEntropy(NDArray *logits, NDArray *target, char reduction, int with_grad, NDArray **dlogits);
 
 #ifdef __cplusplus
 }

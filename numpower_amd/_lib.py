@@ -160,6 +160,9 @@ PROTOTYPES = {
     "np_pool2d_shape": (C.c_int, [C.c_size_t] * 8 + [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "np_pool2d_forward": (C.c_int, [_f32p] + [C.c_size_t] * 9 + [C.c_int, _f32p, C.c_void_p]),
     "np_pool2d_backward": (C.c_int, [_f32p, C.c_void_p] + [C.c_size_t] * 9 + [C.c_int, _f32p]),
+    "np_softmax_forward": (C.c_int, [_f32p] + [C.c_size_t] * 3 + [C.c_int, _f32p]),
+    "np_softmax_backward": (C.c_int, [_f32p, _f32p] + [C.c_size_t] * 3 + [C.c_int, _f32p]),
+    "np_cross_entropy": (C.c_int, [_f32p, _f32p] + [C.c_size_t] * 2 + [C.c_int, C.c_float, _f32p, _f32p]),
     "np_permute": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "np_strided_copy": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "np_identity": (C.c_int, [_f32p, C.c_size_t]),
@@ -194,6 +197,9 @@ PROTOTYPES = {
     "np_debug_dnn_last_epilogue": (C.c_int, [C.POINTER(C.c_int)] * 3),
     "np_debug_pool_last_path": (C.c_int, [C.POINTER(C.c_int)] * 2),
     "np_debug_pool_forward_form": (C.c_int, [C.c_int]),
+    "np_debug_softmax_last_path": (C.c_int, [C.POINTER(C.c_int)]),
+    "np_debug_softmax_force_form": (C.c_int, [C.c_int]),
+    "np_debug_softmax_bounds": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
     "np_debug_reduce_last_path": (C.c_int, [C.POINTER(C.c_uint)]),
     "np_debug_chain_reduce_last_path": (C.c_int, [C.POINTER(C.c_uint)]),
     "np_clear_device_error": (C.c_int, [C.POINTER(C.c_uint)]),

@@ -101,4 +101,25 @@ NDArray *NDArrayDNN_Pool2D_Backward(NDArray *x, NDArray *dy, const int *kernel, 
                          dy);
 }
 
+// Softmax, log-softmax and cross-entropy (np_softmax_forward / _backward, np_cross_entropy), which the reference
+// does not have either.  mode 's' softmax, 'l' log-softmax; reduction 'n', 's', 'm'.
+NDArray *NDArrayDNN_Softmax_Forward(NDArray *x, int axis, char mode) {
+    if (!x) return nullptr;
+    return on_contiguous([=](NDArray *cx, NDArray *, NDArray *, NDArray *) { return NPH_Softmax_Forward(cx, axis, mode); }, x, nullptr);
+}
+
+// dx for y = the forward result and dy = its gradient
+NDArray *NDArrayDNN_Softmax_Backward(NDArray *y, NDArray *dy, int axis, char mode) {
+    if (!y || !dy) return nullptr;
+    return on_contiguous([=](NDArray *cy, NDArray *cg, NDArray *, NDArray *) { return NPH_Softmax_Backward(cy, cg, axis, mode); }, y, dy);
+}
+
+// the loss ((rows), or 0-dimensional); *dlogits: a new array when with_grad, nullptr after an error
+NDArray *NDArrayDNN_CrossEntropy(NDArray *logits, NDArray *target, char reduction, int with_grad, NDArray **dlogits) {
+    if (dlogits) *dlogits = nullptr;
+    if (!logits || !target) return nullptr;
+    return on_contiguous([=](NDArray *cl, NDArray *ct, NDArray *, NDArray *) { return NPH_CrossEntropy(cl, ct, reduction, with_grad, dlogits); },
+                         logits, target);
+}
+
 }  // extern "C"

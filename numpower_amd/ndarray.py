@@ -161,6 +161,9 @@ def _load_host():
     sig["NDArrayDNN_Conv2D_LayerBackward"] = (C.POINTER(_P), [_P, _P, _P, _P, ip, ip, ip, C.c_char, C.c_int])
     sig["NDArrayDNN_Pool2D_Forward"] = (_P, [_P, ip, ip, ip, C.c_char])
     sig["NDArrayDNN_Pool2D_Backward"] = (_P, [_P, _P, ip, ip, ip, C.c_char])
+    sig["NDArrayDNN_Softmax_Forward"] = (_P, [_P, C.c_int, C.c_char])
+    sig["NDArrayDNN_Softmax_Backward"] = (_P, [_P, _P, C.c_int, C.c_char])
+    sig["NDArrayDNN_CrossEntropy"] = (_P, [_P, _P, C.c_char, C.c_int, C.POINTER(_P)])
     sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
     sig["NDArray_Eig"] = (C.POINTER(_P), [_P])
     sig["NDArray_Qr"] = (C.POINTER(_P), [_P])
@@ -978,6 +981,57 @@ class NDArray:
         a, _ = NDArray._coerce(x)
         g, _ = NDArray._coerce(dy)
         return NDArray._wrap(h.NDArrayDNN_Pool2D_Backward(a._p, g._p, k, s, p, code))
+
+    @staticmethod
+    def _softmax_axis(axis, who):
+        if not isinstance(axis, (int, np.integer)) or isinstance(axis, bool):
+            raise Error("%s: axis must be an int" % who)
+        return int(axis)
+
+    @staticmethod
+    def softmax(a, axis=-1):      # the reference has no softmax
+        """softmax of a GPU array along `axis` (any ndim >= 1, negative axes count from the end):
+        exp(x - max) / sum, one read and one write, a correctly rounded division.  A row with a NaN, a +Inf, or nothing but
+        -Inf is NaN throughout; a -Inf among finite values gives +0."""
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        return NDArray._wrap(h.NDArrayDNN_Softmax_Forward(x._p, NDArray._softmax_axis(axis, "softmax"), b"s"))
+
+    @staticmethod
+    def log_softmax(a, axis=-1):
+        """(x - max) - log(sum exp(x - max)) along `axis`: finite where log(softmax(x)) is -Inf or NaN."""
+        h = _load_host()
+        x, _ = NDArray._coerce(a)
+        return NDArray._wrap(h.NDArrayDNN_Softmax_Forward(x._p, NDArray._softmax_axis(axis, "log_softmax"), b"l"))
+
+    @staticmethod
+    def softmax_backward(y, dy, axis=-1, log=False):
+        """dx for y = softmax(x, axis) (log=False: y . (dy - sum(dy . y))) or y = log_softmax(x, axis) (log=True:
+        dy - exp(y) . sum(dy)): from the forward OUTPUT, fixed-order sums, bit-identical from run to run."""
+        h = _load_host()
+        out, _ = NDArray._coerce(y)
+        g, _ = NDArray._coerce(dy)
+        return NDArray._wrap(h.NDArrayDNN_Softmax_Backward(out._p, g._p, NDArray._softmax_axis(axis, "softmax_backward"), b"l" if log else b"s"))
+
+    _DNN_XENT_REDUCTIONS = {"none": b"n", "sum": b"s", "mean": b"m"}
+
+    @staticmethod
+    def dnn_cross_entropy(logits, target, reduction="mean", with_grad=False):
+        """The cross-entropy of logits (rows, classes) against a target of (rows) class indices (stored as fp32) or
+        (rows, classes) probabilities, computed from the logits: log(sum exp(l - max)) - (l - max)[label], finite where
+        -log(softmax) overflows.  reduction 'none' returns the (rows) losses, 'sum' and 'mean' a float.  with_grad=True returns
+        (loss, dlogits) with dlogits = (softmax(logits) - target) . scale from the same launch, scale = 1 / rows for 'mean' and 1
+        otherwise.  A label that is not an integer in [0, classes) gives NaN for its row's loss and gradient."""
+        h = _load_host()
+        if not isinstance(reduction, str) or reduction not in NDArray._DNN_XENT_REDUCTIONS:
+            raise Error("dnn_cross_entropy: reduction must be 'none', 'sum' or 'mean', not %r" % (reduction,))
+        l, _ = NDArray._coerce(logits)
+        t, _ = NDArray._coerce(target)
+        grad = _P()
+        loss = h.NDArrayDNN_CrossEntropy(l._p, t._p, NDArray._DNN_XENT_REDUCTIONS[reduction], 1 if with_grad else 0,
+                                         C.byref(grad) if with_grad else None)
+        loss = NDArray._wrap(loss)
+        return (loss, NDArray._wrap(grad)) if with_grad else loss
 
     def copy(self):          # PHP_METHOD copy: NDArray_Copy on the array's own device
         return NDArray._wrap(_load_host().NDArray_Copy(self._p, C.cast(self._p, _P).contents.device))

@@ -29,11 +29,18 @@ Each operation alternates, round by round in one session, with the library's flo
 number of bytes, read plus written: 4 (numel(x) + numel(y)), plus 4 numel(y) where an idx is written or read.  Reported: ms, achieved
 TB/s and the ratio copy / pool (1.00 = the copy's rate, the platform ceiling for streaming kernels), medians of the rounds.  The
 operand sets are rotated (--sets) so that together they pass the 256 MiB Infinity Cache.  Writes profiles/dnn/pool2d_sweep.log.
+--softmax is the leg of softmax, log-softmax, their backward passes and the cross-entropy with its gradient (np_softmax.hip), on
+shapes that reach every kernel form (SOFTMAX_SHAPES).  Each operation alternates, round by round in one session, with the float4
+copy of the SAME bytes (8 per element forward, 12 backward, 8 plus the labels and the losses for the cross-entropy) and, for the row
+shapes, with the four-pass composition examples/softmax_regression.py uses (max, two fused chains, the loss chain), which is how the
+library computed a softmax loss before.  Reported: ms, TB/s, copy / op (1.00 = the copy's rate, the ceiling of a form that reads a row
+once and writes it once) and composition / op.  The log is stamped with the sources it ran on.  Writes profiles/dnn/softmax_sweep.log.
 
 Usage: python tools/dnn_sweep.py [--layers 0,1,...] [--rounds N] [--limit S] [--torch] [--out FILE]
        python tools/dnn_sweep.py --act [--layers ...]         the bias / activation leg
        python tools/dnn_sweep.py --forward-only [--layers ...]
        python tools/dnn_sweep.py --pool [--layers ...]        the pooling leg
+       python tools/dnn_sweep.py --softmax [--layers ...]     the softmax / cross-entropy leg
        python tools/dnn_sweep.py --profile LAYER     three calls of each operation and nothing else, for a run under the kernel profiler"""
 import argparse
 import statistics
@@ -65,8 +72,13 @@ POOL_LAYERS = [("2x2/2 64 ch at 112^2, batch 32", (32, 64, 112, 112), (2, 2), (2
                ("3x3/1 pad 1 256 ch at 28^2, batch 32", (32, 256, 28, 28), (3, 3), (1, 1), (1, 1), ("max", "avg"))]
 POOL_MODE = {"max": 0, "avg": 1, "avg_valid": 2}
 
+# name, (outer, cols, inner)
+SOFTMAX_SHAPES = [("10^7 x 10", (10 ** 7, 10, 1)), ("200000 x 10", (200000, 10, 1)), ("65536 x 1000", (65536, 1000, 1)),
+                  ("8192 x 32768", (8192, 32768, 1)), ("64 x 10^6", (64, 10 ** 6, 1)), ("NCHW channels (64, 21, 128, 128)", (64, 21, 128 * 128))]
+
 ap = argparse.ArgumentParser()
 ap.add_argument("--pool", action="store_true")
+ap.add_argument("--softmax", action="store_true")
 ap.add_argument("--sets", type=int, default=0, help="--pool: operand sets to rotate through (0: enough to pass 256 MiB)")
 ap.add_argument("--layers", default=None)
 ap.add_argument("--rounds", type=int, default=5)
@@ -79,9 +91,9 @@ ap.add_argument("--profile", type=int, default=None)
 ap.add_argument("--child", default=None, help="internal: 'layer:<i>' or 'torch'")
 args = ap.parse_args()
 if args.layers is None:
-    args.layers = ",".join(str(i) for i in range(len(POOL_LAYERS if args.pool else LAYERS)))
+    args.layers = ",".join(str(i) for i in range(len(SOFTMAX_SHAPES if args.softmax else POOL_LAYERS if args.pool else LAYERS)))
 if args.out is None:
-    args.out = str(ROOT / "profiles" / "dnn" / ("pool2d_sweep.log" if args.pool else "conv2d_act_sweep.log" if args.act else
+    args.out = str(ROOT / "profiles" / "dnn" / ("softmax_sweep.log" if args.softmax else "pool2d_sweep.log" if args.pool else "conv2d_act_sweep.log" if args.act else
                                                "conv2d_forward_only.log" if args.forward_only else "conv2d_sweep.log"))
 LARGE = (256, 128, 3136)                        # (N, F, P) of the large case of --act: 1.03e8 elements
 HBM_TBS = 8.0
@@ -364,6 +376,105 @@ def run_pool(i, rounds, sets):
                      min(c / p for c, p in zip(copy_ms, pool_ms)), max(c / p for c, p in zip(copy_ms, pool_ms))), flush=True)
 
 
+def run_softmax(i, rounds, sets):
+    """one shape: every operation alternates with a float4 copy of the same bytes and (row shapes) with the four-pass composition"""
+    import ctypes as C_
+    import numpy as np
+    D, lib, check, ramp, _ = _setup()
+    from numpower_amd._lib import Timer
+    t = Timer()
+    name, (outer, cols, inner) = SOFTMAX_SHAPES[i]
+    n = outer * cols * inner
+    if sets < 1:
+        sets = max(2, -(-(256 << 20) // (4 * n)) + 1)
+    rng = np.random.default_rng(i)
+    block = rng.standard_normal(1 << 20).astype(np.float32)
+    host = np.resize(block, n)
+    labels = rng.integers(0, cols, outer).astype(np.float32)
+    xs = [D.DeviceArray.from_host(host) for _ in range(sets)]
+    ys, dys, dxs = ([D.DeviceArray((n,)) for _ in range(sets)] for _ in range(3))
+    for d in dys:
+        check(lib.np_memcpy_d2d(d.ptr, xs[0].ptr, 4 * n))
+    cs, cd = [D.DeviceArray((3 * n // 2 + 16,)) for _ in range(sets)], [D.DeviceArray((3 * n // 2 + 16,)) for _ in range(sets)]      # the copy's own operands
+    for c in cs:
+        check(lib.np_memset0(c.ptr, 4 * (3 * n // 2 + 16)))
+    tg, losses = D.DeviceArray.from_host(labels), D.DeviceArray((outer,))
+    dims = (outer, cols, inner)
+    ramp()
+    turn = [0]
+
+    def rotating(fn):
+        def call():
+            turn[0] = (turn[0] + 1) % sets
+            fn(turn[0])
+        return call
+
+    def copy_of(total_bytes):
+        half = total_bytes // 2 // 16 * 16        # a copy of B / 2 bytes reads B / 2 and writes B / 2
+        return rotating(lambda k: check(lib.np_memcpy_d2d(cd[k].ptr, cs[k].ptr, half)))
+
+    def timed(fn, reps):
+        t.start()
+        for _ in range(reps):
+            fn()
+        t.stop()
+        return t.elapsed_ms() / reps
+
+    composition = None
+    if inner == 1:                                # what examples/softmax_regression.py does per step for its loss: four passes over (rows, cols)
+        from numpower_amd.lazy import Lazy  # noqa: F401  (installs NDArray.lazy)
+        from numpower_amd.ndarray import NDArray as nd
+        logits = nd.array(host.reshape(outer, cols)).gpu()
+        onehot = np.zeros((outer, cols), np.float32)
+        onehot[np.arange(outer), labels.astype(np.int64)] = 1.0
+        gY = nd.array(onehot).gpu()
+        del onehot
+
+        def composition():
+            row_max = nd.reshape(nd.max(logits, 1), [outer, 1])
+            row_sum = nd.reshape((logits.lazy() - row_max).exp().sum(axis=1), [outer, 1])
+            P = ((logits.lazy() - row_max).exp() / row_sum).eval()
+            return -(P.lazy().log() * gY).sum() / outer
+
+    for k in range(sets):                         # the backward passes read an output of the forward pass
+        check(lib.np_softmax_forward(xs[k].ptr, *dims, 0, ys[k].ptr))
+    ops = [("softmax", rotating(lambda k: check(lib.np_softmax_forward(xs[k].ptr, *dims, 0, ys[k].ptr))), 8 * n, False),
+           ("log-softmax", rotating(lambda k: check(lib.np_softmax_forward(xs[k].ptr, *dims, 1, dxs[k].ptr))), 8 * n, False),
+           ("softmax backward", rotating(lambda k: check(lib.np_softmax_backward(ys[k].ptr, dys[k].ptr, *dims, 0, dxs[k].ptr))), 12 * n, False),
+           ("log-softmax backward", rotating(lambda k: check(lib.np_softmax_backward(ys[k].ptr, dys[k].ptr, *dims, 1, dxs[k].ptr))), 12 * n, False)]
+    if inner == 1:
+        ops.append(("cross-entropy + gradient", rotating(lambda k: check(lib.np_cross_entropy(xs[k].ptr, tg.ptr, outer, cols, 0, 1.0 / outer, losses.ptr, dxs[k].ptr))),
+                    8 * n + 8 * outer, True))
+        ops.append(("cross-entropy, loss alone", rotating(lambda k: check(lib.np_cross_entropy(xs[k].ptr, tg.ptr, outer, cols, 0, 1.0, losses.ptr, None))),
+                    4 * n + 8 * outer, True))
+    for label, fn, nbytes, against in ops:
+        copy = copy_of(nbytes)
+        for f in (fn, copy):                      # warm
+            for _ in range(3):
+                f()
+        D.sync()
+        t0 = time.time()
+        fn()
+        D.sync()
+        reps = max(5, min(200, int(0.05 / max(time.time() - t0, 1e-5))))
+        op_ms, copy_ms, comp_ms = [], [], []
+        for _ in range(rounds):                   # alternating in one session
+            op_ms.append(timed(fn, reps))
+            copy_ms.append(timed(copy, reps))
+            if against and composition is not None:
+                comp_ms.append(timed(composition, max(2, reps // 8)))
+        om, cm = statistics.median(op_ms), statistics.median(copy_ms)
+        form = C_.c_int()
+        check(lib.np_debug_softmax_last_path(C_.byref(form)))
+        tail = ""
+        if comp_ms:
+            pm = statistics.median(comp_ms)
+            tail = "   composition %9.4f ms   composition / op %6.2f" % (pm, pm / om)
+        print("%-34s %-26s form %d %8.1f MB %9.4f ms %5.2f TB/s   copy %9.4f ms %5.2f TB/s   copy / op %5.2f   (min %5.2f max %5.2f)%s"
+              % (name, label, form.value, nbytes * 1e-6, om, nbytes / om * 1e-9, cm, nbytes / cm * 1e-9, cm / om,
+                 min(c / p for c, p in zip(copy_ms, op_ms)), max(c / p for c, p in zip(copy_ms, op_ms)), tail), flush=True)
+
+
 def run_torch(layers, rounds):
     import torch
     if not torch.cuda.is_available():
@@ -408,6 +519,8 @@ if args.child:
         run_act(args.child.split(":")[1], args.rounds)
     elif args.child.startswith("pool:"):
         run_pool(int(args.child.split(":")[1]), args.rounds, args.sets)
+    elif args.child.startswith("softmax:"):
+        run_softmax(int(args.child.split(":")[1]), args.rounds, args.sets)
     elif args.child.startswith("fwd:"):
         run_forward_only(int(args.child.split(":")[1]), args.rounds)
     else:
@@ -437,8 +550,15 @@ def child(what):
     return proc.returncode == 0
 
 
-kind = "pool" if args.pool else "act" if args.act else "fwd" if args.forward_only else "layer"
-if args.pool:
+kind = "softmax" if args.softmax else "pool" if args.pool else "act" if args.act else "fwd" if args.forward_only else "layer"
+if args.softmax:
+    import hashlib
+    say("np_softmax_forward / np_softmax_backward / np_cross_entropy (form of the launch: 1 short rows, 2 a wave per row, 3 a workgroup per row, 4 streaming, 5 strided) "
+        "against np_memcpy_d2d (the float4 copy) of the same bytes read + written and against the four-pass composition of examples/softmax_regression.py, "
+        "alternating round by round; fp32, ms per call, medians of %d rounds" % args.rounds)
+    say("sources: " + ", ".join("%s sha256 %s" % (f, hashlib.sha256((ROOT / "numpower_amd" / "csrc" / f).read_bytes()).hexdigest()[:16])
+                                for f in ("np_softmax.hip", "np_elementwise_ops.h", "np_internal.h")))
+elif args.pool:
     say("np_pool2d_forward / np_pool2d_backward (forms of the last forward and backward launch: forward 1 direct, 2 staged; backward 1 gather) against np_memcpy_d2d (the float4 copy) of the same "
         "bytes read + written, alternating round by round; fp32, ms per call, medians of %d rounds" % args.rounds)
 elif args.act:
