@@ -104,7 +104,13 @@ int np_sgemm_debug_plan_unaligned(size_t M, size_t N, size_t K, int cus, double 
  * registers; 12000 + k / 14000 + k: first-axis chains on k workgroups per CU, compiled ones with 2 / 4 rows in flight.  Any non-zero code also
  * keeps FULL (op) ROW off the 2-D form. */
 int np_elementwise_set_variant(int variant);
-int np_layout_set_variant(int variant);   /* transpose tile: 0 = default, 64, 128; 1 = default tiles without the write-aligned form for output rows off the 128-byte grid */
+/* A/B switches of np_layout.hip, same bits either way.  Plain codes (one value, 0 = default): 64 / 128 force the transpose tile (and keep
+ * the interleave, skinny, write-aligned and plane kernels off), 1 = default tiles without the write-aligned form for output rows off
+ * the 128-byte grid, 3 / 4 = np_permute without the plane path, 5 = no interleave, 6 = the plane path on single floats only, 7 =
+ * write-aligned tiles of 64 always.  Separate values: 7000 + N = write-aligned transposes below N tiles of 128 take tiles of 64
+ * (default 1200, 0 = never); 17000 + k = the write-aligned tile order k = 0 / 1 / 2, 17003 = by size; 17010 + k = the tile kernel's
+ * order, 17013 = default; 17020 + k = the plane kernel's, 17023 = default.  Everything back: 0, 8200, 17003, 17013, 17023. */
+int np_layout_set_variant(int variant);
 int np_select_set_variant(int variant);   /* order statistics: 0 = plain three passes only (no bracket path, no one-workgroup kernel), 1 = default (n >= 2^26), else the smallest n that takes it */
 int np_select_last_path(int *path);       /* tests / tools: 1 if the last selection ran over the bracket's copied keys, 0 if over the array, 2 if in the one-workgroup kernel (synchronises) */
 int np_reduce_set_variant(int variant);   /* streaming reductions, first pass: workgroups per CU (0 = default) */
@@ -287,6 +293,38 @@ int np_sgemm_debug_last_launches(unsigned *host_records, unsigned capacity, unsi
  * the LU and the Cholesky, on its own: one launch of the subtracting 128 x 128 tile kernel on the library stream.  Checked like
  * np_sgemm_debug_ld; clears and fills the two probes above like a product call (the mask reads 0: no np_sgemm path ran). */
 int np_sgemm_debug_sub_ld(size_t M, size_t N, size_t K, const float *A, size_t lda, const float *B, size_t ldb, float *C, size_t ldc);
+/* tests / tools: what the last np_transpose2d, np_permute, np_strided_copy or np_copy2d call of the process launched: ONE record of
+ * NP_LAYOUT_RECORD_WORDS unsigned words for the kernel (or device copy) that finally ran.  Cleared at the top of each of those entry
+ * points, so np_permute handing its fused shape to np_transpose2d leaves the record of the transpose kernel alone; *host_count = the
+ * launches noted since the record was cleared (0: none yet, or a call that had nothing to move; else 1).  `capacity` counts records:
+ * min(count, capacity) records are written.  Host stores at the launch sites: no device work, no synchronisation; plain process
+ * globals, meaningful only while one thread calls the layout entry points.  A record:
+ *   word 0      NP_LAYOUT_FAMILY: NP_LAYOUT_PATH_*
+ *   word 1      NP_LAYOUT_FORM: the template arguments — INTERLEAVE: R | TO_INTERLEAVED << 8; SKINNY: TALL; TILE: tile | VEC << 8;
+ *               WALIGN: tile; PLANE: W; GATHER: index bits (32 / 64) | W << 8; COPY2D: V; MEMCPY: 0
+ *   word 2      NP_LAYOUT_ORDER: the tile order as passed to the kernel (TILE 0 / 1, WALIGN 0 / 1 / 2, PLANE its xcd_runs; else 0)
+ *   words 3-5   NP_LAYOUT_GRID_X / _Y / _Z: the grid (0, 0, 0 for MEMCPY)
+ *   words 6-14  by family, 0 where unused — TILE and WALIGN: tiles_x, tiles_y, in_pitch, out_pitch (floats, low 32 bits), nbatch
+ *               (batch axes in the PlaneBatch); PLANE: A, B, E, ta, tb, tiles_a, tiles_b, pitch, xcd_runs as the kernel sees them
+ *               (float4 units where W = 4) */
+#define NP_LAYOUT_RECORD_WORDS 16u
+#define NP_LAYOUT_FAMILY 0
+#define NP_LAYOUT_FORM 1
+#define NP_LAYOUT_ORDER 2
+#define NP_LAYOUT_GRID_X 3
+#define NP_LAYOUT_GRID_Y 4
+#define NP_LAYOUT_GRID_Z 5
+#define NP_LAYOUT_EXTRA 6
+#define NP_LAYOUT_PATH_NONE 0u
+#define NP_LAYOUT_PATH_MEMCPY 1u       /* np_memcpy_d2d: identity after fusion, contiguous strides, unpitched np_copy2d */
+#define NP_LAYOUT_PATH_INTERLEAVE 2u   /* interleave_kernel<R, TO_INTERLEAVED> */
+#define NP_LAYOUT_PATH_SKINNY 3u       /* transpose_skinny_kernel<TALL> */
+#define NP_LAYOUT_PATH_TILE 4u         /* transpose_tile_kernel<T, T, VEC> */
+#define NP_LAYOUT_PATH_WALIGN 5u       /* transpose_walign_kernel<T, T> */
+#define NP_LAYOUT_PATH_PLANE 6u        /* permute_plane_kernel<W> */
+#define NP_LAYOUT_PATH_GATHER 7u       /* permute_gather_kernel<I, W> */
+#define NP_LAYOUT_PATH_COPY2D 8u       /* copy2d_kernel<V> */
+int np_debug_layout_last_record(unsigned *host_record, unsigned capacity, unsigned *host_count);
 
 #ifdef __cplusplus
 }

@@ -178,6 +178,7 @@ PROTOTYPES = {
     "np_sgemm_debug_sub_ld": (C.c_int, [C.c_size_t] * 3 + [_f32p, C.c_size_t, _f32p, C.c_size_t, _f32p, C.c_size_t]),
     "np_elementwise_set_variant": (C.c_int, [C.c_int]),
     "np_layout_set_variant": (C.c_int, [C.c_int]),
+    "np_debug_layout_last_record": (C.c_int, [C.POINTER(C.c_uint), C.c_uint, C.POINTER(C.c_uint)]),
     "np_reduce_set_variant": (C.c_int, [C.c_int]),
     "np_select_set_variant": (C.c_int, [C.c_int]),
     "np_runtime_set_variant": (C.c_int, [C.c_int]),

@@ -13,6 +13,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <type_traits>
 #include <vector>
 
@@ -24,6 +25,32 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // a float4 that is only 4-byte aligned: global_load/store_dwordx4 take dword-aligned addresses, which
 // is all a row of odd length offers
 struct __attribute__((packed, aligned(4))) U4 { v4f v; };
+
+// np_debug_layout_last_record: the NP_LAYOUT_* record (np_hip_debug.h) of what the last np_transpose2d / np_permute / np_strided_copy /
+// np_copy2d call launched; cleared at the top of those entry points, one host store per launch site.
+unsigned g_layout_record[NP_LAYOUT_RECORD_WORDS];
+unsigned g_layout_count = 0;
+void layout_clear() {
+    memset(g_layout_record, 0, sizeof g_layout_record);
+    g_layout_count = 0;
+}
+void layout_note(unsigned family, unsigned form, unsigned order, dim3 grid, std::initializer_list<size_t> extra) {
+    memset(g_layout_record, 0, sizeof g_layout_record);
+    g_layout_record[NP_LAYOUT_FAMILY] = family;
+    g_layout_record[NP_LAYOUT_FORM] = form;
+    g_layout_record[NP_LAYOUT_ORDER] = order;
+    g_layout_record[NP_LAYOUT_GRID_X] = grid.x;
+    g_layout_record[NP_LAYOUT_GRID_Y] = grid.y;
+    g_layout_record[NP_LAYOUT_GRID_Z] = grid.z;
+    unsigned w = NP_LAYOUT_EXTRA;
+    for (size_t v : extra)
+        if (w < NP_LAYOUT_RECORD_WORDS) g_layout_record[w++] = (unsigned)v;
+    ++g_layout_count;
+}
+int layout_memcpy(float *out, const float *in, size_t bytes) {
+    layout_note(NP_LAYOUT_PATH_MEMCPY, 0, 0, dim3(0, 0, 0), {});
+    return np_memcpy_d2d(out, in, bytes);
+}
 
 constexpr int MAX_ND = 8;
 // Where a plane sits: rows `in_pitch` floats apart in the input, output rows `out_pitch` apart; blockIdx.z runs over the
@@ -332,6 +359,7 @@ template <bool TO_INTERLEAVED>
 int launch_interleave(const float *in, float *out, size_t batch, unsigned R, size_t n) {
     const dim3 grid((unsigned)((n + 2047) / 2048), (unsigned)batch);
     hipStream_t s = np::stream();
+    layout_note(NP_LAYOUT_PATH_INTERLEAVE, R | (TO_INTERLEAVED ? 1u : 0u) << 8, 0, grid, {});
     switch (R) {
         case 2: interleave_kernel<2, TO_INTERLEAVED><<<grid, 256, 0, s>>>(in, out, (unsigned)n); break;
         case 3: interleave_kernel<3, TO_INTERLEAVED><<<grid, 256, 0, s>>>(in, out, (unsigned)n); break;
@@ -390,6 +418,7 @@ int launch_gather(const float *in, float *out, size_t n, PermuteArgs a) {
     const size_t cap = (size_t)np::num_cus() * 16;
     if (blocks > cap) blocks = cap;
     hipStream_t s = np::stream();
+    layout_note(NP_LAYOUT_PATH_GATHER, (n < (size_t(1) << 31) ? 32u : 64u) | (vec4 ? 4u : 1u) << 8, 0, dim3((unsigned)blocks), {});
     if (n < (size_t(1) << 31)) {
         if (vec4)
             permute_gather_kernel<uint32_t, 4><<<(unsigned)blocks, 256, 0, s>>>(in, out, (uint32_t)n, a);
@@ -582,6 +611,7 @@ int launch_transpose(const float *in, float *out, size_t batch, size_t rows, siz
     //  4.24 -> 4.35 TB/s, 4096 x 4099 5.12 -> 4.49, 8192 x 10001 / 16000 x 5001 / 3200 x 30001 -1 %, profiles/r06/tile_order_ab.log —
     //  so the launch order stays; np_layout_set_variant(17011) forces the runs for A/B)
     const unsigned order = g_tile_order > 0 ? 1u : 0u;
+    layout_note(NP_LAYOUT_PATH_TILE, (unsigned)TR | (vec ? 1u : 0u) << 8, order, grid, {tiles_x, tiles_y, pb.in_pitch, pb.out_pitch, pb.nbatch});
     if (vec)
         transpose_tile_kernel<TR, TC, true><<<grid, 256, lds, np::stream()>>>(in, out, (unsigned)rows, (unsigned)cols,
                                                                              (unsigned)tiles_x, (unsigned)tiles_y, pb, order);
@@ -640,8 +670,11 @@ int transpose_planes(const float *in, float *out, size_t batch, size_t rows, siz
         const size_t tiles_x = (cols + 63) / 64, tiles_y = (rows + 31 + 63) / 64;
         if (tiles_x * tiles_y <= 0x7fffffffu) {
             constexpr size_t lds = (size_t)64 * 66 * sizeof(float);
-            transpose_walign_kernel<64, 64><<<dim3((unsigned)(tiles_x * tiles_y), 1, (unsigned)batch), 256, lds, np::stream()>>>(
-                in, out, (unsigned)rows, (unsigned)cols, (unsigned)tiles_x, (unsigned)tiles_y, pb, walign_order(rows, cols));
+            const dim3 grid((unsigned)(tiles_x * tiles_y), 1, (unsigned)batch);
+            const unsigned order = walign_order(rows, cols);
+            layout_note(NP_LAYOUT_PATH_WALIGN, 64, order, grid, {tiles_x, tiles_y, pb.in_pitch, pb.out_pitch, pb.nbatch});
+            transpose_walign_kernel<64, 64><<<grid, 256, lds, np::stream()>>>(
+                in, out, (unsigned)rows, (unsigned)cols, (unsigned)tiles_x, (unsigned)tiles_y, pb, order);
             NP_LAUNCH_CHECK("transpose_walign_kernel");
             return NP_OK;
         }
@@ -657,8 +690,11 @@ int transpose_planes(const float *in, float *out, size_t batch, size_t rows, siz
                 NP_HIP_CHECK(hipFuncSetAttribute((const void *)transpose_walign_kernel<128, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 if (dev >= 0 && dev < 64) attr_set[dev] = true;
             }
-            transpose_walign_kernel<128, 128><<<dim3((unsigned)(tiles_x * tiles_y), 1, (unsigned)batch), 256, lds, np::stream()>>>(
-                in, out, (unsigned)rows, (unsigned)cols, (unsigned)tiles_x, (unsigned)tiles_y, pb, walign_order(rows, cols));
+            const dim3 grid((unsigned)(tiles_x * tiles_y), 1, (unsigned)batch);
+            const unsigned order = walign_order(rows, cols);
+            layout_note(NP_LAYOUT_PATH_WALIGN, 128, order, grid, {tiles_x, tiles_y, pb.in_pitch, pb.out_pitch, pb.nbatch});
+            transpose_walign_kernel<128, 128><<<grid, 256, lds, np::stream()>>>(
+                in, out, (unsigned)rows, (unsigned)cols, (unsigned)tiles_x, (unsigned)tiles_y, pb, order);
             NP_LAUNCH_CHECK("transpose_walign_kernel");
             return NP_OK;
         }
@@ -670,6 +706,14 @@ int transpose_planes(const float *in, float *out, size_t batch, size_t rows, siz
 }  // namespace
 
 extern "C" {
+
+int np_debug_layout_last_record(unsigned *host_record, unsigned capacity, unsigned *host_count) {
+    if (!host_count || (capacity && !host_record)) return np::fail(NP_ERR_INVALID, "np_debug_layout_last_record: null pointer");
+    *host_count = g_layout_count;
+    if (g_layout_count && capacity)
+        for (unsigned w = 0; w < NP_LAYOUT_RECORD_WORDS; ++w) host_record[w] = g_layout_record[w];
+    return NP_OK;
+}
 
 int np_layout_set_variant(int variant) {
     if (variant >= 7000 && variant < 17000) {
@@ -693,6 +737,7 @@ int np_layout_set_variant(int variant) {
 }
 
 int np_transpose2d(const float *in, float *out, size_t batch, size_t rows, size_t cols) {
+    layout_clear();
     if (batch == 0 || rows == 0 || cols == 0) return NP_OK;
     if (!in || !out) return np::fail(NP_ERR_INVALID, "np_transpose2d: null pointer");
     if (in == out) return np::fail(NP_ERR_INVALID, "np_transpose2d: in-place transpose is not supported");
@@ -711,6 +756,7 @@ int np_transpose2d(const float *in, float *out, size_t batch, size_t rows, size_
         const size_t cap = (size_t)np::num_cus() * 32;
         if (blocks > cap) blocks = cap;
         const dim3 grid((unsigned)blocks, (unsigned)batch);
+        layout_note(NP_LAYOUT_PATH_SKINNY, tall ? 1u : 0u, 0, grid, {});
         if (tall)
             transpose_skinny_kernel<true><<<grid, 256, 0, np::stream()>>>(in, out, rows, cols);
         else
@@ -732,6 +778,7 @@ int np_transpose2d(const float *in, float *out, size_t batch, size_t rows, size_
 }
 
 int np_permute(const float *in, float *out, int ndim, const int *host_shape, const int *host_perm) {
+    layout_clear();
     if (ndim < 0 || ndim > MAX_ND) return np::fail(NP_ERR_INVALID, "np_permute: ndim %d not in 0..%d", ndim, MAX_ND);
     if (ndim > 0 && (!host_shape || !host_perm)) return np::fail(NP_ERR_INVALID, "np_permute: null shape/perm");
     size_t n = 1;
@@ -795,7 +842,7 @@ int np_permute(const float *in, float *out, int ndim, const int *host_shape, con
 
     bool identity = true;
     for (int i = 0; i < ndim; ++i) identity = identity && host_perm[i] == i;
-    if (identity) return np_memcpy_d2d(out, in, n * sizeof(float));
+    if (identity) return layout_memcpy(out, in, n * sizeof(float));
     // leading axes untouched, last two swapped -> batched tile transpose
     bool last_two = ndim >= 2 && host_perm[ndim - 1] == ndim - 2 && host_perm[ndim - 2] == ndim - 1;
     for (int i = 0; i + 2 < ndim; ++i) last_two = last_two && host_perm[i] == i;
@@ -910,6 +957,8 @@ int np_permute(const float *in, float *out, int ndim, const int *host_shape, con
                 // reversed 2.79 -> 2.91, 100^4 and (50, 60, 70, 80) unchanged; float4 elements (runs that ARE whole lines) lose 5-20 % that
                 // way and keep the launch order (profiles/r06/plane_order_ab.log)
                 p.xcd_runs = g_plane_order >= 0 ? (unsigned)g_plane_order : (w4 ? 0u : 1u);
+                layout_note(NP_LAYOUT_PATH_PLANE, w4 ? 4u : 1u, p.xcd_runs, dim3((unsigned)blocks),
+                            {p.A, p.B, p.E, p.ta, p.tb, p.tiles_a, p.tiles_b, p.pitch, p.xcd_runs});
                 if (w4)
                     permute_plane_kernel<4><<<(unsigned)blocks, 256, lds, np::stream()>>>(in, out, p);
                 else
@@ -1027,11 +1076,12 @@ int np_arange(float *out, double start, double step, size_t n) {
 }
 
 int np_copy2d(float *dst, size_t dst_pitch, const float *src, size_t src_pitch, size_t width, size_t rows) {
+    layout_clear();
     if (width == 0 || rows == 0) return NP_OK;
     if (!dst || !src) return np::fail(NP_ERR_INVALID, "np_copy2d: null pointer");
     if (dst_pitch < width || src_pitch < width) return np::fail(NP_ERR_INVALID, "np_copy2d: pitch smaller than the row width");
     if (int rc = np::ensure_init()) return rc;
-    if (dst_pitch == width && src_pitch == width) return np_memcpy_d2d(dst, src, rows * width * sizeof(float));
+    if (dst_pitch == width && src_pitch == width) return layout_memcpy(dst, src, rows * width * sizeof(float));
     hipStream_t s = np::stream();
     const bool vec = width % 4 == 0;
     const size_t per_row = vec ? width / 4 : width;
@@ -1040,6 +1090,7 @@ int np_copy2d(float *dst, size_t dst_pitch, const float *src, size_t src_pitch, 
     const size_t cap = (size_t)np::num_cus() * 32;
     if (blocks > cap) blocks = cap;
     if (units >> 32) return np::fail(NP_ERR_INVALID, "np_copy2d: more than 2^32 units");
+    layout_note(NP_LAYOUT_PATH_COPY2D, vec ? 4u : 1u, 0, dim3((unsigned)blocks), {});
     if (vec) copy2d_kernel<4><<<(unsigned)blocks, 256, 0, s>>>(dst, dst_pitch, src, src_pitch, (unsigned)per_row, units);
     else copy2d_kernel<1><<<(unsigned)blocks, 256, 0, s>>>(dst, dst_pitch, src, src_pitch, (unsigned)per_row, units);
     NP_LAUNCH_CHECK("copy2d_kernel");
@@ -1047,6 +1098,7 @@ int np_copy2d(float *dst, size_t dst_pitch, const float *src, size_t src_pitch, 
 }
 
 int np_strided_copy(const float *in, float *out, int ndim, const int *host_shape, const long long *host_strides) {
+    layout_clear();
     if (ndim < 0 || ndim > MAX_ND) return np::fail(NP_ERR_INVALID, "np_strided_copy: ndim %d not in 0..%d", ndim, MAX_ND);
     if (ndim > 0 && (!host_shape || !host_strides)) return np::fail(NP_ERR_INVALID, "np_strided_copy: null shape/strides");
     size_t n = 1;
@@ -1063,7 +1115,7 @@ int np_strided_copy(const float *in, float *out, int ndim, const int *host_shape
         if (host_shape[i] != 1 && host_strides[i] != (long long)expect) contiguous = false;
         expect *= (size_t)host_shape[i];
     }
-    if (contiguous) return np_memcpy_d2d(out, in, n * sizeof(float));
+    if (contiguous) return layout_memcpy(out, in, n * sizeof(float));
     PermuteArgs a;
     a.ndim = (unsigned)ndim;
     for (int i = 0; i < MAX_ND; ++i) {

@@ -74,22 +74,24 @@ def test_transpose_16384x4096(hip):
     del C
 
 
-PERMS = [((30, 3, 64, 65), (0, 2, 3, 1)),        # NCHW -> NHWC: fuses to a batched 3 x 4160 transpose (skinny path)
-         ((30, 64, 65, 3), (0, 3, 1, 2)),        # NHWC -> NCHW
-         ((70, 130, 66), (2, 1, 0)),             # full reversal: LDS-tiled plane transpose, batch = middle axis
-         ((9, 10, 11, 12), (3, 2, 1, 0)),
-         ((5, 1, 7, 1, 9), (4, 3, 2, 1, 0)),     # extent-1 axes are dropped before dispatch
-         ((2, 3, 4, 5, 6, 7), (5, 0, 1, 2, 3, 4)),   # rotate: fuses to (720, 7) -> (7, 720)
-         ((2, 3, 4, 5, 6, 7), (1, 0, 3, 2, 5, 4)),
-         ((129, 257, 3), (1, 0, 2)),             # innermost axis kept: gather path
-         ((4, 5, 6, 7, 8, 3, 2, 2), (7, 6, 5, 4, 3, 2, 1, 0)),
-         ((64, 64, 64), (1, 2, 0))]
+# (the kernel each shape is planned onto on 256 CUs, as np_debug_layout_last_record reports it; tests/test_gpu_layout_exact.py asserts paths)
+PERMS = [((30, 3, 64, 65), (0, 2, 3, 1)),        # NCHW -> NHWC: fuses to a batched 3 x 4160 transpose: interleave_kernel<3, to interleaved>
+         ((30, 64, 65, 3), (0, 3, 1, 2)),        # NHWC -> NCHW: interleave_kernel<3, to planes>
+         ((70, 130, 66), (2, 1, 0)),             # full reversal: the pitched 64-tile transpose (not VEC), batch = middle axis
+         ((9, 10, 11, 12), (3, 2, 1, 0)),        # permute_plane_kernel<1>, one 9 x 12 tile per plane
+         ((5, 1, 7, 1, 9), (4, 3, 2, 1, 0)),     # extent-1 axes are dropped before dispatch: permute_plane_kernel<1>
+         ((2, 3, 4, 5, 6, 7), (5, 0, 1, 2, 3, 4)),   # rotate: fuses to (720, 7) -> (7, 720): the skinny kernel
+         ((2, 3, 4, 5, 6, 7), (1, 0, 3, 2, 5, 4)),   # permute_plane_kernel<1> with four batch axes
+         ((129, 257, 3), (1, 0, 2)),             # innermost axis of 3 floats kept: permute_plane_kernel<1> with E = 3 (NOT the gather)
+         ((4, 5, 6, 7, 8, 3, 2, 2), (7, 6, 5, 4, 3, 2, 1, 0)),   # permute_plane_kernel<1> with six batch axes
+         ((64, 64, 64), (1, 2, 0))]              # fuses to (64, 4096) -> (4096, 64): the 64-tile transpose, VEC
 
 
 @pytest.mark.parametrize("shape,axes", PERMS)
 def test_permute_paths(shape, axes, hip):
-    """np_permute after axis fusion: every dispatch (copy, batched 2-D transpose incl. the skinny
-    kernel, LDS-tiled plane transpose, gather) against numpy, bit for bit."""
+    """np_permute after axis fusion against numpy, bit for bit: the interleaves, the skinny kernel, the tile transpose plain and
+    pitched, permute_plane_kernel<1>.  No shape of the list reaches the gather, the write-aligned kernel or the memcpy shortcut:
+    tests/test_gpu_layout_exact.py has those, with the path asserted."""
     from numpower_amd.ndarray import NDArray
     x = synth.uniform(shape, 73, -1.0, 1.0)
     got = NDArray.transpose(NDArray.array(x).gpu(), axes).cpu().numpy()
@@ -99,10 +101,12 @@ def test_permute_paths(shape, axes, hip):
 
 @pytest.mark.parametrize("rc", [(100_003, 3), (3, 100_003), (70_000, 1), (1, 70_000), (5000, 16), (16, 5000), (1031, 1033),
                                 (4099, 257), (2, 2), (17, 17),
-                                (4099, 4099), (4100, 4243), (5000, 4099)])   # write-aligned tiles: 64 x 64 below 1200 tiles of 128 (round 5), 128 x 128 above
+                                (4099, 4099), (4100, 4243), (5000, 4099)])   # write-aligned tiles: 64 x 64 below 1200 tiles of 128 (the first two), 128 x 128 above
 def test_transpose2d_skinny_and_odd(rc, hip):
     """Tall-skinny / short-wide matrices (one side <= 16: transpose_skinny_kernel; these also have
-    more tile rows than gridDim.y allows) and odd sizes (dword-aligned float4 path)."""
+    more tile rows than gridDim.y allows; 70000 x 1 and its transpose fuse to one axis and are a device copy) and odd sizes
+    (dword-aligned float4 path).  On 256 CUs 1031 x 1033 and 4099 x 257 are too few tiles of 128 for the write-aligned kernel
+    and take the plain 64-tiles; the last three shapes reach it."""
     from numpower_amd.ndarray import NDArray
     x = synth.uniform(rc, 74, -1.0, 1.0)
     got = NDArray.transpose(NDArray.array(x).gpu()).cpu().numpy()
