@@ -1,5 +1,5 @@
 /*
- * hip_dnn.c — the device side of NDArrayDNN_Conv2D_Forward / _Backward, of the pooling layers and of softmax / cross-entropy (hip_dnn.h).  Compiled into a --with-hip tree against the
+ * hip_dnn.c — the device side of NDArrayDNN_Conv2D_Forward / _Backward, of the pooling layers, of softmax / cross-entropy and of batch normalization (hip_dnn.h).  Compiled into a --with-hip tree against the
  * reference's headers (-DNUMPOWER_NDARRAY_HEADER='"src/initializers.h"') and into libnumpower_host.so against
  * include/numpower_host.h; it uses only what both declare, with one switch: the reference's arrays take ownership of an
  * emalloc'd shape and its result vectors are emalloc'd, the host library copies shapes and hands out malloc'd vectors.
@@ -538,3 +538,121 @@ NDArray *NPH_CrossEntropy(NDArray *logits, NDArray *target, char reduction, int 
     return rtn;
 }
 
+
+/* ---- batch normalization (hip_dnn.h): np_batchnorm_forward / np_batchnorm_backward ---- */
+
+typedef struct { size_t N, C, inner; } nph_batchnorm;
+
+/* 1 when a is a (C) array */
+static int is_channel_vector(NDArray *a, int C) { return NDArray_NDIM(a) == 1 && NDArray_SHAPE(a)[0] == C; }
+
+/* the checks both directions share, in the order of hip_dnn.h.  Forward: dy == NULL, s1 / s2 the running statistics; backward:
+ * s1 / s2 the saved statistics.  Absent operands are NULL.  0 after a raised error */
+static int batchnorm_of(NDArray *x, NDArray *dy, NDArray *gamma, NDArray *beta, NDArray *s1, NDArray *s2, int backward, int training,
+                        double momentum, double eps, nph_batchnorm *b) {
+    const int ndim = NDArray_NDIM(x);
+    if (ndim < 2) {
+        np_ext_throw(NPH_BN_MSG_NDIM);
+        return 0;
+    }
+    const int *xs = NDArray_SHAPE(x);
+    const int C = xs[1];
+    b->N = (size_t) xs[0], b->C = (size_t) C, b->inner = 1;
+    for (int d = 2; d < ndim; ++d) b->inner *= (size_t) xs[d];
+    if (xs[0] < 1 || C < 1 || b->inner < 1) {
+        np_ext_throw(NPH_BN_MSG_EMPTY);
+        return 0;
+    }
+    if (gamma != NULL && !is_channel_vector(gamma, C)) {
+        np_ext_throw(NPH_BN_MSG_GAMMA);
+        return 0;
+    }
+    if (beta != NULL && !is_channel_vector(beta, C)) {
+        np_ext_throw(NPH_BN_MSG_BETA);
+        return 0;
+    }
+    if ((s1 != NULL && !is_channel_vector(s1, C)) || (s2 != NULL && !is_channel_vector(s2, C))) {
+        np_ext_throw(backward ? NPH_BN_MSG_SAVED : NPH_BN_MSG_RUNNING);
+        return 0;
+    }
+    if (!backward && !training && (s1 == NULL || s2 == NULL)) {
+        np_ext_throw(NPH_BN_MSG_INFERENCE);
+        return 0;
+    }
+    if (dy != NULL) {
+        int same = NDArray_NDIM(dy) == ndim;
+        for (int d = 0; same && d < ndim; ++d) same = NDArray_SHAPE(dy)[d] == xs[d];
+        if (!same) {
+            np_ext_throw(NPH_BN_MSG_GRADIENT);
+            return 0;
+        }
+    }
+    if (!(eps >= 0.0)) {
+        np_ext_throw(NPH_BN_MSG_EPS);
+        return 0;
+    }
+    if (!(momentum >= 0.0 && momentum <= 1.0)) {
+        np_ext_throw(NPH_BN_MSG_MOMENTUM);
+        return 0;
+    }
+    NDArray *others[5] = {dy, gamma, beta, s1, s2};
+    for (int k = 0; k < 5; ++k)
+        if (others[k] != NULL && NDArray_DEVICE(others[k]) != NDArray_DEVICE(x)) {
+            np_ext_throw(NPH_BN_MSG_DEVICE);
+            return 0;
+        }
+    if (NDArray_DEVICE(x) != NDARRAY_DEVICE_GPU) {
+        np_ext_throw(NPH_BN_MSG_CPU);
+        return 0;
+    }
+    if (!backward && training && b->N * b->inner == 1) {
+        np_ext_throw(NPH_BN_MSG_ONE_VALUE);
+        return 0;
+    }
+    return 1;
+}
+
+/* frees what a failed call had built; NULL */
+static NDArray **batchnorm_drop(NDArray **rtns, NDArray *a, NDArray *b, NDArray *c) {
+    if (a != NULL) NDArray_FREE(a);
+    if (b != NULL) NDArray_FREE(b);
+    if (c != NULL) NDArray_FREE(c);
+    if (rtns != NULL) NPH_RELEASE(rtns);
+    return NULL;
+}
+
+NDArray **NPH_BatchNorm_Forward(NDArray *x, NDArray *gamma, NDArray *beta, NDArray *running_mean, NDArray *running_var, int training,
+                                double momentum, double eps) {
+    nph_batchnorm b;
+    if (x == NULL || !batchnorm_of(x, NULL, gamma, beta, running_mean, running_var, 0, training, momentum, eps, &b)) return NULL;
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 3);
+    NDArray *y = empty_like_on_gpu(x);
+    NDArray *mean = training ? empty_on_gpu(1, &b.C) : NULL, *invstd = training ? empty_on_gpu(1, &b.C) : NULL;
+    if (rtns == NULL || y == NULL || (training && (mean == NULL || invstd == NULL))) return batchnorm_drop(rtns, y, mean, invstd);
+    if (np_batchnorm_forward(NDArray_FDATA(x), gamma != NULL ? NDArray_FDATA(gamma) : NULL, beta != NULL ? NDArray_FDATA(beta) : NULL, b.N, b.C,
+                             b.inner, training, momentum, eps, running_mean != NULL ? NDArray_FDATA(running_mean) : NULL,
+                             running_var != NULL ? NDArray_FDATA(running_var) : NULL, NDArray_FDATA(y), training ? NDArray_FDATA(mean) : NULL,
+                             training ? NDArray_FDATA(invstd) : NULL) != NP_OK) {
+        np_ext_throw_last();
+        return batchnorm_drop(rtns, y, mean, invstd);
+    }
+    rtns[0] = y, rtns[1] = mean, rtns[2] = invstd;
+    return rtns;
+}
+
+NDArray **NPH_BatchNorm_Backward(NDArray *x, NDArray *dy, NDArray *gamma, NDArray *save_mean, NDArray *save_invstd) {
+    nph_batchnorm b;
+    if (x == NULL || dy == NULL || save_mean == NULL || save_invstd == NULL) return NULL;
+    if (!batchnorm_of(x, dy, gamma, NULL, save_mean, save_invstd, 1, 1, 0.0, 0.0, &b)) return NULL;
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 3);
+    NDArray *dx = empty_like_on_gpu(x), *dgamma = empty_on_gpu(1, &b.C), *dbeta = empty_on_gpu(1, &b.C);
+    if (rtns == NULL || dx == NULL || dgamma == NULL || dbeta == NULL) return batchnorm_drop(rtns, dx, dgamma, dbeta);
+    if (np_batchnorm_backward(NDArray_FDATA(x), NDArray_FDATA(dy), gamma != NULL ? NDArray_FDATA(gamma) : NULL, NDArray_FDATA(save_mean),
+                              NDArray_FDATA(save_invstd), b.N, b.C, b.inner, NDArray_FDATA(dx), NDArray_FDATA(dgamma),
+                              NDArray_FDATA(dbeta)) != NP_OK) {
+        np_ext_throw_last();
+        return batchnorm_drop(rtns, dx, dgamma, dbeta);
+    }
+    rtns[0] = dx, rtns[1] = dgamma, rtns[2] = dbeta;
+    return rtns;
+}

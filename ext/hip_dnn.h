@@ -148,6 +148,37 @@ struct NDArray *NPH_Softmax_Backward(struct NDArray *y, struct NDArray *dy, int 
 /* the loss; *dlogits (when with_grad != 0 and dlogits != NULL) a new GPU array of the logits' shape, NULL after an error */
 struct NDArray *NPH_CrossEntropy(struct NDArray *logits, struct NDArray *target, char reduction, int with_grad, struct NDArray **dlogits);
 
+/* ---- batch normalization (np_batchnorm_forward / _backward of include/np_hip.h) ----
+ * The reference has no normalization layer, so tools/apply_with_hip.py inserts nothing; they are what a binding with these methods
+ * calls.  x has ndim >= 2 with the channel on axis 1 and is seen as (N, C, inner) = (shape[0], shape[1], the product of the rest).
+ * gamma, beta, the running statistics and the saved statistics are (C) arrays; gamma, beta and, in training, the running
+ * statistics may be NULL.  Training returns y, save_mean and save_invstd and updates the running statistics in place;
+ * inference (training == 0) needs both running statistics and returns y alone.  The backward pass is training mode's.
+ * The messages, checked in this order (the saved statistics' and the gradient's by NPH_BatchNorm_Backward alone; the running
+ * statistics', eps', momentum's and the last by NPH_BatchNorm_Forward alone): */
+#define NPH_BN_MSG_NDIM "dnn_batch_norm: the input must have at least 2 dimensions (N, C, ...)"
+#define NPH_BN_MSG_EMPTY "dnn_batch_norm: an operand has no elements"
+#define NPH_BN_MSG_GAMMA "dnn_batch_norm: gamma must be a (C) array, C = the input's shape[1]"
+#define NPH_BN_MSG_BETA "dnn_batch_norm: beta must be a (C) array, C = the input's shape[1]"
+#define NPH_BN_MSG_RUNNING "dnn_batch_norm: running_mean and running_var must be (C) arrays, C = the input's shape[1]"
+#define NPH_BN_MSG_INFERENCE "dnn_batch_norm: inference needs both running_mean and running_var"
+#define NPH_BN_MSG_SAVED "dnn_batch_norm_backward: save_mean and save_invstd must be (C) arrays, C = the input's shape[1]"
+#define NPH_BN_MSG_GRADIENT "dnn_batch_norm_backward: the gradient must have the shape of the input"
+#define NPH_BN_MSG_EPS "dnn_batch_norm: eps must not be negative"
+#define NPH_BN_MSG_MOMENTUM "dnn_batch_norm: momentum must lie in [0, 1]"
+#define NPH_BN_MSG_DEVICE "dnn_batch_norm: the operands must be on the same device"
+#define NPH_BN_MSG_CPU "dnn_batch_norm: operands are on the CPU; numpower_amd only computes on the GPU (call ->gpu() first)"
+#define NPH_BN_MSG_ONE_VALUE "dnn_batch_norm: training needs more than one value per channel"
+/* raised by the host library: a running statistic that had to be copied (a view) could not be updated in place */
+#define NPH_BN_MSG_RUNNING_VIEW "dnn_batch_norm: the running statistics are updated in place and must be contiguous arrays"
+
+/* a vector of three new GPU arrays: y in x's shape, save_mean (C), save_invstd (C); in inference the last two are NULL */
+struct NDArray **NPH_BatchNorm_Forward(struct NDArray *x, struct NDArray *gamma, struct NDArray *beta, struct NDArray *running_mean,
+                                       struct NDArray *running_var, int training, double momentum, double eps);
+/* a vector of three new GPU arrays: dx in x's shape, dgamma (C), dbeta (C) */
+struct NDArray **NPH_BatchNorm_Backward(struct NDArray *x, struct NDArray *dy, struct NDArray *gamma, struct NDArray *save_mean,
+                                        struct NDArray *save_invstd);
+
 #ifdef __cplusplus
 }
 #endif

@@ -747,6 +747,49 @@ int np_softmax_backward(const float *y, const float *dy, size_t outer, size_t co
 int np_cross_entropy(const float *logits, const float *target, size_t rows, size_t cols, int target_kind, float scale,
                      float *loss_rows, float *dlogits /* may be NULL */);
 
+/* ---- batch normalization (np_batchnorm.hip; DESIGN.md "batch normalization") ------------
+ * The operand is a contiguous fp32 array seen as (N, C, inner): inner == 1 is the (N, C) output of a dense layer, inner = H.W is
+ * NCHW.  The statistics are per channel c over the n = N.inner values x[., c, .].
+ *   Statistics      carried in fp64.  Per channel a shift K = x[0, c, 0]; S1 = sum of (x - K) and S2 = sum of (x - K)^2 are
+ *                   accumulated in double from +0.0 (the difference of two floats is exact in double except for exponent gaps
+ *                   beyond 29).
+ *                   mean64 = K + S1 / n.  var64 = S2 / n - (S1 / n)^2, the biased variance.  The order of the additions
+ *                   depends on (N, C, inner) and the kernel form alone; it moves the fp64 values far below fp32 resolution.
+ *   Saved values    save_mean = f32(mean64), save_invstd = f32(1 / sqrt(var64 + eps)): each ONE rounding of an fp64 value.
+ *                   eps and momentum are doubles.
+ *   Element         identical in training and inference, three separately rounded fp32 steps, no contraction:
+ *                   d = x - mean; h = d . invstd; y = h . gamma[c] + beta[c], a multiply, then an add.  A NULL gamma means 1 and
+ *                   a NULL beta means 0, and their steps are skipped.
+ *   Inference       training == 0 takes running_mean and running_var (both required): mean = running_mean,
+ *                   invstd = f32(1 / sqrt((double) running_var + eps)).  Inference on the statistics that training saved gives
+ *                   training's y bit for bit.  save_mean and save_invstd are not touched.
+ *   Running statistics   optional in training (NULL pointers skip them), updated in place:
+ *                   r = f32((1 - momentum) . (double) r + momentum . s64), s64 = mean64 for the running mean and
+ *                   s64 = var64 . n / (n - 1), the unbiased variance, for the running variance.
+ *   n == 1          training with one value per channel is refused with a message; inference with n == 1 is fine.
+ *   Backward        training mode, from x, dy, gamma, save_mean, save_invstd.  xh = (x - mean) . invstd rounded as above.
+ *                   sum of dy and sum of dy . xh are accumulated in fp64 from +0.0, each product formed in double from the two floats.
+ *                   dbeta = f32(sum dy); dgamma = f32(sum dy . xh); mb = f32(sum dy / n); mg = f32(sum dy . xh / n);
+ *                   dx = (gamma . invstd) . ((dy - mb) - xh . mg), every step a separately rounded fp32 operation in exactly
+ *                   that association (a NULL gamma: invstd alone).  dgamma and dbeta may be NULL.
+ *   Special values  a channel that holds a NaN or +-Inf comes out NaN in every element of y and dx; no other channel is
+ *                   touched.  A constant channel has var64 = 0: with eps > 0, y = beta exactly; with eps = 0, invstd = +Inf
+ *                   and y = NaN.  eps < 0 is refused; momentum outside [0, 1] is refused.
+ *   Aliasing        dx may alias dy (dx == dy).  No other output may overlap an input or another output.
+ *   Sizes           all size_t.  C >= 2^31 is refused with a message, never truncated; N.C.inner beyond 2^31 elements works.
+ *   Determinism     no float or double atomics; partial sums go to pool scratch that is released on every path; the work runs
+ *                   on the library stream.  Results are bit-identical from run to run.
+ *   Alignment       any 4-byte-aligned pointer is accepted and gives the same bits as a 16-byte-aligned one.
+ * Convention as above: pointers are checked first, then the extents, the parameters, the aliasing, then work begins.
+ * NP_ERR_INVALID before any device work: a null pointer (gamma, beta, dgamma, dbeta and, in training, the running statistics may
+ * be NULL), a zero extent, C at 2^31 or more, a negative eps, a momentum outside [0, 1], n == 1 in training, overlapping
+ * operands. */
+int np_batchnorm_forward(const float *x, const float *gamma, const float *beta, size_t N, size_t C, size_t inner, int training,
+                         double momentum, double eps, float *running_mean, float *running_var, float *y, float *save_mean,
+                         float *save_invstd);
+int np_batchnorm_backward(const float *x, const float *dy, const float *gamma, const float *save_mean, const float *save_invstd,
+                          size_t N, size_t C, size_t inner, float *dx, float *dgamma /* may be NULL */, float *dbeta /* may be NULL */);
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

@@ -180,6 +180,20 @@ int np_debug_softmax_force_form(int form);
 /* the boundaries, n >= 5: bounds[0 .. 2] = the largest cols of the short, wave and workgroup forms, bounds[3] = the words of
  * one staged slab, bounds[4] = the most rows a slab holds (rows per slab = min(bounds[4], bounds[3] / (cols | 1))) */
 int np_debug_softmax_bounds(size_t bounds[], int n);
+/* tests / tools: what the last np_batchnorm_forward or np_batchnorm_backward of the process launched.  form: 1 = one launch, a
+ * workgroup per channel with the channel in registers, 2 = split (statistics per (channel, slice), fold, apply), 3 = rows
+ * (inner == 1: lanes along C, slices of N), 4 = inference (the apply kernel alone).  launches: the kernels it took (1 for forms 1
+ * and 4, 3 for forms 2 and 3).  slices: S of forms 2, 3 and 4, 0 for form 1.  Zeros before any launch; NP_ERR_INVALID on a null
+ * pointer.  Plain process globals. */
+int np_debug_batchnorm_last_path(int *form, int *launches, size_t *slices);
+/* testing / A-B: form = 1 .. 3 sends every call through that form (inference: through that form's apply kernel; 1 counts as 2
+ * there), -1 (the default) chooses by (N, inner).  A call whose shape the forced form cannot serve is refused (NP_ERR_INVALID)
+ * before any device work.  Process-global. */
+int np_debug_batchnorm_force_form(int form);
+/* the boundaries, n >= 5: bounds[0] = the most values of a channel that form 1 takes on 256 lanes, bounds[1] = on 1024 lanes (the
+ * largest n of form 1), bounds[2] = the workgroups the slices aim for, bounds[3] = the most slices, bounds[4] = the fewest
+ * workgroup steps a slice holds */
+int np_debug_batchnorm_bounds(size_t bounds[], int n);
 /* tests / tools: which kernel families the last np_reduce_axis or np_reduce_all(_dev) call of the process launched, the calls it
  * makes on its own partials included: the OR of the NP_REDUCE_PATH_ bits below (0 = none yet).  A plain process global, cleared
  * at the top of those entry points; calls the library makes itself (split-K GEMM folds, chain partials) overwrite it too. */

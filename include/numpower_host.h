@@ -428,6 +428,17 @@ NDArray *NDArrayDNN_Pool2D_Backward(NDArray *x, NDArray *dy, const int *kernel, 
 NDArray *NDArrayDNN_Softmax_Forward(NDArray *x, int axis, char mode);
 NDArray *NDArrayDNN_Softmax_Backward(NDArray *y, NDArray *dy, int axis, char mode);
 NDArray *NDArrayDNN_CrossEntropy(NDArray *logits, NDArray *target, char reduction, int with_grad, NDArray **dlogits);
+/* Batch normalization (host/numpower_dnn.cpp; the reference has none): GPU operands, x of ndim >= 2 with the channel on axis 1,
+ * gamma / beta / running_mean / running_var (C) arrays or NULL.  training != 0: a vector of three new arrays (y, save_mean,
+ * save_invstd), the running statistics updated in place when given (momentum in [0, 1]; they must be contiguous arrays);
+ * training == 0: both running statistics are required, the vector holds y and two NULLs.  _Backward is training mode's backward
+ * pass from x, dy, gamma (or NULL) and the saved statistics: a vector (dx, dgamma, dbeta).  The caller frees the vector.  Views are
+ * made contiguous; NPH_BatchNorm_Forward / _Backward over np_batchnorm_forward / _backward do the work.  Errors (ext/hip_dnn.h,
+ * NPH_BN_MSG_*): ndim < 2, gamma, beta or statistics that are not (C), inference without running statistics, a gradient of another
+ * shape, eps < 0, momentum outside [0, 1], operands on different devices, CPU operands, one value per channel in training. */
+NDArray **NDArrayDNN_BatchNorm_Forward(NDArray *x, NDArray *gamma, NDArray *beta, NDArray *running_mean, NDArray *running_var, int training,
+                                       double momentum, double eps);
+NDArray **NDArrayDNN_BatchNorm_Backward(NDArray *x, NDArray *dy, NDArray *gamma, NDArray *save_mean, NDArray *save_invstd);
 
 #ifdef __cplusplus
 }

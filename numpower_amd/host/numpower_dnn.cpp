@@ -12,6 +12,7 @@
 #include <optional>
 
 #include "hip_dnn.h"
+#include "np_ext_hooks.h"
 #include "numpower_host.h"
 #include "numpower_operand.h"
 
@@ -120,6 +121,38 @@ NDArray *NDArrayDNN_CrossEntropy(NDArray *logits, NDArray *target, char reductio
     if (!logits || !target) return nullptr;
     return on_contiguous([=](NDArray *cl, NDArray *ct, NDArray *, NDArray *) { return NPH_CrossEntropy(cl, ct, reduction, with_grad, dlogits); },
                          logits, target);
+}
+
+// Batch normalization (np_batchnorm_forward / _backward), which the reference does not have either.  gamma, beta
+// and, in training, the running statistics may be nullptr.  The running statistics are updated in place: one that had to be
+// copied to become contiguous (a view) is refused in training.
+NDArray **NDArrayDNN_BatchNorm_Forward(NDArray *x, NDArray *gamma, NDArray *beta, NDArray *running_mean, NDArray *running_var, int training,
+                                       double momentum, double eps) {
+    if (!x) return nullptr;
+    return on_contiguous(
+        [=](NDArray *cx, NDArray *cg, NDArray *cb, NDArray *) -> NDArray ** {
+            return on_contiguous(
+                [=](NDArray *cm, NDArray *cv, NDArray *, NDArray *) -> NDArray ** {
+                    if (training && (cm != running_mean || cv != running_var)) {
+                        np_ext_throw(NPH_BN_MSG_RUNNING_VIEW);
+                        return nullptr;
+                    }
+                    return NPH_BatchNorm_Forward(cx, cg, cb, cm, cv, training, momentum, eps);
+                },
+                running_mean, running_var);
+        },
+        x, gamma, beta);
+}
+
+// (dx, dgamma, dbeta) of training mode, from the layer's input and the statistics the forward pass saved
+NDArray **NDArrayDNN_BatchNorm_Backward(NDArray *x, NDArray *dy, NDArray *gamma, NDArray *save_mean, NDArray *save_invstd) {
+    if (!x || !dy || !save_mean || !save_invstd) return nullptr;
+    return on_contiguous(
+        [=](NDArray *cx, NDArray *cd, NDArray *cm, NDArray *cv) -> NDArray ** {
+            return on_contiguous([=](NDArray *cg, NDArray *, NDArray *, NDArray *) -> NDArray ** { return NPH_BatchNorm_Backward(cx, cd, cg, cm, cv); },
+                                 gamma, nullptr);
+        },
+        x, dy, save_mean, save_invstd);
 }
 
 }  // extern "C"

@@ -164,6 +164,8 @@ def _load_host():
     sig["NDArrayDNN_Softmax_Forward"] = (_P, [_P, C.c_int, C.c_char])
     sig["NDArrayDNN_Softmax_Backward"] = (_P, [_P, _P, C.c_int, C.c_char])
     sig["NDArrayDNN_CrossEntropy"] = (_P, [_P, _P, C.c_char, C.c_int, C.POINTER(_P)])
+    sig["NDArrayDNN_BatchNorm_Forward"] = (C.POINTER(_P), [_P] * 5 + [C.c_int, C.c_double, C.c_double])
+    sig["NDArrayDNN_BatchNorm_Backward"] = (C.POINTER(_P), [_P] * 5)
     sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
     sig["NDArray_Eig"] = (C.POINTER(_P), [_P])
     sig["NDArray_Qr"] = (C.POINTER(_P), [_P])
@@ -1032,6 +1034,47 @@ class NDArray:
                                          C.byref(grad) if with_grad else None)
         loss = NDArray._wrap(loss)
         return (loss, NDArray._wrap(grad)) if with_grad else loss
+
+    @staticmethod
+    def _bn_operand(value):
+        return None if value is None else NDArray._coerce(value)[0]
+
+    @staticmethod
+    def dnn_batch_norm_forward(x, gamma=None, beta=None, running_mean=None, running_var=None, training=True, momentum=0.1, eps=1e-5):
+        """Batch normalization of a GPU array of ndim >= 2 with the channel on axis 1: per channel the mean and
+        the biased variance over every other axis, carried in fp64 from shifted sums, then y = (x - mean) . invstd . gamma + beta.
+        training=True returns (y, save_mean, save_invstd) and updates running_mean / running_var in place when given
+        (r = (1 - momentum) . r + momentum . s, the unbiased variance for running_var); training=False needs both running
+        arrays and returns y.  gamma and beta are (C) arrays or None (1 and 0)."""
+        h = _load_host()
+        if isinstance(momentum, bool) or isinstance(eps, bool) or not isinstance(momentum, (int, float, np.floating, np.integer)) \
+                or not isinstance(eps, (int, float, np.floating, np.integer)):
+            raise Error("dnn_batch_norm_forward: momentum and eps must be numbers")
+        ops = [NDArray._bn_operand(v) for v in (x, gamma, beta, running_mean, running_var)]
+        if ops[0] is None:
+            raise Error("dnn_batch_norm_forward: x must be an array")
+        rtns = h.NDArrayDNN_BatchNorm_Forward(*[None if o is None else o._p for o in ops], 1 if training else 0, float(momentum), float(eps))
+        if not rtns:
+            _raise_pending(h)
+        out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(3 if training else 1))
+        _libc_free(C.cast(rtns, C.c_void_p))
+        return out if training else out[0]
+
+    @staticmethod
+    def dnn_batch_norm_backward(x, dy, gamma, save_mean, save_invstd):
+        """(dx, dgamma, dbeta) of training-mode batch normalization from the layer's input x, the gradient dy of its output, gamma
+        (or None) and the statistics the forward pass saved: fp64 sums of dy and dy . xhat, then
+        dx = (gamma . invstd) . ((dy - mean(dy)) - xhat . mean(dy . xhat))."""
+        h = _load_host()
+        ops = [NDArray._bn_operand(v) for v in (x, dy, gamma, save_mean, save_invstd)]
+        if any(ops[i] is None for i in (0, 1, 3, 4)):
+            raise Error("dnn_batch_norm_backward: x, dy, save_mean and save_invstd must be arrays")
+        rtns = h.NDArrayDNN_BatchNorm_Backward(*[None if o is None else o._p for o in ops])
+        if not rtns:
+            _raise_pending(h)
+        out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(3))
+        _libc_free(C.cast(rtns, C.c_void_p))
+        return out
 
     def copy(self):          # PHP_METHOD copy: NDArray_Copy on the array's own device
         return NDArray._wrap(_load_host().NDArray_Copy(self._p, C.cast(self._p, _P).contents.device))

@@ -35,12 +35,19 @@ copy of the SAME bytes (8 per element forward, 12 backward, 8 plus the labels an
 shapes, with the four-pass composition examples/softmax_regression.py uses (max, two fused chains, the loss chain), which is how the
 library computed a softmax loss before.  Reported: ms, TB/s, copy / op (1.00 = the copy's rate, the ceiling of a form that reads a row
 once and writes it once) and composition / op.  The log is stamped with the sources it ran on.  Writes profiles/dnn/softmax_sweep.log.
+--batchnorm is the leg of batch normalization (np_batchnorm.hip): training forward, inference forward and backward on BATCHNORM_SHAPES,
+which reach every kernel form.  Each operation alternates, round by round in one session, with the float4 copy of the bytes its form
+moves (8 per element for inference and the one-launch training form, 12 for the split and rows training forward, 12 for the
+one-launch backward, 20 for the split and rows backward) and, for the (N, C) shapes, the training forward with the composition a user
+would write from NDArray calls (two column means, a centred square, three row broadcasts); an NCHW composition needs transposes and
+is not expressed.  Reported: ms, TB/s, copy / op and composition / op.  Writes profiles/dnn/batchnorm_sweep.log.
 
 Usage: python tools/dnn_sweep.py [--layers 0,1,...] [--rounds N] [--limit S] [--torch] [--out FILE]
        python tools/dnn_sweep.py --act [--layers ...]         the bias / activation leg
        python tools/dnn_sweep.py --forward-only [--layers ...]
        python tools/dnn_sweep.py --pool [--layers ...]        the pooling leg
        python tools/dnn_sweep.py --softmax [--layers ...]     the softmax / cross-entropy leg
+       python tools/dnn_sweep.py --batchnorm [--layers ...]   the batch-normalization leg
        python tools/dnn_sweep.py --profile LAYER     three calls of each operation and nothing else, for a run under the kernel profiler"""
 import argparse
 import statistics
@@ -76,7 +83,13 @@ POOL_MODE = {"max": 0, "avg": 1, "avg_valid": 2}
 SOFTMAX_SHAPES = [("10^7 x 10", (10 ** 7, 10, 1)), ("200000 x 10", (200000, 10, 1)), ("65536 x 1000", (65536, 1000, 1)),
                   ("8192 x 32768", (8192, 32768, 1)), ("64 x 10^6", (64, 10 ** 6, 1)), ("NCHW channels (64, 21, 128, 128)", (64, 21, 128 * 128))]
 
+# name, (N, C, inner)
+BATCHNORM_SHAPES = [("(64, 64, 112, 112)", (64, 64, 112 * 112)), ("(64, 3, 224, 224)", (64, 3, 224 * 224)), ("(256, 512, 7, 7)", (256, 512, 49)),
+                    ("(65536, 1024)", (65536, 1024, 1)), ("(10^6, 16)", (10 ** 6, 16, 1)), ("(64, 2048, 7, 7)", (64, 2048, 49)),
+                    ("(32, 512, 14, 14)", (32, 512, 196))]
+
 ap = argparse.ArgumentParser()
+ap.add_argument("--batchnorm", action="store_true")
 ap.add_argument("--pool", action="store_true")
 ap.add_argument("--softmax", action="store_true")
 ap.add_argument("--sets", type=int, default=0, help="--pool: operand sets to rotate through (0: enough to pass 256 MiB)")
@@ -91,9 +104,9 @@ ap.add_argument("--profile", type=int, default=None)
 ap.add_argument("--child", default=None, help="internal: 'layer:<i>' or 'torch'")
 args = ap.parse_args()
 if args.layers is None:
-    args.layers = ",".join(str(i) for i in range(len(SOFTMAX_SHAPES if args.softmax else POOL_LAYERS if args.pool else LAYERS)))
+    args.layers = ",".join(str(i) for i in range(len(BATCHNORM_SHAPES if args.batchnorm else SOFTMAX_SHAPES if args.softmax else POOL_LAYERS if args.pool else LAYERS)))
 if args.out is None:
-    args.out = str(ROOT / "profiles" / "dnn" / ("softmax_sweep.log" if args.softmax else "pool2d_sweep.log" if args.pool else "conv2d_act_sweep.log" if args.act else
+    args.out = str(ROOT / "profiles" / "dnn" / ("batchnorm_sweep.log" if args.batchnorm else "softmax_sweep.log" if args.softmax else "pool2d_sweep.log" if args.pool else "conv2d_act_sweep.log" if args.act else
                                                "conv2d_forward_only.log" if args.forward_only else "conv2d_sweep.log"))
 LARGE = (256, 128, 3136)                        # (N, F, P) of the large case of --act: 1.03e8 elements
 HBM_TBS = 8.0
@@ -376,6 +389,104 @@ def run_pool(i, rounds, sets):
                      min(c / p for c, p in zip(copy_ms, pool_ms)), max(c / p for c, p in zip(copy_ms, pool_ms))), flush=True)
 
 
+def run_batchnorm(i, rounds, sets):
+    """one shape: training forward, inference forward and backward, each alternating with a float4 copy of the bytes its form moves"""
+    import ctypes as C_
+    import numpy as np
+    D, lib, check, ramp, _ = _setup()
+    from numpower_amd._lib import Timer
+    t = Timer()
+    name, (N, C, inner) = BATCHNORM_SHAPES[i]
+    n = N * C * inner
+    if sets < 1:
+        sets = max(2, -(-(256 << 20) // (4 * n)) + 1)
+    rng = np.random.default_rng(i)
+    block = rng.standard_normal(1 << 20).astype(np.float32)
+    host = np.resize(block, n)
+    xs = [D.DeviceArray.from_host(host) for _ in range(sets)]
+    ys, dys, dxs = ([D.DeviceArray((n,)) for _ in range(sets)] for _ in range(3))
+    for d in dys:
+        check(lib.np_memcpy_d2d(d.ptr, xs[0].ptr, 4 * n))
+    words = 5 * n // 2 + 16
+    cs, cd = [D.DeviceArray((words,)) for _ in range(sets)], [D.DeviceArray((words,)) for _ in range(sets)]      # the copy's own operands
+    for c in cs:
+        check(lib.np_memset0(c.ptr, 4 * words))
+    gamma, beta = D.DeviceArray.from_host(rng.standard_normal(C).astype(np.float32)), D.DeviceArray.from_host(rng.standard_normal(C).astype(np.float32))
+    rm, rv = D.DeviceArray.from_host(np.zeros(C, np.float32)), D.DeviceArray.from_host(np.ones(C, np.float32))
+    mean, invstd, dgamma, dbeta = (D.DeviceArray((C,)) for _ in range(4))
+    dims = (N, C, inner)
+    ramp()
+    turn = [0]
+
+    def rotating(fn):
+        def call():
+            turn[0] = (turn[0] + 1) % sets
+            fn(turn[0])
+        return call
+
+    def copy_of(total_bytes):
+        half = total_bytes // 2 // 16 * 16        # a copy of B / 2 bytes reads B / 2 and writes B / 2
+        return rotating(lambda k: check(lib.np_memcpy_d2d(cd[k].ptr, cs[k].ptr, half)))
+
+    def timed(fn, reps):
+        t.start()
+        for _ in range(reps):
+            fn()
+        t.stop()
+        return t.elapsed_ms() / reps
+
+    def probe():
+        form, launches, slices = C_.c_int(), C_.c_int(), C_.c_size_t()
+        check(lib.np_debug_batchnorm_last_path(C_.byref(form), C_.byref(launches), C_.byref(slices)))
+        return form.value, launches.value, slices.value
+
+    composition = None
+    if inner == 1:                                # what a user writes today for an (N, C) array: single-axis means and row broadcasts
+        from numpower_amd.ndarray import NDArray as nd
+        gx = nd.array(host.reshape(N, C)).gpu()
+        gg, gb = nd.array(np.ones(C, np.float32)).gpu(), nd.array(np.zeros(C, np.float32)).gpu()
+
+        def composition():
+            m = nd.mean(gx, 0)
+            xc = gx - m
+            inv = 1.0 / nd.sqrt(nd.mean(xc * xc, 0) + 1e-5)
+            return xc * inv * gg + gb
+
+    training = rotating(lambda k: check(lib.np_batchnorm_forward(xs[k].ptr, gamma.ptr, beta.ptr, *dims, 1, 0.1, 1e-5, rm.ptr, rv.ptr, ys[k].ptr, mean.ptr, invstd.ptr)))
+    inference = rotating(lambda k: check(lib.np_batchnorm_forward(xs[k].ptr, gamma.ptr, beta.ptr, *dims, 0, 0.1, 1e-5, rm.ptr, rv.ptr, ys[k].ptr, None, None)))
+    backward = rotating(lambda k: check(lib.np_batchnorm_backward(xs[k].ptr, dys[k].ptr, gamma.ptr, mean.ptr, invstd.ptr, *dims, dxs[k].ptr, dgamma.ptr, dbeta.ptr)))
+    training()
+    one = probe()[0] == 1
+    ops = [("training forward", training, (8 if one else 12) * n, True), ("inference forward", inference, 8 * n, False),
+           ("backward", backward, (12 if one else 20) * n, False)]
+    for label, fn, nbytes, against in ops:
+        copy = copy_of(nbytes)
+        for f in (fn, copy):                      # warm
+            for _ in range(3):
+                f()
+        D.sync()
+        t0 = time.time()
+        fn()
+        D.sync()
+        reps = max(5, min(200, int(0.05 / max(time.time() - t0, 1e-5))))
+        op_ms, copy_ms, comp_ms = [], [], []
+        for _ in range(rounds):                   # alternating in one session
+            op_ms.append(timed(fn, reps))
+            copy_ms.append(timed(copy, reps))
+            if against and composition is not None:
+                comp_ms.append(timed(composition, max(2, reps // 8)))
+        fn()
+        form, launches, slices = probe()
+        om, cm = statistics.median(op_ms), statistics.median(copy_ms)
+        tail = ""
+        if comp_ms:
+            pm = statistics.median(comp_ms)
+            tail = "   composition %9.4f ms   composition / op %6.2f" % (pm, pm / om)
+        print("%-20s %-18s form %d launches %d S %4d %8.1f MB %9.4f ms %5.2f TB/s   copy %9.4f ms %5.2f TB/s   copy / op %5.2f   (min %5.2f max %5.2f)%s"
+              % (name, label, form, launches, slices, nbytes * 1e-6, om, nbytes / om * 1e-9, cm, nbytes / cm * 1e-9, cm / om,
+                 min(c / p for c, p in zip(copy_ms, op_ms)), max(c / p for c, p in zip(copy_ms, op_ms)), tail), flush=True)
+
+
 def run_softmax(i, rounds, sets):
     """one shape: every operation alternates with a float4 copy of the same bytes and (row shapes) with the four-pass composition"""
     import ctypes as C_
@@ -519,6 +630,8 @@ if args.child:
         run_act(args.child.split(":")[1], args.rounds)
     elif args.child.startswith("pool:"):
         run_pool(int(args.child.split(":")[1]), args.rounds, args.sets)
+    elif args.child.startswith("batchnorm:"):
+        run_batchnorm(int(args.child.split(":")[1]), args.rounds, args.sets)
     elif args.child.startswith("softmax:"):
         run_softmax(int(args.child.split(":")[1]), args.rounds, args.sets)
     elif args.child.startswith("fwd:"):
@@ -550,8 +663,15 @@ def child(what):
     return proc.returncode == 0
 
 
-kind = "softmax" if args.softmax else "pool" if args.pool else "act" if args.act else "fwd" if args.forward_only else "layer"
-if args.softmax:
+kind = "batchnorm" if args.batchnorm else "softmax" if args.softmax else "pool" if args.pool else "act" if args.act else "fwd" if args.forward_only else "layer"
+if args.batchnorm:
+    import hashlib
+    say("np_batchnorm_forward (training, inference) / np_batchnorm_backward (form of the launch: 1 one launch, 2 split, 3 rows, 4 inference's apply kernel) "
+        "against np_memcpy_d2d (the float4 copy) of the bytes the form moves and, for (N, C) shapes, the training forward against the composition from "
+        "NDArray calls, alternating round by round; fp32, ms per call, medians of %d rounds" % args.rounds)
+    say("sources: " + ", ".join("%s sha256 %s" % (f, hashlib.sha256((ROOT / "numpower_amd" / "csrc" / f).read_bytes()).hexdigest()[:16])
+                                for f in ("np_batchnorm.hip", "np_internal.h")))
+elif args.softmax:
     import hashlib
     say("np_softmax_forward / np_softmax_backward / np_cross_entropy (form of the launch: 1 short rows, 2 a wave per row, 3 a workgroup per row, 4 streaming, 5 strided) "
         "against np_memcpy_d2d (the float4 copy) of the same bytes read + written and against the four-pass composition of examples/softmax_regression.py, "
