@@ -656,3 +656,189 @@ NDArray **NPH_BatchNorm_Backward(NDArray *x, NDArray *dy, NDArray *gamma, NDArra
     rtns[0] = dx, rtns[1] = dgamma, rtns[2] = dbeta;
     return rtns;
 }
+
+
+/* ---- layer and group normalization (hip_dnn.h): np_groupnorm_forward / np_groupnorm_backward ---- */
+
+typedef struct { size_t N, G, D, inner; } nph_groupnorm;
+
+/* a new GPU array of ndim >= 1 extents */
+static NDArray *empty_of_ints_on_gpu(const int *dims, int ndim) {
+    int *shape = (int *) NPH_ALLOC(sizeof(int) * (size_t) ndim);
+    if (shape == NULL) return NULL;
+    for (int d = 0; d < ndim; ++d) shape[d] = dims[d];
+    NDArray *rtn = NDArray_Empty(shape, ndim, "float32", NDARRAY_DEVICE_GPU);
+    if (NPH_SHAPE_IS_COPIED) NPH_RELEASE(shape);
+    return rtn;
+}
+
+/* 1 when a has exactly the ndim extents of dims */
+static int has_shape(NDArray *a, const int *dims, int ndim) {
+    if (NDArray_NDIM(a) != ndim) return 0;
+    for (int d = 0; d < ndim; ++d)
+        if (NDArray_SHAPE(a)[d] != dims[d]) return 0;
+    return 1;
+}
+
+/* the messages of one of the two layers, in the order of the checks they share */
+typedef struct { const char *empty, *gamma, *beta, *saved, *gradient, *eps, *device, *cpu; } nph_norm_messages;
+static const nph_norm_messages nph_ln_messages = {NPH_LN_MSG_EMPTY, NPH_LN_MSG_GAMMA, NPH_LN_MSG_BETA, NPH_LN_MSG_SAVED, NPH_LN_MSG_GRADIENT,
+                                                  NPH_LN_MSG_EPS, NPH_LN_MSG_DEVICE, NPH_LN_MSG_CPU};
+static const nph_norm_messages nph_gn_messages = {NPH_GN_MSG_EMPTY, NPH_GN_MSG_GAMMA, NPH_GN_MSG_BETA, NPH_GN_MSG_SAVED, NPH_GN_MSG_GRADIENT,
+                                                  NPH_GN_MSG_EPS, NPH_GN_MSG_DEVICE, NPH_GN_MSG_CPU};
+
+/* the checks both layers and both directions share once the geometry is known, in the order of hip_dnn.h: the parameters have
+ * the par_ndim extents of par, the saved statistics the stat_ndim extents of stat.  Absent operands are NULL.  0 after a raised
+ * error */
+static int norm_operands(const nph_norm_messages *msg, NDArray *x, NDArray *dy, NDArray *gamma, NDArray *beta, NDArray *mean, NDArray *invstd,
+                         const int *par, int par_ndim, const int *stat, int stat_ndim, double eps, const nph_groupnorm *b) {
+    if (b->N < 1 || b->G < 1 || b->D < 1 || b->inner < 1) {
+        np_ext_throw(msg->empty);
+        return 0;
+    }
+    if (gamma != NULL && !has_shape(gamma, par, par_ndim)) {
+        np_ext_throw(msg->gamma);
+        return 0;
+    }
+    if (beta != NULL && !has_shape(beta, par, par_ndim)) {
+        np_ext_throw(msg->beta);
+        return 0;
+    }
+    if ((mean != NULL && !has_shape(mean, stat, stat_ndim)) || (invstd != NULL && !has_shape(invstd, stat, stat_ndim))) {
+        np_ext_throw(msg->saved);
+        return 0;
+    }
+    if (dy != NULL && !has_shape(dy, NDArray_SHAPE(x), NDArray_NDIM(x))) {
+        np_ext_throw(msg->gradient);
+        return 0;
+    }
+    if (!(eps >= 0.0)) {
+        np_ext_throw(msg->eps);
+        return 0;
+    }
+    NDArray *others[5] = {dy, gamma, beta, mean, invstd};
+    for (int k = 0; k < 5; ++k)
+        if (others[k] != NULL && NDArray_DEVICE(others[k]) != NDArray_DEVICE(x)) {
+            np_ext_throw(msg->device);
+            return 0;
+        }
+    if (NDArray_DEVICE(x) != NDARRAY_DEVICE_GPU) {
+        np_ext_throw(msg->cpu);
+        return 0;
+    }
+    return 1;
+}
+
+/* layer normalization's geometry: (M, 1, L, 1).  *stat / *stat_ndim: the leading shape ((1) when there is no leading axis) */
+static int layernorm_of(NDArray *x, NDArray *dy, const int *normalized_shape, int normalized_ndim, NDArray *gamma, NDArray *beta, NDArray *mean,
+                        NDArray *invstd, double eps, nph_groupnorm *b, const int **stat, int *stat_ndim) {
+    static const int one = 1;
+    const int ndim = NDArray_NDIM(x), lead = ndim - normalized_ndim;
+    if (normalized_shape == NULL || normalized_ndim < 1 || normalized_ndim > ndim) {
+        np_ext_throw(NPH_LN_MSG_NDIM);
+        return 0;
+    }
+    const int *xs = NDArray_SHAPE(x);
+    for (int d = 0; d < normalized_ndim; ++d)
+        if (normalized_shape[d] != xs[lead + d]) {
+            np_ext_throw(NPH_LN_MSG_SHAPE);
+            return 0;
+        }
+    b->N = 1, b->G = 1, b->D = 1, b->inner = 1;
+    for (int d = 0; d < lead; ++d) b->N *= (size_t) (xs[d] > 0 ? xs[d] : 0);
+    for (int d = lead; d < ndim; ++d) b->D *= (size_t) (xs[d] > 0 ? xs[d] : 0);
+    *stat = lead > 0 ? xs : &one, *stat_ndim = lead > 0 ? lead : 1;
+    return norm_operands(&nph_ln_messages, x, dy, gamma, beta, mean, invstd, xs + lead, normalized_ndim, *stat, *stat_ndim, eps, b);
+}
+
+/* group normalization's geometry: (N, G, C / G, inner).  stat: room for the two extents (N, G) */
+static int groupnorm_of(NDArray *x, NDArray *dy, int num_groups, NDArray *gamma, NDArray *beta, NDArray *mean, NDArray *invstd, double eps,
+                        nph_groupnorm *b, int *stat) {
+    const int ndim = NDArray_NDIM(x);
+    if (ndim < 2) {
+        np_ext_throw(NPH_GN_MSG_NDIM);
+        return 0;
+    }
+    const int *xs = NDArray_SHAPE(x);
+    const int C = xs[1];
+    b->inner = 1;
+    for (int d = 2; d < ndim; ++d) b->inner *= (size_t) (xs[d] > 0 ? xs[d] : 0);
+    if (xs[0] < 1 || C < 1 || b->inner < 1) {
+        np_ext_throw(NPH_GN_MSG_EMPTY);
+        return 0;
+    }
+    if (num_groups < 1) {
+        np_ext_throw(NPH_GN_MSG_GROUPS);
+        return 0;
+    }
+    if (C % num_groups != 0) {
+        np_ext_throw(NPH_GN_MSG_DIVISIBLE);
+        return 0;
+    }
+    b->N = (size_t) xs[0], b->G = (size_t) num_groups, b->D = (size_t) (C / num_groups);
+    stat[0] = xs[0], stat[1] = num_groups;
+    return norm_operands(&nph_gn_messages, x, dy, gamma, beta, mean, invstd, &C, 1, stat, 2, eps, b);
+}
+
+/* the forward call on checked operands: (y, save_mean, save_invstd), the statistics with the stat_ndim extents of stat */
+static NDArray **norm_forward(NDArray *x, NDArray *gamma, NDArray *beta, double eps, const nph_groupnorm *b, const int *stat, int stat_ndim) {
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 3);
+    NDArray *y = empty_like_on_gpu(x), *mean = empty_of_ints_on_gpu(stat, stat_ndim), *invstd = empty_of_ints_on_gpu(stat, stat_ndim);
+    if (rtns == NULL || y == NULL || mean == NULL || invstd == NULL) return batchnorm_drop(rtns, y, mean, invstd);
+    if (np_groupnorm_forward(NDArray_FDATA(x), gamma != NULL ? NDArray_FDATA(gamma) : NULL, beta != NULL ? NDArray_FDATA(beta) : NULL, b->N, b->G,
+                             b->D, b->inner, eps, NDArray_FDATA(y), NDArray_FDATA(mean), NDArray_FDATA(invstd)) != NP_OK) {
+        np_ext_throw_last();
+        return batchnorm_drop(rtns, y, mean, invstd);
+    }
+    rtns[0] = y, rtns[1] = mean, rtns[2] = invstd;
+    return rtns;
+}
+
+/* the backward call on checked operands: (dx, dgamma, dbeta), the gradients with the par_ndim extents of par */
+static NDArray **norm_backward(NDArray *x, NDArray *dy, NDArray *gamma, NDArray *mean, NDArray *invstd, const nph_groupnorm *b, const int *par,
+                               int par_ndim) {
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 3);
+    NDArray *dx = empty_like_on_gpu(x), *dgamma = empty_of_ints_on_gpu(par, par_ndim), *dbeta = empty_of_ints_on_gpu(par, par_ndim);
+    if (rtns == NULL || dx == NULL || dgamma == NULL || dbeta == NULL) return batchnorm_drop(rtns, dx, dgamma, dbeta);
+    if (np_groupnorm_backward(NDArray_FDATA(x), NDArray_FDATA(dy), gamma != NULL ? NDArray_FDATA(gamma) : NULL, NDArray_FDATA(mean),
+                              NDArray_FDATA(invstd), b->N, b->G, b->D, b->inner, NDArray_FDATA(dx), NDArray_FDATA(dgamma),
+                              NDArray_FDATA(dbeta)) != NP_OK) {
+        np_ext_throw_last();
+        return batchnorm_drop(rtns, dx, dgamma, dbeta);
+    }
+    rtns[0] = dx, rtns[1] = dgamma, rtns[2] = dbeta;
+    return rtns;
+}
+
+NDArray **NPH_LayerNorm_Forward(NDArray *x, const int *normalized_shape, int normalized_ndim, NDArray *gamma, NDArray *beta, double eps) {
+    nph_groupnorm b;
+    const int *stat;
+    int stat_ndim;
+    if (x == NULL || !layernorm_of(x, NULL, normalized_shape, normalized_ndim, gamma, beta, NULL, NULL, eps, &b, &stat, &stat_ndim)) return NULL;
+    return norm_forward(x, gamma, beta, eps, &b, stat, stat_ndim);
+}
+
+NDArray **NPH_LayerNorm_Backward(NDArray *x, NDArray *dy, const int *normalized_shape, int normalized_ndim, NDArray *gamma, NDArray *save_mean,
+                                 NDArray *save_invstd) {
+    nph_groupnorm b;
+    const int *stat;
+    int stat_ndim;
+    if (x == NULL || dy == NULL || save_mean == NULL || save_invstd == NULL) return NULL;
+    if (!layernorm_of(x, dy, normalized_shape, normalized_ndim, gamma, NULL, save_mean, save_invstd, 0.0, &b, &stat, &stat_ndim)) return NULL;
+    return norm_backward(x, dy, gamma, save_mean, save_invstd, &b, NDArray_SHAPE(x) + (NDArray_NDIM(x) - normalized_ndim), normalized_ndim);
+}
+
+NDArray **NPH_GroupNorm_Forward(NDArray *x, int num_groups, NDArray *gamma, NDArray *beta, double eps) {
+    nph_groupnorm b;
+    int stat[2];
+    if (x == NULL || !groupnorm_of(x, NULL, num_groups, gamma, beta, NULL, NULL, eps, &b, stat)) return NULL;
+    return norm_forward(x, gamma, beta, eps, &b, stat, 2);
+}
+
+NDArray **NPH_GroupNorm_Backward(NDArray *x, NDArray *dy, int num_groups, NDArray *gamma, NDArray *save_mean, NDArray *save_invstd) {
+    nph_groupnorm b;
+    int stat[2];
+    if (x == NULL || dy == NULL || save_mean == NULL || save_invstd == NULL) return NULL;
+    if (!groupnorm_of(x, dy, num_groups, gamma, NULL, save_mean, save_invstd, 0.0, &b, stat)) return NULL;
+    return norm_backward(x, dy, gamma, save_mean, save_invstd, &b, &NDArray_SHAPE(x)[1], 1);
+}

@@ -179,6 +179,50 @@ struct NDArray **NPH_BatchNorm_Forward(struct NDArray *x, struct NDArray *gamma,
 struct NDArray **NPH_BatchNorm_Backward(struct NDArray *x, struct NDArray *dy, struct NDArray *gamma, struct NDArray *save_mean,
                                         struct NDArray *save_invstd);
 
+/* ---- layer and group normalization (np_groupnorm_forward / _backward of include/np_hip.h) ----
+ * The reference has no normalization layer, so tools/apply_with_hip.py inserts nothing; they are what a binding with these methods
+ * calls.
+ * Layer normalization: normalized_shape (normalized_ndim >= 1 extents) must equal x's trailing axes; x is seen as (M, L), M the
+ * product of the leading axes; gamma and beta have the normalized shape or are NULL; the statistics have the leading shape ((1)
+ * when the normalized shape is the whole of x).
+ * Group normalization: x has ndim >= 2 with the channel on axis 1 and is seen as (N, G, C / G, inner); gamma and beta are (C)
+ * arrays or NULL; the statistics are (N, G) arrays.  Instance normalization is num_groups = C.
+ * The messages, checked in this order (the saved statistics' and the gradient's by the backward passes alone, eps' by the forward
+ * passes alone): */
+#define NPH_LN_MSG_NDIM "dnn_layer_norm: normalized_shape must have between 1 and the input's number of dimensions"
+#define NPH_LN_MSG_SHAPE "dnn_layer_norm: normalized_shape must equal the input's trailing axes"
+#define NPH_LN_MSG_EMPTY "dnn_layer_norm: an operand has no elements"
+#define NPH_LN_MSG_GAMMA "dnn_layer_norm: gamma must have the normalized shape"
+#define NPH_LN_MSG_BETA "dnn_layer_norm: beta must have the normalized shape"
+#define NPH_LN_MSG_SAVED "dnn_layer_norm_backward: save_mean and save_invstd must have the shape of the input's leading axes"
+#define NPH_LN_MSG_GRADIENT "dnn_layer_norm_backward: the gradient must have the shape of the input"
+#define NPH_LN_MSG_EPS "dnn_layer_norm: eps must not be negative"
+#define NPH_LN_MSG_DEVICE "dnn_layer_norm: the operands must be on the same device"
+#define NPH_LN_MSG_CPU "dnn_layer_norm: operands are on the CPU; numpower_amd only computes on the GPU (call ->gpu() first)"
+#define NPH_GN_MSG_NDIM "dnn_group_norm: the input must have at least 2 dimensions (N, C, ...)"
+#define NPH_GN_MSG_EMPTY "dnn_group_norm: an operand has no elements"
+#define NPH_GN_MSG_GROUPS "dnn_group_norm: num_groups must be at least 1"
+#define NPH_GN_MSG_DIVISIBLE "dnn_group_norm: C = the input's shape[1] must be divisible by num_groups"
+#define NPH_GN_MSG_GAMMA "dnn_group_norm: gamma must be a (C) array, C = the input's shape[1]"
+#define NPH_GN_MSG_BETA "dnn_group_norm: beta must be a (C) array, C = the input's shape[1]"
+#define NPH_GN_MSG_SAVED "dnn_group_norm_backward: save_mean and save_invstd must be (N, num_groups) arrays"
+#define NPH_GN_MSG_GRADIENT "dnn_group_norm_backward: the gradient must have the shape of the input"
+#define NPH_GN_MSG_EPS "dnn_group_norm: eps must not be negative"
+#define NPH_GN_MSG_DEVICE "dnn_group_norm: the operands must be on the same device"
+#define NPH_GN_MSG_CPU "dnn_group_norm: operands are on the CPU; numpower_amd only computes on the GPU (call ->gpu() first)"
+
+/* a vector of three new GPU arrays: y in x's shape, save_mean and save_invstd in the leading shape */
+struct NDArray **NPH_LayerNorm_Forward(struct NDArray *x, const int *normalized_shape, int normalized_ndim, struct NDArray *gamma,
+                                       struct NDArray *beta, double eps);
+/* a vector of three new GPU arrays: dx in x's shape, dgamma and dbeta in the normalized shape */
+struct NDArray **NPH_LayerNorm_Backward(struct NDArray *x, struct NDArray *dy, const int *normalized_shape, int normalized_ndim,
+                                        struct NDArray *gamma, struct NDArray *save_mean, struct NDArray *save_invstd);
+/* a vector of three new GPU arrays: y in x's shape, save_mean (N, num_groups), save_invstd (N, num_groups) */
+struct NDArray **NPH_GroupNorm_Forward(struct NDArray *x, int num_groups, struct NDArray *gamma, struct NDArray *beta, double eps);
+/* a vector of three new GPU arrays: dx in x's shape, dgamma (C), dbeta (C) */
+struct NDArray **NPH_GroupNorm_Backward(struct NDArray *x, struct NDArray *dy, int num_groups, struct NDArray *gamma,
+                                        struct NDArray *save_mean, struct NDArray *save_invstd);
+
 #ifdef __cplusplus
 }
 #endif

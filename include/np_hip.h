@@ -790,6 +790,47 @@ int np_batchnorm_forward(const float *x, const float *gamma, const float *beta, 
 int np_batchnorm_backward(const float *x, const float *dy, const float *gamma, const float *save_mean, const float *save_invstd,
                           size_t N, size_t C, size_t inner, float *dx, float *dgamma /* may be NULL */, float *dbeta /* may be NULL */);
 
+/* ---- layer and group normalization (np_groupnorm.hip; DESIGN.md "layer and group normalization") ------------
+ * One geometry serves both.  The operand is a contiguous fp32 array seen as (N, G, D, inner): M = N.G rows of L = D.inner
+ * contiguous floats, P = G.D affine parameters, and element j of row r uses parameter (r mod G).D + j / inner.
+ *   Layer normalization over the trailing axes is G = 1, D = L, inner = 1 (P = L).  Group normalization of (N, C, spatial...)
+ *   with num_groups = G is D = C / G, inner = the product of the spatial extents (P = C).  Instance normalization is G = C.
+ * It is batch normalization's definition applied per row:
+ *   Statistics      carried in fp64.  Per row a shift K = x[r, 0]; S1 = sum of (x - K) and S2 = sum of (x - K)^2 are accumulated
+ *                   in double from +0.0.  mean64 = K + S1 / L.  var64 = S2 / L - (S1 / L)^2, the biased variance.  The order of
+ *                   the additions depends on (N, G, D, inner) and the kernel form alone.
+ *   Saved values    save_mean[r] = f32(mean64), save_invstd[r] = f32(1 / sqrt(var64 + eps)), r = 0 .. N.G - 1: each ONE rounding of
+ *                   an fp64 value.  eps is a double.
+ *   Element         three separately rounded fp32 steps, no contraction: d = x - mean; h = d . invstd;
+ *                   y = h . gamma[p] + beta[p], a multiply, then an add.  A NULL gamma means 1 and a NULL beta means 0, and
+ *                   their steps are skipped.
+ *   Backward, per row        xh = (x - mean) . invstd rounded as above.  g = f32(dy . gamma[p]) (a NULL gamma: g = dy).  sum of g
+ *                   and sum of g . xh are accumulated in fp64 from +0.0, each product formed in double from the two floats.
+ *                   mb = f32(sum g / L); mg = f32(sum g . xh / L); dx = invstd . ((g - mb) - xh . mg), every step a separately
+ *                   rounded fp32 operation in exactly that association.
+ *   Backward, per parameter  dbeta[p] = f32(sum dy) and dgamma[p] = f32(sum dy . xh) over every element that uses parameter p,
+ *                   in fp64 from +0.0, products formed in double.  Either may be NULL; with both NULL the reduction is not
+ *                   launched.
+ *   Special values  a row that holds a NaN or +-Inf comes out NaN in every element of y and dx; no other row is touched.  A
+ *                   constant row has var64 = 0: with eps > 0, y = beta exactly; with eps = 0, invstd = +Inf and y = NaN.  The
+ *                   same holds for L = 1, which is accepted.  eps < 0 is refused.
+ *   Aliasing        dx may alias dy (dx == dy).  No other output may overlap an input or another output.
+ *   Sizes           all size_t.  M = N.G or P = G.D at 2^31 or more is refused with a message, never truncated; element offsets
+ *                   are size_t, so N.G.D.inner beyond 2^31 elements works.
+ *   Determinism     no float or double atomics; partial sums go to pool scratch that is released on every path; the work runs
+ *                   on the library stream; forms and slice counts come from (N, G, D, inner) alone.  Results are bit-identical
+ *                   from run to run.
+ *   Alignment       any 4-byte-aligned pointer is accepted and gives the same bits as a 16-byte-aligned one.
+ * Convention as above: pointers are checked first, then the extents, the parameters, the aliasing, then work begins.
+ * NP_ERR_INVALID before any device work: a null pointer (gamma, beta, dgamma and dbeta may be NULL), a zero extent, M or P at 2^31
+ * or more, a negative eps, overlapping operands. */
+int np_groupnorm_forward(const float *x, const float *gamma /* P, may be NULL */, const float *beta /* P, may be NULL */,
+                         size_t N, size_t G, size_t D, size_t inner, double eps,
+                         float *y, float *save_mean /* N.G */, float *save_invstd /* N.G */);
+int np_groupnorm_backward(const float *x, const float *dy, const float *gamma, const float *save_mean, const float *save_invstd,
+                          size_t N, size_t G, size_t D, size_t inner,
+                          float *dx, float *dgamma /* P, may be NULL */, float *dbeta /* P, may be NULL */);
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

@@ -194,6 +194,20 @@ int np_debug_batchnorm_force_form(int form);
  * largest n of form 1), bounds[2] = the workgroups the slices aim for, bounds[3] = the most slices, bounds[4] = the fewest
  * workgroup steps a slice holds */
 int np_debug_batchnorm_bounds(size_t bounds[], int n);
+/* tests / tools: what the last np_groupnorm_forward or np_groupnorm_backward of the process launched.  row_form: 1 = short rows
+ * (a power-of-two segment of a wave per row), 2 = a wave per row, 3 = a workgroup per row (both with the row in registers),
+ * 4 = split (statistics per (row, slice), fold, apply).  param_form: 0 = no parameter reduction (the forward pass; dgamma and
+ * dbeta both NULL), 1 = columns (inner == 1), 2 = planes.  launches: the kernels it took (1 or 3 for the rows, 2 for the
+ * parameters).  row_slices: S of row form 4, 0 otherwise.  param_slices: the slices of the parameter reduction, 0 without one.
+ * Zeros before any launch; NP_ERR_INVALID on a null pointer.  Plain process globals. */
+int np_debug_groupnorm_last_path(int *row_form, int *param_form, int *launches, size_t *row_slices, size_t *param_slices);
+/* testing / A-B: row_form = 1 .. 4 and param_form = 1 .. 2 send every call through that form, -1 (the default) chooses by
+ * (D, inner).  A call whose shape a forced form cannot serve is refused (NP_ERR_INVALID) before any device work.  Process-global. */
+int np_debug_groupnorm_force_form(int row_form, int param_form);
+/* the boundaries, n >= 7: bounds[0 .. 1] = the largest L of the short and the wave form, bounds[2] = the largest L a workgroup
+ * of 256 lanes takes, bounds[3] = of 1024 lanes (the largest L of form 3), bounds[4] = the workgroups the slices aim for,
+ * bounds[5] = the most slices, bounds[6] = the fewest workgroup steps a slice holds */
+int np_debug_groupnorm_bounds(size_t bounds[], int n);
 /* tests / tools: which kernel families the last np_reduce_axis or np_reduce_all(_dev) call of the process launched, the calls it
  * makes on its own partials included: the OR of the NP_REDUCE_PATH_ bits below (0 = none yet).  A plain process global, cleared
  * at the top of those entry points; calls the library makes itself (split-K GEMM folds, chain partials) overwrite it too. */

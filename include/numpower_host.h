@@ -439,6 +439,18 @@ NDArray *NDArrayDNN_CrossEntropy(NDArray *logits, NDArray *target, char reductio
 NDArray **NDArrayDNN_BatchNorm_Forward(NDArray *x, NDArray *gamma, NDArray *beta, NDArray *running_mean, NDArray *running_var, int training,
                                        double momentum, double eps);
 NDArray **NDArrayDNN_BatchNorm_Backward(NDArray *x, NDArray *dy, NDArray *gamma, NDArray *save_mean, NDArray *save_invstd);
+/* Layer and group normalization (host/numpower_dnn.cpp; the reference has none): GPU operands.  Layer normalization takes the
+ * normalized_ndim trailing extents of x as normalized_shape; gamma and beta have that shape or are NULL; the statistics have the
+ * shape of the leading axes ((1) without one).  Group normalization takes x of ndim >= 2 with the channel on axis 1 and
+ * num_groups dividing C; gamma and beta are (C) arrays or NULL; the statistics are (N, num_groups); instance normalization is
+ * num_groups = C.  _Forward: a vector of three new arrays (y, save_mean, save_invstd); _Backward, from x, dy, gamma (or NULL) and
+ * the saved statistics: (dx, dgamma, dbeta).  The caller frees the vector.  Views are made contiguous; NPH_LayerNorm_* and
+ * NPH_GroupNorm_* over np_groupnorm_forward / _backward do the work.  Errors: ext/hip_dnn.h, NPH_LN_MSG_* and NPH_GN_MSG_*. */
+NDArray **NDArrayDNN_LayerNorm_Forward(NDArray *x, const int *normalized_shape, int normalized_ndim, NDArray *gamma, NDArray *beta, double eps);
+NDArray **NDArrayDNN_LayerNorm_Backward(NDArray *x, NDArray *dy, const int *normalized_shape, int normalized_ndim, NDArray *gamma,
+                                        NDArray *save_mean, NDArray *save_invstd);
+NDArray **NDArrayDNN_GroupNorm_Forward(NDArray *x, int num_groups, NDArray *gamma, NDArray *beta, double eps);
+NDArray **NDArrayDNN_GroupNorm_Backward(NDArray *x, NDArray *dy, int num_groups, NDArray *gamma, NDArray *save_mean, NDArray *save_invstd);
 
 #ifdef __cplusplus
 }

@@ -155,4 +155,48 @@ NDArray **NDArrayDNN_BatchNorm_Backward(NDArray *x, NDArray *dy, NDArray *gamma,
         x, dy, save_mean, save_invstd);
 }
 
+// Layer and group normalization (np_groupnorm_forward / _backward), which the reference does not have either.
+// normalized_shape: the normalized_ndim trailing extents of x; gamma and beta may be nullptr.
+NDArray **NDArrayDNN_LayerNorm_Forward(NDArray *x, const int *normalized_shape, int normalized_ndim, NDArray *gamma, NDArray *beta, double eps) {
+    if (!x) return nullptr;
+    return on_contiguous(
+        [=](NDArray *cx, NDArray *cg, NDArray *cb, NDArray *) -> NDArray ** {
+            return NPH_LayerNorm_Forward(cx, normalized_shape, normalized_ndim, cg, cb, eps);
+        },
+        x, gamma, beta);
+}
+
+// (dx, dgamma, dbeta) from the layer's input and the statistics the forward pass saved
+NDArray **NDArrayDNN_LayerNorm_Backward(NDArray *x, NDArray *dy, const int *normalized_shape, int normalized_ndim, NDArray *gamma,
+                                        NDArray *save_mean, NDArray *save_invstd) {
+    if (!x || !dy || !save_mean || !save_invstd) return nullptr;
+    return on_contiguous(
+        [=](NDArray *cx, NDArray *cd, NDArray *cm, NDArray *cv) -> NDArray ** {
+            return on_contiguous(
+                [=](NDArray *cg, NDArray *, NDArray *, NDArray *) -> NDArray ** {
+                    return NPH_LayerNorm_Backward(cx, cd, normalized_shape, normalized_ndim, cg, cm, cv);
+                },
+                gamma, nullptr);
+        },
+        x, dy, save_mean, save_invstd);
+}
+
+// x (N, C, ...) in num_groups groups of C / num_groups channels; instance normalization is num_groups = C
+NDArray **NDArrayDNN_GroupNorm_Forward(NDArray *x, int num_groups, NDArray *gamma, NDArray *beta, double eps) {
+    if (!x) return nullptr;
+    return on_contiguous([=](NDArray *cx, NDArray *cg, NDArray *cb, NDArray *) -> NDArray ** { return NPH_GroupNorm_Forward(cx, num_groups, cg, cb, eps); },
+                         x, gamma, beta);
+}
+
+NDArray **NDArrayDNN_GroupNorm_Backward(NDArray *x, NDArray *dy, int num_groups, NDArray *gamma, NDArray *save_mean, NDArray *save_invstd) {
+    if (!x || !dy || !save_mean || !save_invstd) return nullptr;
+    return on_contiguous(
+        [=](NDArray *cx, NDArray *cd, NDArray *cm, NDArray *cv) -> NDArray ** {
+            return on_contiguous(
+                [=](NDArray *cg, NDArray *, NDArray *, NDArray *) -> NDArray ** { return NPH_GroupNorm_Backward(cx, cd, num_groups, cg, cm, cv); }, gamma,
+                nullptr);
+        },
+        x, dy, save_mean, save_invstd);
+}
+
 }  // extern "C"

@@ -166,6 +166,10 @@ def _load_host():
     sig["NDArrayDNN_CrossEntropy"] = (_P, [_P, _P, C.c_char, C.c_int, C.POINTER(_P)])
     sig["NDArrayDNN_BatchNorm_Forward"] = (C.POINTER(_P), [_P] * 5 + [C.c_int, C.c_double, C.c_double])
     sig["NDArrayDNN_BatchNorm_Backward"] = (C.POINTER(_P), [_P] * 5)
+    sig["NDArrayDNN_LayerNorm_Forward"] = (C.POINTER(_P), [_P, ip, C.c_int, _P, _P, C.c_double])
+    sig["NDArrayDNN_LayerNorm_Backward"] = (C.POINTER(_P), [_P, _P, ip, C.c_int, _P, _P, _P])
+    sig["NDArrayDNN_GroupNorm_Forward"] = (C.POINTER(_P), [_P, C.c_int, _P, _P, C.c_double])
+    sig["NDArrayDNN_GroupNorm_Backward"] = (C.POINTER(_P), [_P, _P, C.c_int, _P, _P, _P])
     sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
     sig["NDArray_Eig"] = (C.POINTER(_P), [_P])
     sig["NDArray_Qr"] = (C.POINTER(_P), [_P])
@@ -1075,6 +1079,82 @@ class NDArray:
         out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(3))
         _libc_free(C.cast(rtns, C.c_void_p))
         return out
+
+    @staticmethod
+    def _norm_results(h, rtns):
+        if not rtns:
+            _raise_pending(h)
+        out = tuple(NDArray(C.cast(rtns[i], _P)) for i in range(3))
+        _libc_free(C.cast(rtns, C.c_void_p))
+        return out
+
+    @staticmethod
+    def _normalized_shape(who, normalized_shape):
+        """-> (int array, ndim) for an int or a tuple of ints"""
+        dims = (normalized_shape,) if isinstance(normalized_shape, (int, np.integer)) and not isinstance(normalized_shape, bool) else normalized_shape
+        if not isinstance(dims, (tuple, list)) or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in dims):
+            raise Error(who + ": normalized_shape must be an int or a tuple of ints")
+        return (C.c_int * max(1, len(dims)))(*[int(v) for v in dims]), len(dims)
+
+    @staticmethod
+    def dnn_layer_norm_forward(x, normalized_shape, gamma=None, beta=None, eps=1e-5):
+        """Layer normalization of a GPU array over its trailing axes: normalized_shape, an int or a tuple, must
+        equal those axes.  Per row (one per index of the leading axes) the mean and the biased variance, carried in fp64 from
+        shifted sums, then y = (x - mean) . invstd . gamma + beta with gamma and beta of the normalized shape, or None (1 and 0).
+        Returns (y, save_mean, save_invstd), the statistics in the shape of the leading axes."""
+        h = _load_host()
+        if isinstance(eps, bool) or not isinstance(eps, (int, float, np.floating, np.integer)):
+            raise Error("dnn_layer_norm_forward: eps must be a number")
+        dims, ndim = NDArray._normalized_shape("dnn_layer_norm_forward", normalized_shape)
+        ops = [NDArray._bn_operand(v) for v in (x, gamma, beta)]
+        if ops[0] is None:
+            raise Error("dnn_layer_norm_forward: x must be an array")
+        p = [None if o is None else o._p for o in ops]
+        return NDArray._norm_results(h, h.NDArrayDNN_LayerNorm_Forward(p[0], dims, ndim, p[1], p[2], float(eps)))
+
+    @staticmethod
+    def dnn_layer_norm_backward(x, dy, normalized_shape, gamma, save_mean, save_invstd):
+        """(dx, dgamma, dbeta) of layer normalization from the layer's input x, the gradient dy of its output, gamma (or None) and
+        the statistics the forward pass saved: per row g = dy . gamma, fp64 sums of g and g . xhat, then
+        dx = invstd . ((g - mean(g)) - xhat . mean(g . xhat)); per parameter dbeta = sum dy and dgamma = sum dy . xhat."""
+        h = _load_host()
+        dims, ndim = NDArray._normalized_shape("dnn_layer_norm_backward", normalized_shape)
+        ops = [NDArray._bn_operand(v) for v in (x, dy, gamma, save_mean, save_invstd)]
+        if any(ops[i] is None for i in (0, 1, 3, 4)):
+            raise Error("dnn_layer_norm_backward: x, dy, save_mean and save_invstd must be arrays")
+        p = [None if o is None else o._p for o in ops]
+        return NDArray._norm_results(h, h.NDArrayDNN_LayerNorm_Backward(p[0], p[1], dims, ndim, p[2], p[3], p[4]))
+
+    @staticmethod
+    def dnn_group_norm_forward(x, num_groups, gamma=None, beta=None, eps=1e-5):
+        """Group normalization of a GPU array of ndim >= 2 with the channel on axis 1: the C channels form
+        num_groups groups of C / num_groups, and each (sample, group) is normalized over its channels and every later axis, with
+        statistics carried in fp64 from shifted sums; then y = (x - mean) . invstd . gamma + beta with gamma and beta (C) arrays
+        or None (1 and 0).  Instance normalization is num_groups = C; num_groups = 1 normalizes each sample as a whole.
+        Returns (y, save_mean, save_invstd), the statistics of shape (N, num_groups)."""
+        h = _load_host()
+        if isinstance(eps, bool) or not isinstance(eps, (int, float, np.floating, np.integer)):
+            raise Error("dnn_group_norm_forward: eps must be a number")
+        if isinstance(num_groups, bool) or not isinstance(num_groups, (int, np.integer)):
+            raise Error("dnn_group_norm_forward: num_groups must be an int")
+        ops = [NDArray._bn_operand(v) for v in (x, gamma, beta)]
+        if ops[0] is None:
+            raise Error("dnn_group_norm_forward: x must be an array")
+        p = [None if o is None else o._p for o in ops]
+        return NDArray._norm_results(h, h.NDArrayDNN_GroupNorm_Forward(p[0], int(num_groups), p[1], p[2], float(eps)))
+
+    @staticmethod
+    def dnn_group_norm_backward(x, dy, num_groups, gamma, save_mean, save_invstd):
+        """(dx, dgamma, dbeta) of group normalization (instance normalization: num_groups = C) from the layer's input x, the
+        gradient dy of its output, gamma (or None) and the statistics the forward pass saved."""
+        h = _load_host()
+        if isinstance(num_groups, bool) or not isinstance(num_groups, (int, np.integer)):
+            raise Error("dnn_group_norm_backward: num_groups must be an int")
+        ops = [NDArray._bn_operand(v) for v in (x, dy, gamma, save_mean, save_invstd)]
+        if any(ops[i] is None for i in (0, 1, 3, 4)):
+            raise Error("dnn_group_norm_backward: x, dy, save_mean and save_invstd must be arrays")
+        p = [None if o is None else o._p for o in ops]
+        return NDArray._norm_results(h, h.NDArrayDNN_GroupNorm_Backward(p[0], p[1], int(num_groups), p[2], p[3], p[4]))
 
     def copy(self):          # PHP_METHOD copy: NDArray_Copy on the array's own device
         return NDArray._wrap(_load_host().NDArray_Copy(self._p, C.cast(self._p, _P).contents.device))

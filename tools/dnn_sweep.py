@@ -41,6 +41,12 @@ moves (8 per element for inference and the one-launch training form, 12 for the 
 one-launch backward, 20 for the split and rows backward) and, for the (N, C) shapes, the training forward with the composition a user
 would write from NDArray calls (two column means, a centred square, three row broadcasts); an NCHW composition needs transposes and
 is not expressed.  Reported: ms, TB/s, copy / op and composition / op.  Writes profiles/dnn/batchnorm_sweep.log.
+--groupnorm is the leg of layer and group normalization (np_groupnorm.hip): forward, backward with the parameter gradients and
+backward without them on GROUPNORM_SHAPES.  Each operation alternates, round by round in one session, with the float4 copy of the
+bytes its form moves (forward 8 per element with the row in registers, 12 split; backward 12 or 20, and 8 more for the parameter
+reduction) and, for the two 2-D shapes where it can be written, the forward pass with the composition from NDArray calls and with
+np_batchnorm_forward's rows form on the same array.  Reported: ms, TB/s, copy / op, composition / op and batch norm / op.  Writes
+profiles/dnn/groupnorm_sweep.log.
 
 Usage: python tools/dnn_sweep.py [--layers 0,1,...] [--rounds N] [--limit S] [--torch] [--out FILE]
        python tools/dnn_sweep.py --act [--layers ...]         the bias / activation leg
@@ -48,6 +54,7 @@ Usage: python tools/dnn_sweep.py [--layers 0,1,...] [--rounds N] [--limit S] [--
        python tools/dnn_sweep.py --pool [--layers ...]        the pooling leg
        python tools/dnn_sweep.py --softmax [--layers ...]     the softmax / cross-entropy leg
        python tools/dnn_sweep.py --batchnorm [--layers ...]   the batch-normalization leg
+       python tools/dnn_sweep.py --groupnorm [--layers ...]   the layer / group normalization leg
        python tools/dnn_sweep.py --profile LAYER     three calls of each operation and nothing else, for a run under the kernel profiler"""
 import argparse
 import statistics
@@ -88,8 +95,15 @@ BATCHNORM_SHAPES = [("(64, 64, 112, 112)", (64, 64, 112 * 112)), ("(64, 3, 224, 
                     ("(65536, 1024)", (65536, 1024, 1)), ("(10^6, 16)", (10 ** 6, 16, 1)), ("(64, 2048, 7, 7)", (64, 2048, 49)),
                     ("(32, 512, 14, 14)", (32, 512, 196))]
 
+# name, (N, G, D, inner), compare with the composition and batch norm's rows form
+GROUPNORM_SHAPES = [("layer (65536, 1024)", (65536, 1, 1024, 1), True), ("layer (10^6, 16)", (10 ** 6, 1, 16, 1), True),
+                    ("layer (8192, 8192)", (8192, 1, 8192, 1), False), ("layer (64, 10^6)", (64, 1, 10 ** 6, 1), False),
+                    ("group 32 (64, 64, 112, 112)", (64, 32, 2, 112 * 112), False), ("group 32 (256, 512, 7, 7)", (256, 32, 16, 49), False),
+                    ("group 32 (2, 64, 112, 112)", (2, 32, 2, 112 * 112), False), ("instance (64, 64, 56, 56)", (64, 64, 1, 56 * 56), False)]
+
 ap = argparse.ArgumentParser()
 ap.add_argument("--batchnorm", action="store_true")
+ap.add_argument("--groupnorm", action="store_true")
 ap.add_argument("--pool", action="store_true")
 ap.add_argument("--softmax", action="store_true")
 ap.add_argument("--sets", type=int, default=0, help="--pool: operand sets to rotate through (0: enough to pass 256 MiB)")
@@ -104,9 +118,9 @@ ap.add_argument("--profile", type=int, default=None)
 ap.add_argument("--child", default=None, help="internal: 'layer:<i>' or 'torch'")
 args = ap.parse_args()
 if args.layers is None:
-    args.layers = ",".join(str(i) for i in range(len(BATCHNORM_SHAPES if args.batchnorm else SOFTMAX_SHAPES if args.softmax else POOL_LAYERS if args.pool else LAYERS)))
+    args.layers = ",".join(str(i) for i in range(len(GROUPNORM_SHAPES if args.groupnorm else BATCHNORM_SHAPES if args.batchnorm else SOFTMAX_SHAPES if args.softmax else POOL_LAYERS if args.pool else LAYERS)))
 if args.out is None:
-    args.out = str(ROOT / "profiles" / "dnn" / ("batchnorm_sweep.log" if args.batchnorm else "softmax_sweep.log" if args.softmax else "pool2d_sweep.log" if args.pool else "conv2d_act_sweep.log" if args.act else
+    args.out = str(ROOT / "profiles" / "dnn" / ("groupnorm_sweep.log" if args.groupnorm else "batchnorm_sweep.log" if args.batchnorm else "softmax_sweep.log" if args.softmax else "pool2d_sweep.log" if args.pool else "conv2d_act_sweep.log" if args.act else
                                                "conv2d_forward_only.log" if args.forward_only else "conv2d_sweep.log"))
 LARGE = (256, 128, 3136)                        # (N, F, P) of the large case of --act: 1.03e8 elements
 HBM_TBS = 8.0
@@ -487,6 +501,120 @@ def run_batchnorm(i, rounds, sets):
                  min(c / p for c, p in zip(copy_ms, op_ms)), max(c / p for c, p in zip(copy_ms, op_ms)), tail), flush=True)
 
 
+def run_groupnorm(i, rounds, sets):
+    """one shape: forward, backward with the parameter gradients, backward without them, each alternating with a float4 copy of the
+    bytes its forms move; for the 2-D shapes the forward pass also with the NDArray composition and batch norm's rows form"""
+    import ctypes as C_
+    import numpy as np
+    D, lib, check, ramp, _ = _setup()
+    from numpower_amd._lib import Timer
+    t = Timer()
+    name, (N, G, Dg, inner), compare = GROUPNORM_SHAPES[i]
+    M, L, P = N * G, Dg * inner, G * Dg
+    n = M * L
+    if sets < 1:
+        sets = max(2, -(-(256 << 20) // (4 * n)) + 1)
+    rng = np.random.default_rng(i)
+    block = rng.standard_normal(1 << 20).astype(np.float32)
+    host = np.resize(block, n)
+    xs = [D.DeviceArray.from_host(host) for _ in range(sets)]
+    ys, dys, dxs = ([D.DeviceArray((n,)) for _ in range(sets)] for _ in range(3))
+    for d in dys:
+        check(lib.np_memcpy_d2d(d.ptr, xs[0].ptr, 4 * n))
+    words = 7 * n // 2 + 16
+    cs, cd = [D.DeviceArray((words,)) for _ in range(sets)], [D.DeviceArray((words,)) for _ in range(sets)]      # the copy's own operands
+    for c in cs:
+        check(lib.np_memset0(c.ptr, 4 * words))
+    gamma, beta = D.DeviceArray.from_host(rng.standard_normal(P).astype(np.float32)), D.DeviceArray.from_host(rng.standard_normal(P).astype(np.float32))
+    stat = max(M, P)
+    mean, invstd = D.DeviceArray((stat,)), D.DeviceArray((stat,))
+    dgamma, dbeta = D.DeviceArray((P,)), D.DeviceArray((P,))
+    dims = (N, G, Dg, inner)
+    ramp()
+    turn = [0]
+
+    def rotating(fn):
+        def call():
+            turn[0] = (turn[0] + 1) % sets
+            fn(turn[0])
+        return call
+
+    def copy_of(total_bytes):
+        half = total_bytes // 2 // 16 * 16        # a copy of B / 2 bytes reads B / 2 and writes B / 2
+        return rotating(lambda k: check(lib.np_memcpy_d2d(cd[k].ptr, cs[k].ptr, half)))
+
+    def timed(fn, reps):
+        t.start()
+        for _ in range(reps):
+            fn()
+        t.stop()
+        return t.elapsed_ms() / reps
+
+    def probe():
+        v = [C_.c_int(), C_.c_int(), C_.c_int(), C_.c_size_t(), C_.c_size_t()]
+        check(lib.np_debug_groupnorm_last_path(*[C_.byref(a) for a in v]))
+        return tuple(a.value for a in v)
+
+    composition = batchnorm = None
+    if compare:                                   # what a user writes today for an (M, L) array: single-axis means and column broadcasts
+        from numpower_amd.ndarray import NDArray as nd
+        gx = nd.array(host.reshape(M, L)).gpu()
+        gg, gb = nd.array(np.ones(L, np.float32)).gpu(), nd.array(np.zeros(L, np.float32)).gpu()
+
+        def composition():
+            m = nd.reshape(nd.mean(gx, 1), [M, 1])
+            xc = gx - m
+            inv = 1.0 / nd.sqrt(nd.reshape(nd.mean(xc * xc, 1), [M, 1]) + 1e-5)
+            return xc * inv * gg + gb
+
+        try:
+            composition()
+        except Exception as e:                    # the composition is a comparison, not the subject
+            print("%-28s the NDArray composition is not expressed: %s" % (name, e), flush=True)
+            composition = None
+        # the nearest call the library had: batch normalization's rows form on the same (M, L) array, statistics per column
+        batchnorm = rotating(lambda k: check(lib.np_batchnorm_forward(xs[k].ptr, gamma.ptr, beta.ptr, M, L, 1, 1, 0.1, 1e-5, None, None, ys[k].ptr, mean.ptr, invstd.ptr)))
+
+    forward = rotating(lambda k: check(lib.np_groupnorm_forward(xs[k].ptr, gamma.ptr, beta.ptr, *dims, 1e-5, ys[k].ptr, mean.ptr, invstd.ptr)))
+    backward = rotating(lambda k: check(lib.np_groupnorm_backward(xs[k].ptr, dys[k].ptr, gamma.ptr, mean.ptr, invstd.ptr, *dims, dxs[k].ptr, dgamma.ptr, dbeta.ptr)))
+    backward_dx = rotating(lambda k: check(lib.np_groupnorm_backward(xs[k].ptr, dys[k].ptr, gamma.ptr, mean.ptr, invstd.ptr, *dims, dxs[k].ptr, None, None)))
+    forward()
+    split = probe()[0] == 4
+    ops = [("forward", forward, (12 if split else 8) * n, True), ("backward", backward, (28 if split else 20) * n, False),
+           ("backward, dx alone", backward_dx, (20 if split else 12) * n, False)]
+    for label, fn, nbytes, against in ops:
+        copy = copy_of(nbytes)
+        for f in (fn, copy):                      # warm
+            for _ in range(3):
+                f()
+        D.sync()
+        t0 = time.time()
+        fn()
+        D.sync()
+        reps = max(5, min(200, int(0.05 / max(time.time() - t0, 1e-5))))
+        op_ms, copy_ms, comp_ms, bn_ms = [], [], [], []
+        for _ in range(rounds):                   # alternating in one session
+            op_ms.append(timed(fn, reps))
+            copy_ms.append(timed(copy, reps))
+            if against and composition is not None:
+                comp_ms.append(timed(composition, max(2, reps // 8)))
+            if against and batchnorm is not None:
+                bn_ms.append(timed(batchnorm, reps))
+        fn()
+        row, param, launches, rs, ps = probe()
+        om, cm = statistics.median(op_ms), statistics.median(copy_ms)
+        tail = ""
+        if comp_ms:
+            pm = statistics.median(comp_ms)
+            tail += "   composition %9.4f ms   composition / op %6.2f" % (pm, pm / om)
+        if bn_ms:
+            bm = statistics.median(bn_ms)
+            tail += "   batch norm rows form %9.4f ms   batch norm / op %6.2f" % (bm, bm / om)
+        print("%-28s %-18s forms %d %d launches %d S %4d %4d %8.1f MB %9.4f ms %5.2f TB/s   copy %9.4f ms %5.2f TB/s   copy / op %5.2f   (min %5.2f max %5.2f)%s"
+              % (name, label, row, param, launches, rs, ps, nbytes * 1e-6, om, nbytes / om * 1e-9, cm, nbytes / cm * 1e-9, cm / om,
+                 min(c / p for c, p in zip(copy_ms, op_ms)), max(c / p for c, p in zip(copy_ms, op_ms)), tail), flush=True)
+
+
 def run_softmax(i, rounds, sets):
     """one shape: every operation alternates with a float4 copy of the same bytes and (row shapes) with the four-pass composition"""
     import ctypes as C_
@@ -632,6 +760,8 @@ if args.child:
         run_pool(int(args.child.split(":")[1]), args.rounds, args.sets)
     elif args.child.startswith("batchnorm:"):
         run_batchnorm(int(args.child.split(":")[1]), args.rounds, args.sets)
+    elif args.child.startswith("groupnorm:"):
+        run_groupnorm(int(args.child.split(":")[1]), args.rounds, args.sets)
     elif args.child.startswith("softmax:"):
         run_softmax(int(args.child.split(":")[1]), args.rounds, args.sets)
     elif args.child.startswith("fwd:"):
@@ -663,8 +793,16 @@ def child(what):
     return proc.returncode == 0
 
 
-kind = "batchnorm" if args.batchnorm else "softmax" if args.softmax else "pool" if args.pool else "act" if args.act else "fwd" if args.forward_only else "layer"
-if args.batchnorm:
+kind = "groupnorm" if args.groupnorm else "batchnorm" if args.batchnorm else "softmax" if args.softmax else "pool" if args.pool else "act" if args.act else "fwd" if args.forward_only else "layer"
+if args.groupnorm:
+    import hashlib
+    say("np_groupnorm_forward / np_groupnorm_backward with and without dgamma and dbeta (row form: 1 short rows, 2 a wave per row, 3 a workgroup per row, "
+        "4 split; parameter form: 0 none, 1 columns, 2 planes) against np_memcpy_d2d (the float4 copy) of the bytes the forms move and, for two 2-D shapes, "
+        "the forward pass against the composition from NDArray calls and against np_batchnorm_forward's rows form on the same array, alternating round by "
+        "round; fp32, ms per call, medians of %d rounds" % args.rounds)
+    say("sources: " + ", ".join("%s sha256 %s" % (f, hashlib.sha256((ROOT / "numpower_amd" / "csrc" / f).read_bytes()).hexdigest()[:16])
+                                for f in ("np_groupnorm.hip", "np_batchnorm.hip", "np_internal.h")))
+elif args.batchnorm:
     import hashlib
     say("np_batchnorm_forward (training, inference) / np_batchnorm_backward (form of the launch: 1 one launch, 2 split, 3 rows, 4 inference's apply kernel) "
         "against np_memcpy_d2d (the float4 copy) of the bytes the form moves and, for (N, C) shapes, the training forward against the composition from "
