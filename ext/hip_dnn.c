@@ -9,6 +9,7 @@
 #endif
 #include NUMPOWER_NDARRAY_HEADER
 
+#include <math.h>
 #include <stddef.h>
 
 #include "hip_dnn.h"
@@ -841,4 +842,102 @@ NDArray **NPH_GroupNorm_Backward(NDArray *x, NDArray *dy, int num_groups, NDArra
     if (x == NULL || dy == NULL || save_mean == NULL || save_invstd == NULL) return NULL;
     if (!groupnorm_of(x, dy, num_groups, gamma, NULL, save_mean, save_invstd, 0.0, &b, stat)) return NULL;
     return norm_backward(x, dy, gamma, save_mean, save_invstd, &b, &NDArray_SHAPE(x)[1], 1);
+}
+
+
+/* ---- scaled dot-product attention (hip_dnn.h): np_attention_forward / np_attention_backward ---- */
+
+typedef struct { size_t BH, Sq, Sk, D; float scale; } nph_attention;
+
+/* the checks of both directions, in the order of hip_dnn.h.  Absent operands are NULL.  0 after a raised error */
+static int attention_of(NDArray *q, NDArray *k, NDArray *v, NDArray *o, NDArray *dout, NDArray *smax, NDArray *ssum, float scale, nph_attention *a) {
+    const int ndim = NDArray_NDIM(q);
+    if (ndim < 2 || NDArray_NDIM(k) != ndim || NDArray_NDIM(v) != ndim) {
+        np_ext_throw(NPH_ATTN_MSG_NDIM);
+        return 0;
+    }
+    const int *qs = NDArray_SHAPE(q), *ks = NDArray_SHAPE(k), *vs = NDArray_SHAPE(v);
+    a->BH = 1;
+    for (int d = 0; d < ndim - 2; ++d) {
+        if (ks[d] != qs[d] || vs[d] != qs[d]) {
+            np_ext_throw(NPH_ATTN_MSG_LEADING);
+            return 0;
+        }
+        a->BH *= (size_t) (qs[d] > 0 ? qs[d] : 0);
+    }
+    if (ks[ndim - 1] != qs[ndim - 1] || vs[ndim - 1] != qs[ndim - 1]) {
+        np_ext_throw(NPH_ATTN_MSG_D);
+        return 0;
+    }
+    if (ks[ndim - 2] != vs[ndim - 2]) {
+        np_ext_throw(NPH_ATTN_MSG_SK);
+        return 0;
+    }
+    if (a->BH < 1 || qs[ndim - 2] < 1 || ks[ndim - 2] < 1 || qs[ndim - 1] < 1) {
+        np_ext_throw(NPH_ATTN_MSG_EMPTY);
+        return 0;
+    }
+    a->Sq = (size_t) qs[ndim - 2], a->Sk = (size_t) ks[ndim - 2], a->D = (size_t) qs[ndim - 1];
+    if (a->D > 128) {
+        np_ext_throw(NPH_ATTN_MSG_DMAX);
+        return 0;
+    }
+    if ((o != NULL && !has_shape(o, qs, ndim)) || (dout != NULL && !has_shape(dout, qs, ndim))) {
+        np_ext_throw(NPH_ATTN_MSG_OUTPUT);
+        return 0;
+    }
+    if ((smax != NULL && !has_shape(smax, qs, ndim - 1)) || (ssum != NULL && !has_shape(ssum, qs, ndim - 1))) {
+        np_ext_throw(NPH_ATTN_MSG_SAVED);
+        return 0;
+    }
+    if (scale > 0.0f && scale - scale != 0.0f) {
+        np_ext_throw(NPH_ATTN_MSG_SCALE);
+        return 0;
+    }
+    a->scale = scale > 0.0f ? scale : 1.0f / sqrtf((float) a->D);      /* not greater than zero, or a NaN: the default */
+    NDArray *others[6] = {k, v, o, dout, smax, ssum};
+    for (int i = 0; i < 6; ++i)
+        if (others[i] != NULL && NDArray_DEVICE(others[i]) != NDArray_DEVICE(q)) {
+            np_ext_throw(NPH_ATTN_MSG_DEVICE);
+            return 0;
+        }
+    if (NDArray_DEVICE(q) != NDARRAY_DEVICE_GPU) {
+        np_ext_throw(NPH_ATTN_MSG_CPU);
+        return 0;
+    }
+    return 1;
+}
+
+NDArray **NPH_Attention_Forward(NDArray *q, NDArray *k, NDArray *v, int causal, float scale) {
+    nph_attention a;
+    if (q == NULL || k == NULL || v == NULL || !attention_of(q, k, v, NULL, NULL, NULL, NULL, scale, &a)) return NULL;
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 3);
+    NDArray *o = empty_like_on_gpu(q), *smax = empty_of_ints_on_gpu(NDArray_SHAPE(q), NDArray_NDIM(q) - 1);
+    NDArray *ssum = empty_of_ints_on_gpu(NDArray_SHAPE(q), NDArray_NDIM(q) - 1);
+    if (rtns == NULL || o == NULL || smax == NULL || ssum == NULL) return batchnorm_drop(rtns, o, smax, ssum);
+    if (np_attention_forward(NDArray_FDATA(q), NDArray_FDATA(k), NDArray_FDATA(v), a.BH, a.Sq, a.Sk, a.D, causal, a.scale, NDArray_FDATA(o),
+                             NDArray_FDATA(smax), NDArray_FDATA(ssum)) != NP_OK) {
+        np_ext_throw_last();
+        return batchnorm_drop(rtns, o, smax, ssum);
+    }
+    rtns[0] = o, rtns[1] = smax, rtns[2] = ssum;
+    return rtns;
+}
+
+NDArray **NPH_Attention_Backward(NDArray *q, NDArray *k, NDArray *v, NDArray *o, NDArray *dout, NDArray *save_max, NDArray *save_sum, int causal,
+                                 float scale) {
+    nph_attention a;
+    if (q == NULL || k == NULL || v == NULL || o == NULL || dout == NULL || save_max == NULL || save_sum == NULL) return NULL;
+    if (!attention_of(q, k, v, o, dout, save_max, save_sum, scale, &a)) return NULL;
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 3);
+    NDArray *dq = empty_like_on_gpu(q), *dk = empty_like_on_gpu(k), *dv = empty_like_on_gpu(v);
+    if (rtns == NULL || dq == NULL || dk == NULL || dv == NULL) return batchnorm_drop(rtns, dq, dk, dv);
+    if (np_attention_backward(NDArray_FDATA(q), NDArray_FDATA(k), NDArray_FDATA(v), NDArray_FDATA(o), NDArray_FDATA(dout), NDArray_FDATA(save_max),
+                              NDArray_FDATA(save_sum), a.BH, a.Sq, a.Sk, a.D, causal, a.scale, NDArray_FDATA(dq), NDArray_FDATA(dk),
+                              NDArray_FDATA(dv)) != NP_OK) {
+        np_ext_throw_last();
+        return batchnorm_drop(rtns, dq, dk, dv);
+    }
+    rtns[0] = dq, rtns[1] = dk, rtns[2] = dv;
+    return rtns;
 }

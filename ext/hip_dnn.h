@@ -223,6 +223,30 @@ struct NDArray **NPH_GroupNorm_Forward(struct NDArray *x, int num_groups, struct
 struct NDArray **NPH_GroupNorm_Backward(struct NDArray *x, struct NDArray *dy, int num_groups, struct NDArray *gamma,
                                         struct NDArray *save_mean, struct NDArray *save_invstd);
 
+/* ---- scaled dot-product attention (np_attention_forward / _backward of include/np_hip.h) ----
+ * The reference has no attention, so tools/apply_with_hip.py inserts nothing; they are what a binding with these methods calls.
+ * q is (..., Sq, D), k and v are (..., Sk, D) with ndim >= 2; the leading axes must be equal across q, k and v and are flattened to
+ * BH (1 without leading axes).  o and dout have q's shape; the statistics have q's shape without its last axis.
+ * scale: a value that is not greater than zero (0, a negative number, a NaN) means the default 1 / sqrt(D).
+ * The messages, checked in this order (the output's, the gradient's and the statistics' by the backward pass alone): */
+#define NPH_ATTN_MSG_NDIM "dnn_attention: q, k and v must have at least 2 dimensions (..., S, D) and the same number of them"
+#define NPH_ATTN_MSG_LEADING "dnn_attention: the leading axes of q, k and v must be equal"
+#define NPH_ATTN_MSG_D "dnn_attention: q, k and v must have the same last axis D"
+#define NPH_ATTN_MSG_SK "dnn_attention: k and v must have the same number of rows Sk"
+#define NPH_ATTN_MSG_EMPTY "dnn_attention: an operand has no elements"
+#define NPH_ATTN_MSG_DMAX "dnn_attention: D, the last axis, must not be above 128"
+#define NPH_ATTN_MSG_OUTPUT "dnn_attention_backward: o and dout must have the shape of q"
+#define NPH_ATTN_MSG_SAVED "dnn_attention_backward: save_max and save_sum must have the shape of q without its last axis"
+#define NPH_ATTN_MSG_SCALE "dnn_attention: scale must be finite"
+#define NPH_ATTN_MSG_DEVICE "dnn_attention: the operands must be on the same device"
+#define NPH_ATTN_MSG_CPU "dnn_attention: operands are on the CPU; numpower_amd only computes on the GPU (call ->gpu() first)"
+
+/* a vector of three new GPU arrays: o in q's shape, save_max and save_sum in q's shape without its last axis */
+struct NDArray **NPH_Attention_Forward(struct NDArray *q, struct NDArray *k, struct NDArray *v, int causal, float scale);
+/* a vector of three new GPU arrays: dq in q's shape, dk in k's shape, dv in v's shape */
+struct NDArray **NPH_Attention_Backward(struct NDArray *q, struct NDArray *k, struct NDArray *v, struct NDArray *o, struct NDArray *dout,
+                                        struct NDArray *save_max, struct NDArray *save_sum, int causal, float scale);
+
 #ifdef __cplusplus
 }
 #endif

@@ -831,6 +831,50 @@ int np_groupnorm_backward(const float *x, const float *dy, const float *gamma, c
                           size_t N, size_t G, size_t D, size_t inner,
                           float *dx, float *dgamma /* P, may be NULL */, float *dbeta /* P, may be NULL */);
 
+/* ---- scaled dot-product attention (np_attention.hip; DESIGN.md "scaled dot-product attention") ------------
+ * o = softmax(q . k^T . scale) . v per slice, fused: the (Sq x Sk) score matrix is never stored.  Operands are contiguous fp32:
+ * q (BH, Sq, D), k (BH, Sk, D), v (BH, Sk, D), o (BH, Sq, D), the row statistics save_max and save_sum (BH, Sq).
+ * 1 <= D <= 128; Sq, Sk, BH >= 1.  For query row i of slice b the visible keys are all j, or j <= i when causal: the alignment is
+ * top-left, so every row sees at least key 0 whatever Sq and Sk are.
+ *   Score           s_ij = f32(chain_d(q_id . k_jd) . scale): the matrix core's fp32 fmaf chain from +0.0f over d ascending, then
+ *                   ONE fp32 multiply of the finished dot product by scale.  scale is a float argument.
+ *   Maximum         m_i = the maximum over the visible j, from -Inf; a NaN never wins (row_max of the softmax unit).
+ *   Sum             e_ij = fast_exp(s_ij - m_i); l_i = sum of e_ij, evaluated online over key tiles: a tile that raises the running
+ *                   maximum multiplies the running sum and the running output by ONE fast_exp of the step (the rescaling of
+ *                   online_add), then adds its own e against the new maximum.  Key tiles are always walked from key 0 in
+ *                   ascending order; the order of the keys inside a tile is a fixed permutation.
+ *   Output          o_id = (sum of e_ij . v_jd) / l_i: ONE correctly rounded division per element, no reciprocal.
+ *   Saved values    save_max = m_i, save_sum = l_i: what the online evaluation ended with.  Either may be NULL.
+ *   Backward        takes q, k, v, o, dout, save_max, save_sum.  p_ij = fast_exp(s_ij - m_i) / l_i, the same instruction sequence
+ *                   as the forward probability.  delta_i = sum over d of dout_id . o_id; dp_ij = chain_d(dout_id . v_jd);
+ *                   ds_ij = p_ij . (dp_ij - delta_i); dv_jd = sum over i of p_ij . dout_id; dk_jd = (sum over i of ds_ij . q_id) . scale;
+ *                   dq_id = (sum over j of ds_ij . k_jd) . scale.  Any of dq, dk, dv may be NULL; a kernel that would only
+ *                   produce NULL outputs is not launched.
+ *   Determinism     no float atomics; every reduction order is a function of the extents and the compile-time tile constants
+ *                   alone.  Results are bit-identical from run to run.
+ *   Independence    by bits: a slice alone equals the same slice inside a larger batch.  Without causal, the first n rows of a
+ *                   call equal the call on q[:, :n].  With causal, row i reads the key tiles 0 .. i / T alone (T = the key tile,
+ *                   np_debug_attention_bounds) and masks the keys above i to -Inf, which is what a key past Sk gets too: on
+ *                   finite operands row i equals row i of the call on q[:, :n], k[:, :c], v[:, :c] for every n > i and every
+ *                   c with min(c, i + 1) = min(Sk, i + 1); cutting both to i + 1 rounded up to T is one such call.
+ *   Special values  a NaN or +-Inf anywhere in q[b, i, :] makes row i of o, save_sum and dq NaN, and no other row of o.  A NaN in
+ *                   k[b, j] or v[b, j] makes every row that sees j NaN.  Under causal, rows i < j that share a key tile with j
+ *                   are NOT specified: 0 . NaN on the matrix core is NaN, as in a materialised computation, and skipped tiles never
+ *                   read it.  No other slice b is ever reached.  A row whose visible scores are all -Inf is NaN in o and in save_sum
+ *                   (e_ij = fast_exp(-Inf + Inf)); its save_max is -Inf.
+ *   Memory          the forward pass takes no scratch.  The backward pass takes pool scratch for delta (BH.Sq floats) and for
+ *                   nothing proportional to Sq.Sk; it is released on every path.  The work runs on the library stream.
+ *   Sizes           all size_t; every offset is formed in size_t, so BH.S.D may pass 2^31.  Sq or Sk at 2^31 or more, or BH times
+ *                   the tiles of a slice at 2^31 or more, does not fit the grid arithmetic and is refused.
+ * Convention as above: pointers are checked first, then the extents, the scale, the aliasing, then work begins.
+ * NP_ERR_INVALID before any device work: a null pointer (save_max, save_sum, dq, dk, dv may be NULL), a zero extent, D > 128, an
+ * extent that does not fit, a scale that is not finite, an output that overlaps an input or another output. */
+int np_attention_forward(const float *q, const float *k, const float *v, size_t BH, size_t Sq, size_t Sk, size_t D,
+                         int causal, float scale, float *o, float *save_max /* may be NULL */, float *save_sum /* may be NULL */);
+int np_attention_backward(const float *q, const float *k, const float *v, const float *o, const float *dout,
+                          const float *save_max, const float *save_sum, size_t BH, size_t Sq, size_t Sk, size_t D,
+                          int causal, float scale, float *dq, float *dk, float *dv);
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

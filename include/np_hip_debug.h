@@ -208,6 +208,17 @@ int np_debug_groupnorm_force_form(int row_form, int param_form);
  * of 256 lanes takes, bounds[3] = of 1024 lanes (the largest L of form 3), bounds[4] = the workgroups the slices aim for,
  * bounds[5] = the most slices, bounds[6] = the fewest workgroup steps a slice holds */
 int np_debug_groupnorm_bounds(size_t bounds[], int n);
+/* tests / tools: what the last np_attention_forward or np_attention_backward of the process launched.  d_class: the D
+ * instantiation (32, 64 or 128).  q_tile, k_tile: the query rows of a workgroup and the keys of a staged tile.  launches: the
+ * kernels it took (1 forward; backward 1 for delta, 1 for dk / dv unless both are NULL, 1 for dq unless it is NULL, 0 with all
+ * three NULL).  key_tiles: the key tiles the workgroup of the LAST query rows visits.  skipped: the (query workgroup, key tile)
+ * pairs of one slice that causal skips, 0 without causal.  Zeros before any launch; NP_ERR_INVALID on a null pointer.  Plain
+ * process globals. */
+int np_debug_attention_last_path(int *d_class, int *q_tile, int *k_tile, int *launches, size_t *key_tiles, size_t *skipped);
+/* the constants, n >= 7: bounds[0] = the query rows of a workgroup, bounds[1] = the keys of a staged tile (T of the causal
+ * rule), bounds[2 .. 4] = the largest D of the three instantiations, bounds[5] = the rows of a wave, bounds[6] = the keys of a
+ * workgroup of the dk / dv kernel */
+int np_debug_attention_bounds(size_t bounds[], int n);
 /* tests / tools: which kernel families the last np_reduce_axis or np_reduce_all(_dev) call of the process launched, the calls it
  * makes on its own partials included: the OR of the NP_REDUCE_PATH_ bits below (0 = none yet).  A plain process global, cleared
  * at the top of those entry points; calls the library makes itself (split-K GEMM folds, chain partials) overwrite it too. */

@@ -451,6 +451,15 @@ NDArray **NDArrayDNN_LayerNorm_Backward(NDArray *x, NDArray *dy, const int *norm
                                         NDArray *save_mean, NDArray *save_invstd);
 NDArray **NDArrayDNN_GroupNorm_Forward(NDArray *x, int num_groups, NDArray *gamma, NDArray *beta, double eps);
 NDArray **NDArrayDNN_GroupNorm_Backward(NDArray *x, NDArray *dy, int num_groups, NDArray *gamma, NDArray *save_mean, NDArray *save_invstd);
+/* Scaled dot-product attention (host/numpower_dnn.cpp; the reference has none): GPU operands q (..., Sq, D), k and v (..., Sk, D)
+ * with equal leading axes, D <= 128.  causal masks the keys above the row (top-left alignment).  scale: a value that is not greater
+ * than zero, or a NaN, means 1 / sqrt(D).  _Forward: a vector of three new arrays (o, save_max, save_sum), the statistics in q's
+ * shape without its last axis; _Backward, from q, k, v, o, the gradient dout of o and the saved statistics: (dq, dk, dv).  The caller
+ * frees the vector.  Views are made contiguous; NPH_Attention_* over np_attention_forward / _backward do the work.  Errors:
+ * ext/hip_dnn.h, NPH_ATTN_MSG_*. */
+NDArray **NDArrayDNN_Attention_Forward(NDArray *q, NDArray *k, NDArray *v, int causal, float scale);
+NDArray **NDArrayDNN_Attention_Backward(NDArray *q, NDArray *k, NDArray *v, NDArray *o, NDArray *dout, NDArray *save_max, NDArray *save_sum,
+                                        int causal, float scale);
 
 #ifdef __cplusplus
 }

@@ -199,4 +199,27 @@ NDArray **NDArrayDNN_GroupNorm_Backward(NDArray *x, NDArray *dy, int num_groups,
         x, dy, save_mean, save_invstd);
 }
 
+// Scaled dot-product attention (np_attention_forward / _backward), which the reference does not have either.
+// scale: not greater than zero, or a NaN, means 1 / sqrt(D).
+NDArray **NDArrayDNN_Attention_Forward(NDArray *q, NDArray *k, NDArray *v, int causal, float scale) {
+    if (!q || !k || !v) return nullptr;
+    return on_contiguous([=](NDArray *cq, NDArray *ck, NDArray *cv, NDArray *) -> NDArray ** { return NPH_Attention_Forward(cq, ck, cv, causal, scale); },
+                         q, k, v);
+}
+
+// (dq, dk, dv) from the layer's operands, its output, the gradient of the output and the statistics the forward pass saved
+NDArray **NDArrayDNN_Attention_Backward(NDArray *q, NDArray *k, NDArray *v, NDArray *o, NDArray *dout, NDArray *save_max, NDArray *save_sum,
+                                        int causal, float scale) {
+    if (!q || !k || !v || !o || !dout || !save_max || !save_sum) return nullptr;
+    return on_contiguous(
+        [=](NDArray *cq, NDArray *ck, NDArray *cv, NDArray *co) -> NDArray ** {
+            return on_contiguous(
+                [=](NDArray *cd, NDArray *cm, NDArray *cs, NDArray *) -> NDArray ** {
+                    return NPH_Attention_Backward(cq, ck, cv, co, cd, cm, cs, causal, scale);
+                },
+                dout, save_max, save_sum);
+        },
+        q, k, v, o);
+}
+
 }  // extern "C"

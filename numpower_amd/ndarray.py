@@ -170,6 +170,8 @@ def _load_host():
     sig["NDArrayDNN_LayerNorm_Backward"] = (C.POINTER(_P), [_P, _P, ip, C.c_int, _P, _P, _P])
     sig["NDArrayDNN_GroupNorm_Forward"] = (C.POINTER(_P), [_P, C.c_int, _P, _P, C.c_double])
     sig["NDArrayDNN_GroupNorm_Backward"] = (C.POINTER(_P), [_P, _P, C.c_int, _P, _P, _P])
+    sig["NDArrayDNN_Attention_Forward"] = (C.POINTER(_P), [_P, _P, _P, C.c_int, C.c_float])
+    sig["NDArrayDNN_Attention_Backward"] = (C.POINTER(_P), [_P] * 7 + [C.c_int, C.c_float])
     sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
     sig["NDArray_Eig"] = (C.POINTER(_P), [_P])
     sig["NDArray_Qr"] = (C.POINTER(_P), [_P])
@@ -1155,6 +1157,43 @@ class NDArray:
             raise Error("dnn_group_norm_backward: x, dy, save_mean and save_invstd must be arrays")
         p = [None if o is None else o._p for o in ops]
         return NDArray._norm_results(h, h.NDArrayDNN_GroupNorm_Backward(p[0], p[1], int(num_groups), p[2], p[3], p[4]))
+
+    @staticmethod
+    def _attention_scale(who, scale):
+        """None -> 0.0, which the layers below read as the default 1 / sqrt(D)"""
+        if scale is None:
+            return 0.0
+        if isinstance(scale, bool) or not isinstance(scale, (int, float, np.floating, np.integer)):
+            raise Error(who + ": scale must be a number or None")
+        if not float(scale) > 0.0:
+            raise Error(who + ": scale must be greater than zero (None: 1 / sqrt(D))")
+        return float(scale)
+
+    @staticmethod
+    def dnn_attention_forward(q, k, v, causal=False, scale=None):
+        """Scaled dot-product attention of GPU arrays: o = softmax(q . k^T . scale) . v per index of the leading
+        axes, fused, so the (Sq, Sk) scores are never stored.  q is (..., Sq, D), k and v are (..., Sk, D) with equal leading axes
+        and D <= 128.  causal=True lets row i see the keys j <= i (top-left alignment).  scale=None means 1 / sqrt(D).
+        Returns (o, save_max, save_sum): the row maximum of the scaled scores and the sum of exp(score - maximum), in q's shape
+        without its last axis, which dnn_attention_backward takes."""
+        h = _load_host()
+        sc = NDArray._attention_scale("dnn_attention_forward", scale)
+        ops = [NDArray._bn_operand(a) for a in (q, k, v)]
+        if any(o is None for o in ops):
+            raise Error("dnn_attention_forward: q, k and v must be arrays")
+        return NDArray._norm_results(h, h.NDArrayDNN_Attention_Forward(ops[0]._p, ops[1]._p, ops[2]._p, 1 if causal else 0, sc))
+
+    @staticmethod
+    def dnn_attention_backward(q, k, v, o, dout, save_max, save_sum, causal=False, scale=None):
+        """(dq, dk, dv) of dnn_attention_forward from its operands, its output o, the gradient dout of o and the statistics it
+        saved; causal and scale must be the forward call's.  The probabilities are recomputed tile by tile; the scratch is one
+        float per query row."""
+        h = _load_host()
+        sc = NDArray._attention_scale("dnn_attention_backward", scale)
+        ops = [NDArray._bn_operand(a) for a in (q, k, v, o, dout, save_max, save_sum)]
+        if any(a is None for a in ops):
+            raise Error("dnn_attention_backward: q, k, v, o, dout, save_max and save_sum must be arrays")
+        return NDArray._norm_results(h, h.NDArrayDNN_Attention_Backward(*[a._p for a in ops], 1 if causal else 0, sc))
 
     def copy(self):          # PHP_METHOD copy: NDArray_Copy on the array's own device
         return NDArray._wrap(_load_host().NDArray_Copy(self._p, C.cast(self._p, _P).contents.device))

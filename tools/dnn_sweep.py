@@ -47,6 +47,11 @@ bytes its form moves (forward 8 per element with the row in registers, 12 split;
 reduction) and, for the two 2-D shapes where it can be written, the forward pass with the composition from NDArray calls and with
 np_batchnorm_forward's rows form on the same array.  Reported: ms, TB/s, copy / op, composition / op and batch norm / op.  Writes
 profiles/dnn/groupnorm_sweep.log.
+--attention is the leg of scaled dot-product attention (np_attention.hip): forward, backward and backward with dq alone on
+ATTENTION_SHAPES, causal and not.  Reported: ms, the useful TFLOP/s (4.BH.Sq.Sk.D forward, 10.BH.Sq.Sk.D backward, halved under causal)
+and its fraction of the 157.3 TFLOP/s fp32 matrix peak; for the forward pass without causal also the ratio to the composition from
+NDArray calls (batched_matmul on a transposed k, a multiply, softmax, batched_matmul) and to np_sgemm_strided_batched on the two
+products alone, alternating round by round in one session.  Writes profiles/dnn/attention_sweep.log.
 
 Usage: python tools/dnn_sweep.py [--layers 0,1,...] [--rounds N] [--limit S] [--torch] [--out FILE]
        python tools/dnn_sweep.py --act [--layers ...]         the bias / activation leg
@@ -55,6 +60,7 @@ Usage: python tools/dnn_sweep.py [--layers 0,1,...] [--rounds N] [--limit S] [--
        python tools/dnn_sweep.py --softmax [--layers ...]     the softmax / cross-entropy leg
        python tools/dnn_sweep.py --batchnorm [--layers ...]   the batch-normalization leg
        python tools/dnn_sweep.py --groupnorm [--layers ...]   the layer / group normalization leg
+       python tools/dnn_sweep.py --attention [--layers ...]   the attention leg
        python tools/dnn_sweep.py --profile LAYER     three calls of each operation and nothing else, for a run under the kernel profiler"""
 import argparse
 import statistics
@@ -101,9 +107,14 @@ GROUPNORM_SHAPES = [("layer (65536, 1024)", (65536, 1, 1024, 1), True), ("layer 
                     ("group 32 (64, 64, 112, 112)", (64, 32, 2, 112 * 112), False), ("group 32 (256, 512, 7, 7)", (256, 32, 16, 49), False),
                     ("group 32 (2, 64, 112, 112)", (2, 32, 2, 112 * 112), False), ("instance (64, 64, 56, 56)", (64, 64, 1, 56 * 56), False)]
 
+# (BH, S, D): Sq = Sk = S
+ATTENTION_SHAPES = [(64, 512, 64), (64, 2048, 64), (16, 8192, 64), (64, 2048, 128), (512, 197, 64), (64, 2048, 32)]
+MATRIX_PEAK_TFLOPS = 157.3
+
 ap = argparse.ArgumentParser()
 ap.add_argument("--batchnorm", action="store_true")
 ap.add_argument("--groupnorm", action="store_true")
+ap.add_argument("--attention", action="store_true")
 ap.add_argument("--pool", action="store_true")
 ap.add_argument("--softmax", action="store_true")
 ap.add_argument("--sets", type=int, default=0, help="--pool: operand sets to rotate through (0: enough to pass 256 MiB)")
@@ -118,9 +129,9 @@ ap.add_argument("--profile", type=int, default=None)
 ap.add_argument("--child", default=None, help="internal: 'layer:<i>' or 'torch'")
 args = ap.parse_args()
 if args.layers is None:
-    args.layers = ",".join(str(i) for i in range(len(GROUPNORM_SHAPES if args.groupnorm else BATCHNORM_SHAPES if args.batchnorm else SOFTMAX_SHAPES if args.softmax else POOL_LAYERS if args.pool else LAYERS)))
+    args.layers = ",".join(str(i) for i in range(len(ATTENTION_SHAPES if args.attention else GROUPNORM_SHAPES if args.groupnorm else BATCHNORM_SHAPES if args.batchnorm else SOFTMAX_SHAPES if args.softmax else POOL_LAYERS if args.pool else LAYERS)))
 if args.out is None:
-    args.out = str(ROOT / "profiles" / "dnn" / ("groupnorm_sweep.log" if args.groupnorm else "batchnorm_sweep.log" if args.batchnorm else "softmax_sweep.log" if args.softmax else "pool2d_sweep.log" if args.pool else "conv2d_act_sweep.log" if args.act else
+    args.out = str(ROOT / "profiles" / "dnn" / ("attention_sweep.log" if args.attention else "groupnorm_sweep.log" if args.groupnorm else "batchnorm_sweep.log" if args.batchnorm else "softmax_sweep.log" if args.softmax else "pool2d_sweep.log" if args.pool else "conv2d_act_sweep.log" if args.act else
                                                "conv2d_forward_only.log" if args.forward_only else "conv2d_sweep.log"))
 LARGE = (256, 128, 3136)                        # (N, F, P) of the large case of --act: 1.03e8 elements
 HBM_TBS = 8.0
@@ -615,6 +626,71 @@ def run_groupnorm(i, rounds, sets):
                  min(c / p for c, p in zip(copy_ms, op_ms)), max(c / p for c, p in zip(copy_ms, op_ms)), tail), flush=True)
 
 
+def run_attention(i, rounds):
+    """one shape, causal and not: forward, backward, backward with dq alone; the forward pass without causal also against the NDArray
+    composition and against np_sgemm_strided_batched on the two products alone, alternating round by round"""
+    import numpy as np
+    D, lib, check, ramp, _ = _setup()
+    from numpower_amd._lib import Timer
+    from numpower_amd.ndarray import NDArray as nd
+    t = Timer()
+    BH, S, Dh = ATTENTION_SHAPES[i]
+    n, scale = BH * S * Dh, float(np.float32(1.0) / np.sqrt(np.float32(Dh)))
+    rng = np.random.default_rng(i)
+    host = [np.resize(rng.standard_normal(1 << 20).astype(np.float32), n) for _ in range(4)]
+    q, k, v, dout = (D.DeviceArray.from_host(h) for h in host)
+    o, dq, dk, dv = (D.DeviceArray((n,)) for _ in range(4))
+    smax, ssum = D.DeviceArray((BH * S,)), D.DeviceArray((BH * S,))
+    kt = D.DeviceArray.from_host(np.ascontiguousarray(host[1].reshape(BH, S, Dh).transpose(0, 2, 1)).reshape(-1))      # k^T, made outside the timing
+    scores = D.DeviceArray((BH * S * S,))
+    gq, gk, gv = (nd.array(h.reshape(BH, S, Dh)).gpu() for h in host[:3])
+
+    def composition():
+        return nd.batched_matmul(nd.softmax(nd.batched_matmul(gq, nd.transpose(gk, (0, 2, 1))) * scale, -1), gv)
+
+    def products():
+        check(lib.np_sgemm_strided_batched(BH, S, S, Dh, q.ptr, S * Dh, kt.ptr, Dh * S, scores.ptr, S * S))
+        check(lib.np_sgemm_strided_batched(BH, S, Dh, S, scores.ptr, S * S, v.ptr, S * Dh, o.ptr, S * Dh))
+
+    def timed(fn, reps):
+        t.start()
+        for _ in range(reps):
+            fn()
+        t.stop()
+        return t.elapsed_ms() / reps
+
+    ramp()
+    for causal in (0, 1):
+        forward = lambda: check(lib.np_attention_forward(q.ptr, k.ptr, v.ptr, BH, S, S, Dh, causal, scale, o.ptr, smax.ptr, ssum.ptr))
+        backward = lambda: check(lib.np_attention_backward(q.ptr, k.ptr, v.ptr, o.ptr, dout.ptr, smax.ptr, ssum.ptr, BH, S, S, Dh, causal, scale, dq.ptr, dk.ptr, dv.ptr))
+        backward_dq = lambda: check(lib.np_attention_backward(q.ptr, k.ptr, v.ptr, o.ptr, dout.ptr, smax.ptr, ssum.ptr, BH, S, S, Dh, causal, scale, dq.ptr, None, None))
+        forward()
+        for label, fn, flop, against in (("forward", forward, 4.0 * BH * S * S * Dh, not causal), ("backward", backward, 10.0 * BH * S * S * Dh, False),
+                                         ("backward, dq alone", backward_dq, 6.0 * BH * S * S * Dh, False)):
+            flop = flop / 2 if causal else flop
+            others = [composition, products] if against else []
+            for f in [fn] + others:                  # warm
+                for _ in range(2):
+                    f()
+            D.sync()
+            t0 = time.time()
+            fn()
+            D.sync()
+            reps = max(3, min(100, int(0.05 / max(time.time() - t0, 1e-5))))
+            op_ms, other_ms = [], [[] for _ in others]
+            for _ in range(rounds):                   # alternating in one session
+                op_ms.append(timed(fn, reps))
+                for f, ms in zip(others, other_ms):
+                    ms.append(timed(f, max(2, reps // 4)))
+            om = statistics.median(op_ms)
+            tail = ""
+            if against:
+                cm, pm = (statistics.median(ms) for ms in other_ms)
+                tail = "   composition %9.4f ms   composition / fused %6.2f   two products alone %9.4f ms   products / fused %6.2f" % (cm, cm / om, pm, pm / om)
+            print("(%d, %d, %d) %-10s %-19s %9.4f ms %7.2f TFLOP/s %6.3f of the matrix peak (min %.4f max %.4f ms)%s"
+                  % (BH, S, Dh, "causal" if causal else "full", label, om, flop / om * 1e-9, flop / om * 1e-9 / MATRIX_PEAK_TFLOPS, min(op_ms), max(op_ms), tail), flush=True)
+
+
 def run_softmax(i, rounds, sets):
     """one shape: every operation alternates with a float4 copy of the same bytes and (row shapes) with the four-pass composition"""
     import ctypes as C_
@@ -760,6 +836,8 @@ if args.child:
         run_pool(int(args.child.split(":")[1]), args.rounds, args.sets)
     elif args.child.startswith("batchnorm:"):
         run_batchnorm(int(args.child.split(":")[1]), args.rounds, args.sets)
+    elif args.child.startswith("attention:"):
+        run_attention(int(args.child.split(":")[1]), args.rounds)
     elif args.child.startswith("groupnorm:"):
         run_groupnorm(int(args.child.split(":")[1]), args.rounds, args.sets)
     elif args.child.startswith("softmax:"):
@@ -793,8 +871,16 @@ def child(what):
     return proc.returncode == 0
 
 
-kind = "groupnorm" if args.groupnorm else "batchnorm" if args.batchnorm else "softmax" if args.softmax else "pool" if args.pool else "act" if args.act else "fwd" if args.forward_only else "layer"
-if args.groupnorm:
+kind = "attention" if args.attention else "groupnorm" if args.groupnorm else "batchnorm" if args.batchnorm else "softmax" if args.softmax else "pool" if args.pool else "act" if args.act else "fwd" if args.forward_only else "layer"
+if args.attention:
+    import hashlib
+    say("np_attention_forward / np_attention_backward with all three gradients and with dq alone, Sq = Sk = S, causal and not; useful TFLOP/s from 4.BH.S.S.D "
+        "forward and 10.BH.S.S.D backward (6 for dq alone: its three products), halved under causal, against the %.1f TFLOP/s fp32 matrix peak; the forward pass without causal "
+        "against the composition from NDArray calls and np_sgemm_strided_batched on the two products alone, alternating round by round; fp32, ms per call, "
+        "medians of %d rounds" % (MATRIX_PEAK_TFLOPS, args.rounds))
+    say("sources: " + ", ".join("%s sha256 %s" % (f, hashlib.sha256((ROOT / "numpower_amd" / "csrc" / f).read_bytes()).hexdigest()[:16])
+                                for f in ("np_attention.hip", "np_elementwise_ops.h", "np_internal.h")))
+elif args.groupnorm:
     import hashlib
     say("np_groupnorm_forward / np_groupnorm_backward with and without dgamma and dbeta (row form: 1 short rows, 2 a wave per row, 3 a workgroup per row, "
         "4 split; parameter form: 0 none, 1 columns, 2 planes) against np_memcpy_d2d (the float4 copy) of the bytes the forms move and, for two 2-D shapes, "
