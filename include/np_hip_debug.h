@@ -364,6 +364,50 @@ int np_sgemm_debug_sub_ld(size_t M, size_t N, size_t K, const float *A, size_t l
 #define NP_LAYOUT_PATH_GATHER 7u       /* permute_gather_kernel<I, W> */
 #define NP_LAYOUT_PATH_COPY2D 8u       /* copy2d_kernel<V> */
 int np_debug_layout_last_record(unsigned *host_record, unsigned capacity, unsigned *host_count);
+/* tests / tools: what the last np_argreduce call of the process launched: ONE record of NP_ARG_RECORD_WORDS unsigned words naming the
+ * streaming kernel and the fold of its partials.  Cleared at the top of np_argreduce; the early returns (outer == 0, inner == 0) and
+ * the refusals leave it cleared: *host_count = 0 then, else 1.  `capacity` counts records: min(count, capacity) records are written.
+ * Host stores at the launch sites: no device work, no synchronisation, no kernel argument; plain process globals, meaningful only
+ * while one thread calls np_argreduce.  A record:
+ *   word 0      NP_ARG_KERNEL: NP_ARG_KERNEL_*, the streaming kernel
+ *   word 1      NP_ARG_TEMPLATE: its template argument besides IS_MAX — ROWS_GROUP: L; COLS_TILE: FINAL; else 0
+ *   words 2-4   NP_ARG_GRID_X / _Y / _Z: its grid
+ *   word 5      NP_ARG_CHUNKS: the pieces the axis is cut into (slabs of the flat walks, chunks of ROWS, COLS_TILE and CHUNKS; 1 for
+ *               the kernels that write the result themselves)
+ *   word 6      NP_ARG_CHUNK_LEN: elements of the axis per piece (rows_per_block of the flat walks; the axis itself where chunks = 1
+ *               except COLS_TILE, which reports the chunk_len it passes)
+ *   word 7      NP_ARG_XCD_RUNS: COLS_TILE's xcd_runs argument, else 0
+ *   word 8      NP_ARG_FOLD: NP_ARG_FOLD_*, the kernel that folds the partials (NONE: the streaming kernel wrote the indices)
+ *   word 9      NP_ARG_FOLD_COLS: COLS of argreduce_fold_cols_kernel, else 0
+ *   words 10-12 NP_ARG_FOLD_GRID_X / _Y / _Z: the fold's grid (0, 0, 0 without one) */
+#define NP_ARG_RECORD_WORDS 16u
+#define NP_ARG_KERNEL 0
+#define NP_ARG_TEMPLATE 1
+#define NP_ARG_GRID_X 2
+#define NP_ARG_GRID_Y 3
+#define NP_ARG_GRID_Z 4
+#define NP_ARG_CHUNKS 5
+#define NP_ARG_CHUNK_LEN 6
+#define NP_ARG_XCD_RUNS 7
+#define NP_ARG_FOLD 8
+#define NP_ARG_FOLD_COLS 9
+#define NP_ARG_FOLD_GRID_X 10
+#define NP_ARG_FOLD_GRID_Y 11
+#define NP_ARG_FOLD_GRID_Z 12
+#define NP_ARG_KERNEL_NONE 0u
+#define NP_ARG_KERNEL_ROWS_GROUP 1u     /* argreduce_rows_group<L> */
+#define NP_ARG_KERNEL_ROWS_WAVE 2u      /* argreduce_rows_wave */
+#define NP_ARG_KERNEL_ROWS 3u           /* argreduce_rows_kernel */
+#define NP_ARG_KERNEL_SMALL_INNER 4u    /* argreduce_small_inner */
+#define NP_ARG_KERNEL_SMALL_INNER4 5u   /* argreduce_small_inner4 */
+#define NP_ARG_KERNEL_COLS_TILE 6u      /* argreduce_cols_tile<FINAL> */
+#define NP_ARG_KERNEL_CHUNKS 7u         /* argreduce_chunks_kernel */
+#define NP_ARG_KERNEL_GENERIC 8u        /* argreduce_generic_kernel */
+#define NP_ARG_FOLD_NONE 0u
+#define NP_ARG_FOLD_THREAD 1u           /* argreduce_fold_kernel, a thread per output */
+#define NP_ARG_FOLD_BLOCK 2u            /* argreduce_fold_block_kernel, a workgroup per output */
+#define NP_ARG_FOLD_COLS_KERNEL 3u      /* argreduce_fold_cols_kernel<COLS> */
+int np_debug_argreduce_last_record(unsigned *host_record, unsigned capacity, unsigned *host_count);
 
 #ifdef __cplusplus
 }

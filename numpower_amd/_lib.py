@@ -185,6 +185,7 @@ PROTOTYPES = {
     "np_elementwise_set_variant": (C.c_int, [C.c_int]),
     "np_layout_set_variant": (C.c_int, [C.c_int]),
     "np_debug_layout_last_record": (C.c_int, [C.POINTER(C.c_uint), C.c_uint, C.POINTER(C.c_uint)]),
+    "np_debug_argreduce_last_record": (C.c_int, [C.POINTER(C.c_uint), C.c_uint, C.POINTER(C.c_uint)]),
     "np_reduce_set_variant": (C.c_int, [C.c_int]),
     "np_select_set_variant": (C.c_int, [C.c_int]),
     "np_runtime_set_variant": (C.c_int, [C.c_int]),

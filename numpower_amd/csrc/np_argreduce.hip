@@ -3,6 +3,7 @@
 // launch_arg_fold and the entry point with its planner, in that order.  Value reductions: np_reduce.hip.
 #include <float.h>
 #include <math.h>
+#include <string.h>
 
 #include "np_internal.h"
 
@@ -699,6 +700,34 @@ __global__ __launch_bounds__(256) void argreduce_fold_cols_kernel(const float *_
 // K_<IS_MAX[, further template arguments]> for this call's is_max: a launch site selects its kernel once and launches once
 #define ARG_KERNEL(K_, ...) (is_max ? K_<true, ##__VA_ARGS__> : K_<false, ##__VA_ARGS__>)
 
+// np_debug_argreduce_last_record: the NP_ARG_* record (np_hip_debug.h) of what the last np_argreduce call launched; cleared at the
+// top of the entry point, one host store per launch site.
+unsigned g_arg_record[NP_ARG_RECORD_WORDS];
+unsigned g_arg_count = 0;
+void arg_clear() {
+    memset(g_arg_record, 0, sizeof g_arg_record);
+    g_arg_count = 0;
+}
+void arg_note(unsigned kernel, unsigned targ, dim3 grid, size_t chunks, size_t chunk_len, unsigned xcd_runs) {
+    memset(g_arg_record, 0, sizeof g_arg_record);
+    g_arg_record[NP_ARG_KERNEL] = kernel;
+    g_arg_record[NP_ARG_TEMPLATE] = targ;
+    g_arg_record[NP_ARG_GRID_X] = grid.x;
+    g_arg_record[NP_ARG_GRID_Y] = grid.y;
+    g_arg_record[NP_ARG_GRID_Z] = grid.z;
+    g_arg_record[NP_ARG_CHUNKS] = (unsigned)chunks;
+    g_arg_record[NP_ARG_CHUNK_LEN] = (unsigned)chunk_len;
+    g_arg_record[NP_ARG_XCD_RUNS] = xcd_runs;
+    g_arg_count = 1;
+}
+void arg_note_fold(unsigned fold, unsigned cols, dim3 grid) {
+    g_arg_record[NP_ARG_FOLD] = fold;
+    g_arg_record[NP_ARG_FOLD_COLS] = cols;
+    g_arg_record[NP_ARG_FOLD_GRID_X] = grid.x;
+    g_arg_record[NP_ARG_FOLD_GRID_Y] = grid.y;
+    g_arg_record[NP_ARG_FOLD_GRID_Z] = grid.z;
+}
+
 // fold [outer][chunks][inner] partials: thread per output for short chunk lists, workgroup per output
 // for long ones
 int launch_arg_fold(int is_max, const float *pv, const unsigned *pi, float *out, size_t outputs, size_t chunks, size_t inner) {
@@ -710,16 +739,19 @@ int launch_arg_fold(int is_max, const float *pv, const unsigned *pi, float *out,
         const auto k = cols == 64   ? ARG_KERNEL(argreduce_fold_cols_kernel, 64)
                        : cols == 16 ? ARG_KERNEL(argreduce_fold_cols_kernel, 16)
                                     : ARG_KERNEL(argreduce_fold_cols_kernel, 4);
+        arg_note_fold(NP_ARG_FOLD_COLS_KERNEL, (unsigned)cols, grid);
         k<<<grid, 256, 0, s>>>(pv, pi, out, (unsigned)chunks, inner);
         NP_LAUNCH_CHECK("argreduce_fold_cols_kernel");
         return NP_OK;
     }
     if (chunks > 64 && outputs <= 0x7fffffffu) {
+        arg_note_fold(NP_ARG_FOLD_BLOCK, 0, dim3((unsigned)outputs));
         ARG_KERNEL(argreduce_fold_block_kernel)<<<(unsigned)outputs, 256, 0, s>>>(pv, pi, out, (unsigned)chunks, inner);
         NP_LAUNCH_CHECK("argreduce_fold_block_kernel");
         return NP_OK;
     }
     const unsigned fgrid = (unsigned)((outputs + 255) / 256);
+    arg_note_fold(NP_ARG_FOLD_THREAD, 0, dim3(fgrid));
     ARG_KERNEL(argreduce_fold_kernel)<<<fgrid, 256, 0, s>>>(pv, pi, out, outputs, (unsigned)chunks, inner);
     NP_LAUNCH_CHECK("argreduce_fold_kernel");
     return NP_OK;
@@ -729,7 +761,16 @@ int launch_arg_fold(int is_max, const float *pv, const unsigned *pi, float *out,
 
 extern "C" {
 
+int np_debug_argreduce_last_record(unsigned *host_record, unsigned capacity, unsigned *host_count) {
+    if (!host_count || (capacity && !host_record)) return np::fail(NP_ERR_INVALID, "np_debug_argreduce_last_record: null pointer");
+    *host_count = g_arg_count;
+    if (g_arg_count && capacity)
+        for (unsigned w = 0; w < NP_ARG_RECORD_WORDS; ++w) host_record[w] = g_arg_record[w];
+    return NP_OK;
+}
+
 int np_argreduce(int is_max, const float *in, size_t outer, size_t axis_len, size_t inner, float *out) {
+    arg_clear();
     if (outer == 0 || inner == 0) return NP_OK;
     if (axis_len == 0) return np::fail(NP_ERR_INVALID, "attempt to get %s of an empty sequence", is_max ? "argmax" : "argmin");
     if (!in || !out) return np::fail(NP_ERR_INVALID, "np_argreduce: null pointer");
@@ -751,6 +792,7 @@ int np_argreduce(int is_max, const float *in, size_t outer, size_t axis_len, siz
                 case 16: k = ARG_KERNEL(argreduce_rows_group, 16); break;
                 default: break;   // 32 lanes per row
             }
+            arg_note(NP_ARG_KERNEL_ROWS_GROUP, (unsigned)L, dim3((unsigned)blocks), 1, axis_len, 0);
             k<<<(unsigned)blocks, 256, 0, s>>>(in, out, outer, (unsigned)axis_len);
             NP_LAUNCH_CHECK("argreduce_rows_group");
             return NP_OK;
@@ -759,6 +801,7 @@ int np_argreduce(int is_max, const float *in, size_t outer, size_t axis_len, siz
     if (inner == 1 && axis_len <= 32768 && outer >= (size_t)np::num_cus() * 16 && (outer + 3) / 4 <= 0x7fffffffu) {
         // many rows of a few hundred to a few thousand elements: one wave per row, one launch, no partials
         const unsigned grid = (unsigned)((outer + 3) / 4);
+        arg_note(NP_ARG_KERNEL_ROWS_WAVE, 0, dim3(grid), 1, axis_len, 0);
         ARG_KERNEL(argreduce_rows_wave)<<<grid, 256, 0, s>>>(in, out, outer, (unsigned)axis_len);
         NP_LAUNCH_CHECK("argreduce_rows_wave");
         return NP_OK;
@@ -777,6 +820,7 @@ int np_argreduce(int is_max, const float *in, size_t outer, size_t axis_len, siz
         if (int rc = pv.alloc(outer * chunks * sizeof(float))) return rc;
         if (int rc = pi.alloc(outer * chunks * sizeof(unsigned))) return rc;
         const unsigned grid = (unsigned)(outer * chunks);
+        arg_note(NP_ARG_KERNEL_ROWS, 0, dim3(grid), chunks, (axis_len + chunks - 1) / chunks, 0);
         ARG_KERNEL(argreduce_rows_kernel)<<<grid, 256, 0, s>>>(in, (float *)pv.ptr, (unsigned *)pi.ptr, (unsigned)axis_len, (unsigned)chunks);
         NP_LAUNCH_CHECK("argreduce_rows_kernel");
         return launch_arg_fold(is_max, (const float *)pv.ptr, (const unsigned *)pi.ptr, out, outer, chunks, 1);
@@ -804,6 +848,7 @@ int np_argreduce(int is_max, const float *in, size_t outer, size_t axis_len, siz
             const dim3 grid((unsigned)blocks, (unsigned)outer);
             // (float4 column groups or single columns: the same signature, the row width counted in the kernel's own unit)
             const auto k = groups4 ? ARG_KERNEL(argreduce_small_inner4) : ARG_KERNEL(argreduce_small_inner);
+            arg_note(groups4 ? NP_ARG_KERNEL_SMALL_INNER4 : NP_ARG_KERNEL_SMALL_INNER, 0, grid, blocks, rows_per_block, 0);
             k<<<grid, 256, 0, s>>>(in, (float *)pv.ptr, (unsigned *)pi.ptr, (unsigned)axis_len, (unsigned)(groups4 ? inner / 4 : inner), (unsigned)rows_per_block);
             NP_LAUNCH_CHECK("argreduce_small_inner");
             return launch_arg_fold(is_max, (const float *)pv.ptr, (const unsigned *)pi.ptr, out, total, blocks, inner);
@@ -842,6 +887,7 @@ int np_argreduce(int is_max, const float *in, size_t outer, size_t axis_len, siz
             const bool rows_are_lines = (inner * sizeof(float)) % 128 == 0 && ((uintptr_t)in & 127u) == 0;
             const unsigned xcd_runs = (!rows_are_lines && tiles > 1 && tiles * chunks * outer < (size_t(1) << 31) && !np::g_xcd_runs_off) ? 1u : 0u;
             if (chunks == 1) {
+                arg_note(NP_ARG_KERNEL_COLS_TILE, 1, grid, chunks, chunk_len, xcd_runs);
                 ARG_KERNEL(argreduce_cols_tile, true)<<<grid, 256, 0, s>>>(in, nullptr, nullptr, out, (unsigned)axis_len, (unsigned)inner, (unsigned)chunk_len, xcd_runs);
                 NP_LAUNCH_CHECK("argreduce_cols_tile");
                 return NP_OK;
@@ -849,6 +895,7 @@ int np_argreduce(int is_max, const float *in, size_t outer, size_t axis_len, siz
             np::Scratch pv, pi;
             if (int rc = pv.alloc(total * chunks * sizeof(float))) return rc;
             if (int rc = pi.alloc(total * chunks * sizeof(unsigned))) return rc;
+            arg_note(NP_ARG_KERNEL_COLS_TILE, 0, grid, chunks, chunk_len, xcd_runs);
             ARG_KERNEL(argreduce_cols_tile, false)<<<grid, 256, 0, s>>>(in, (float *)pv.ptr, (unsigned *)pi.ptr, nullptr, (unsigned)axis_len, (unsigned)inner, (unsigned)chunk_len, xcd_runs);
             NP_LAUNCH_CHECK("argreduce_cols_tile");
             return launch_arg_fold(is_max, (const float *)pv.ptr, (const unsigned *)pi.ptr, out, total, chunks, inner);
@@ -870,6 +917,7 @@ int np_argreduce(int is_max, const float *in, size_t outer, size_t axis_len, siz
             size_t blocks = (total * chunks + 255) / 256;
             const size_t cap = (size_t)np::num_cus() * 16;
             if (blocks > cap) blocks = cap;
+            arg_note(NP_ARG_KERNEL_CHUNKS, 0, dim3((unsigned)blocks), chunks, chunk_len, 0);
             ARG_KERNEL(argreduce_chunks_kernel)<<<(unsigned)blocks, 256, 0, s>>>(in, (float *)pv.ptr, (unsigned *)pi.ptr, outer, (unsigned)axis_len, inner, (unsigned)chunks, (unsigned)chunk_len);
             NP_LAUNCH_CHECK("argreduce_chunks_kernel");
             return launch_arg_fold(is_max, (const float *)pv.ptr, (const unsigned *)pi.ptr, out, total, chunks, inner);
@@ -878,6 +926,7 @@ int np_argreduce(int is_max, const float *in, size_t outer, size_t axis_len, siz
     size_t blocks = (total + 255) / 256;
     const size_t cap = (size_t)np::num_cus() * 16;
     if (blocks > cap) blocks = cap;
+    arg_note(NP_ARG_KERNEL_GENERIC, 0, dim3((unsigned)blocks), 1, axis_len, 0);
     ARG_KERNEL(argreduce_generic_kernel)<<<(unsigned)blocks, 256, 0, s>>>(in, out, outer, (unsigned)axis_len, inner);
     NP_LAUNCH_CHECK("argreduce_generic_kernel");
     return NP_OK;
