@@ -941,3 +941,149 @@ NDArray **NPH_Attention_Backward(NDArray *q, NDArray *k, NDArray *v, NDArray *o,
     rtns[0] = dq, rtns[1] = dk, rtns[2] = dv;
     return rtns;
 }
+
+
+/* ---- optimizer steps (hip_dnn.h): np_sgd_step / np_adam_step / np_grad_norm ---- */
+
+/* the device pointers and element counts of a call's lists, one block that is released on every path */
+typedef struct { void *block; float **p, **g, **s1, **s2; size_t *n; } nph_optim;
+
+static void optim_release(nph_optim *o) {
+    if (o->block != NULL) NPH_RELEASE(o->block);
+    o->block = NULL;
+}
+
+/* the checks the three calls share, in the order of hip_dnn.h; lists[0] leads (the parameters, or the gradients of the norm), a
+ * NULL list is absent; refusal: the message of the call's first bad parameter, or NULL.  Fills o.  0 after a raised error */
+static int optim_of(NDArray **lists[4], const int lens[4], NDArray *grad_scale, int grad_scale_index, const char *refusal, nph_optim *o) {
+    o->block = NULL;
+    const int T = lens[0];
+    for (int l = 1; l < 4; ++l)
+        if (lists[l] != NULL && lens[l] != T) {
+            np_ext_throw(NPH_OPTIM_MSG_LENGTHS);
+            return 0;
+        }
+    for (int l = 0; l < 4; ++l)
+        for (int t = 0; lists[l] != NULL && t < T; ++t)
+            if (lists[l][t] == NULL) {
+                np_ext_throw(NPH_OPTIM_MSG_NULL);
+                return 0;
+            }
+    if (lists[0] == NULL || T < 1) {
+        np_ext_throw(NPH_OPTIM_MSG_EMPTY_LIST);
+        return 0;
+    }
+    for (int t = 0; t < T; ++t) {
+        const long n = NDArray_NUMELEMENTS(lists[0][t]);
+        if (n < 1) {
+            np_ext_throw(NPH_OPTIM_MSG_EMPTY);
+            return 0;
+        }
+        for (int l = 1; l < 4; ++l)
+            if (lists[l] != NULL && NDArray_NUMELEMENTS(lists[l][t]) != n) {
+                np_ext_throw(NDArray_NUMELEMENTS(lists[l][t]) < 1 ? NPH_OPTIM_MSG_EMPTY : NPH_OPTIM_MSG_COUNT);
+                return 0;
+            }
+    }
+    if (grad_scale != NULL && (grad_scale_index < 0 || (long) grad_scale_index >= NDArray_NUMELEMENTS(grad_scale))) {
+        np_ext_throw(NPH_OPTIM_MSG_SCALE);
+        return 0;
+    }
+    if (refusal != NULL) {
+        np_ext_throw(refusal);
+        return 0;
+    }
+    const int device = NDArray_DEVICE(lists[0][0]);
+    for (int l = 0; l < 4; ++l)
+        for (int t = 0; lists[l] != NULL && t < T; ++t)
+            if (NDArray_DEVICE(lists[l][t]) != device) {
+                np_ext_throw(NPH_OPTIM_MSG_DEVICE);
+                return 0;
+            }
+    if (grad_scale != NULL && NDArray_DEVICE(grad_scale) != device) {
+        np_ext_throw(NPH_OPTIM_MSG_DEVICE);
+        return 0;
+    }
+    if (device != NDARRAY_DEVICE_GPU) {
+        np_ext_throw(NPH_OPTIM_MSG_CPU);
+        return 0;
+    }
+    o->block = NPH_ALLOC((size_t) T * (4 * sizeof(float *) + sizeof(size_t)));
+    if (o->block == NULL) return 0;
+    o->p = (float **) o->block, o->g = o->p + T, o->s1 = o->g + T, o->s2 = o->s1 + T, o->n = (size_t *) (o->s2 + T);
+    float **into[4] = {o->p, o->g, o->s1, o->s2};
+    for (int t = 0; t < T; ++t) {
+        o->n[t] = (size_t) NDArray_NUMELEMENTS(lists[0][t]);
+        for (int l = 0; l < 4; ++l) into[l][t] = lists[l] != NULL ? NDArray_FDATA(lists[l][t]) : NULL;
+    }
+    return 1;
+}
+
+static int optim_finite_nonneg(double v) { return v >= 0.0 && v <= 1.79769313486231570815e308; }
+
+int NPH_SGD_Step(NDArray **params, int n_params, NDArray **grads, int n_grads, NDArray **bufs, int n_bufs, double lr, double momentum,
+                 double dampening, double weight_decay, int nesterov, int first_step, NDArray *grad_scale, int grad_scale_index) {
+    nph_optim o;
+    NDArray **lists[4] = {params, grads, bufs, NULL};
+    const int lens[4] = {n_params, grads != NULL ? n_grads : -1, n_bufs, 0};
+    if (momentum != 0.0 && bufs == NULL) {
+        np_ext_throw(params != NULL && grads != NULL && n_params == n_grads ? NPH_OPTIM_MSG_BUFFERS : NPH_OPTIM_MSG_LENGTHS);
+        return 0;
+    }
+    if (grads == NULL) {
+        np_ext_throw(NPH_OPTIM_MSG_LENGTHS);
+        return 0;
+    }
+    const char *msg = !optim_finite_nonneg(lr) ? NPH_OPTIM_MSG_LR
+                      : !optim_finite_nonneg(weight_decay) ? NPH_OPTIM_MSG_WEIGHT_DECAY
+                      : !(momentum >= 0.0 && momentum <= 1.0) ? NPH_OPTIM_MSG_MOMENTUM
+                      : !(dampening >= 0.0 && dampening <= 1.0) ? NPH_OPTIM_MSG_DAMPENING
+                      : (nesterov && (momentum == 0.0 || dampening != 0.0)) ? NPH_OPTIM_MSG_NESTEROV : NULL;
+    if (!optim_of(lists, lens, grad_scale, grad_scale_index, msg, &o)) return 0;
+    const int ok = np_sgd_step((float *const *) o.p, (const float *const *) o.g, momentum != 0.0 ? (float *const *) o.s1 : NULL, o.n, (size_t) n_params,
+                               lr, momentum, dampening, weight_decay, nesterov, first_step,
+                               grad_scale != NULL ? NDArray_FDATA(grad_scale) + grad_scale_index : NULL) == NP_OK;
+    if (!ok) np_ext_throw_last();
+    optim_release(&o);
+    return ok;
+}
+
+int NPH_Adam_Step(NDArray **params, int n_params, NDArray **grads, int n_grads, NDArray **exp_avg, int n_exp_avg, NDArray **exp_avg_sq,
+                  int n_exp_avg_sq, long step, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                  NDArray *grad_scale, int grad_scale_index) {
+    nph_optim o;
+    NDArray **lists[4] = {params, grads, exp_avg, exp_avg_sq};
+    const int lens[4] = {n_params, n_grads, n_exp_avg, n_exp_avg_sq};
+    if (grads == NULL || exp_avg == NULL || exp_avg_sq == NULL) {
+        np_ext_throw(NPH_OPTIM_MSG_LENGTHS);
+        return 0;
+    }
+    const char *msg = !optim_finite_nonneg(lr) ? NPH_OPTIM_MSG_LR
+                      : !optim_finite_nonneg(weight_decay) ? NPH_OPTIM_MSG_WEIGHT_DECAY
+                      : (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) ? NPH_OPTIM_MSG_BETAS
+                      : !optim_finite_nonneg(eps) ? NPH_OPTIM_MSG_EPS
+                      : step < 1 ? NPH_OPTIM_MSG_STEP : NULL;
+    if (!optim_of(lists, lens, grad_scale, grad_scale_index, msg, &o)) return 0;
+    const int ok = np_adam_step((float *const *) o.p, (const float *const *) o.g, (float *const *) o.s1, (float *const *) o.s2, o.n, (size_t) n_params,
+                                (long long) step, lr, beta1, beta2, eps, weight_decay, decoupled,
+                                grad_scale != NULL ? NDArray_FDATA(grad_scale) + grad_scale_index : NULL) == NP_OK;
+    if (!ok) np_ext_throw_last();
+    optim_release(&o);
+    return ok;
+}
+
+NDArray *NPH_GradNorm(NDArray **grads, int n_grads, double max_norm) {
+    nph_optim o;
+    NDArray **lists[4] = {grads, NULL, NULL, NULL};
+    const int lens[4] = {n_grads, 0, 0, 0};
+    if (!optim_of(lists, lens, NULL, 0, !(max_norm >= 0.0) ? NPH_OPTIM_MSG_MAX_NORM : NULL, &o)) return NULL;
+    const size_t two = 2;
+    NDArray *out = empty_on_gpu(1, &two);
+    if (out != NULL && np_grad_norm((const float *const *) o.p, o.n, (size_t) n_grads, max_norm, NDArray_FDATA(out)) != NP_OK) {
+        np_ext_throw_last();
+        NDArray_FREE(out);
+        out = NULL;
+    }
+    optim_release(&o);
+    return out;
+}

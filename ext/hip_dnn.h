@@ -247,6 +247,45 @@ struct NDArray **NPH_Attention_Forward(struct NDArray *q, struct NDArray *k, str
 struct NDArray **NPH_Attention_Backward(struct NDArray *q, struct NDArray *k, struct NDArray *v, struct NDArray *o, struct NDArray *dout,
                                         struct NDArray *save_max, struct NDArray *save_sum, int causal, float scale);
 
+/* ---- optimizer steps (np_sgd_step / np_adam_step / np_grad_norm of include/np_hip.h) ----
+ * The reference has no optimizer, so tools/apply_with_hip.py inserts nothing; they are what a binding with these methods calls.
+ * A call takes LISTS of arrays: n_params parameters, as many gradients and, where the rule has a state, as many state arrays, entry
+ * t of each list belonging to tensor t.  Parameters and states are updated in place; a gradient must have as many elements as its
+ * parameter (the shapes are not compared).  grad_scale, when not NULL, is a GPU array and grad_scale_index the element of it that
+ * the kernel multiplies every gradient by: (the result of NPH_GradNorm, 1) clips by the norm with no host read.
+ * The messages, checked in this order (the buffers', momentum's, dampening's and nesterov's by NPH_SGD_Step alone; the betas', eps'
+ * and step's by NPH_Adam_Step alone; max_norm's by NPH_GradNorm alone, which has no parameters and no states): */
+#define NPH_OPTIM_MSG_LENGTHS "dnn_optim: the lists of parameters, gradients and states must have the same length"
+#define NPH_OPTIM_MSG_NULL "dnn_optim: a list holds an entry that is not an array"
+#define NPH_OPTIM_MSG_EMPTY_LIST "dnn_optim: the list is empty"
+#define NPH_OPTIM_MSG_BUFFERS "dnn_sgd_step: a momentum needs the list of buffers"
+#define NPH_OPTIM_MSG_EMPTY "dnn_optim: an operand has no elements"
+#define NPH_OPTIM_MSG_COUNT "dnn_optim: a gradient or a state must have as many elements as its parameter"
+#define NPH_OPTIM_MSG_SCALE "dnn_optim: grad_scale must be an array and grad_scale_index an element of it"
+#define NPH_OPTIM_MSG_LR "dnn_optim: lr must be finite and not negative"
+#define NPH_OPTIM_MSG_WEIGHT_DECAY "dnn_optim: weight_decay must be finite and not negative"
+#define NPH_OPTIM_MSG_MOMENTUM "dnn_sgd_step: momentum must lie in [0, 1]"
+#define NPH_OPTIM_MSG_DAMPENING "dnn_sgd_step: dampening must lie in [0, 1]"
+#define NPH_OPTIM_MSG_NESTEROV "dnn_sgd_step: nesterov needs a momentum and zero dampening"
+#define NPH_OPTIM_MSG_BETAS "dnn_adam_step: the betas must lie in [0, 1)"
+#define NPH_OPTIM_MSG_EPS "dnn_adam_step: eps must be finite and not negative"
+#define NPH_OPTIM_MSG_STEP "dnn_adam_step: step must be at least 1"
+#define NPH_OPTIM_MSG_MAX_NORM "dnn_grad_norm: max_norm must not be negative"
+#define NPH_OPTIM_MSG_DEVICE "dnn_optim: the operands must be on the same device"
+#define NPH_OPTIM_MSG_CPU "dnn_optim: operands are on the CPU; numpower_amd only computes on the GPU (call ->gpu() first)"
+/* raised by the host library: a parameter or a state that had to be copied (a view) could not be updated in place */
+#define NPH_OPTIM_MSG_VIEW "dnn_optim: parameters and states are updated in place and must be contiguous arrays"
+
+/* 1, or 0 after a raised error (nothing was launched).  bufs may be NULL (n_bufs = 0) when momentum == 0 */
+int NPH_SGD_Step(struct NDArray **params, int n_params, struct NDArray **grads, int n_grads, struct NDArray **bufs, int n_bufs, double lr,
+                 double momentum, double dampening, double weight_decay, int nesterov, int first_step, struct NDArray *grad_scale,
+                 int grad_scale_index);
+int NPH_Adam_Step(struct NDArray **params, int n_params, struct NDArray **grads, int n_grads, struct NDArray **exp_avg, int n_exp_avg,
+                  struct NDArray **exp_avg_sq, int n_exp_avg_sq, long step, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, int decoupled, struct NDArray *grad_scale, int grad_scale_index);
+/* a new (2) GPU array: the norm of the list and the clip coefficient for max_norm (+Inf: 1) */
+struct NDArray *NPH_GradNorm(struct NDArray **grads, int n_grads, double max_norm);
+
 #ifdef __cplusplus
 }
 #endif

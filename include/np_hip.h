@@ -875,6 +875,64 @@ int np_attention_backward(const float *q, const float *k, const float *v, const 
                           const float *save_max, const float *save_sum, size_t BH, size_t Sq, size_t Sk, size_t D,
                           int causal, float scale, float *dq, float *dk, float *dv);
 
+/* ---- optimizer steps (np_optim.hip; DESIGN.md "optimizer steps") ------------
+ * One call updates a LIST of T tensors in place: tensor t has counts[t] contiguous fp32 elements, a parameter params[t], a
+ * gradient grads[t] and zero, one or two state arrays.  The pointer arrays and counts are HOST arrays of device pointers; the list
+ * travels in the kernel arguments, so a call copies nothing, takes no scratch and does not synchronise; it runs on the library
+ * stream and may be captured between np_graph_begin and np_graph_end.  T tensors take ceil(T / 64) launches.
+ *   Element         an element's result depends on that element's operands and the scalar arguments alone: the length of the
+ *                   list, the order of the tensors, the packing into launches, the chunking and the alignment cannot change a bit.
+ *                   Every step below is a separately rounded fp32 operation, no contraction; division and square root are
+ *                   correctly rounded, there is no reciprocal and no rsqrt; denormals are kept.
+ *   Coefficients    computed in double on the host from the double arguments and rounded to fp32 ONCE: lr, wd = weight_decay,
+ *                   mu = momentum, omd = f32(1 - dampening); for Adam b1 = beta1, b2 = beta2, omb1 = f32(1 - beta1),
+ *                   omb2 = f32(1 - beta2), lrwd = f32(lr . weight_decay), bc2s = f32(sqrt(1 - beta2^step)),
+ *                   ss = f32(lr / (1 - beta1^step)), eps.  s = *grad_scale is a DEVICE float that the kernel reads.
+ *   Skipping        a step that a coefficient makes the identity is SKIPPED, not multiplied through (0 . Inf would otherwise
+ *                   differ): weight_decay == 0 skips the decay step; momentum == 0 skips the buffer, and bufs and its entries
+ *                   may be NULL; a NULL grad_scale skips the scale.  Nothing else is skipped: omd . g2 is formed when dampening == 0.
+ *   np_sgd_step     torch.optim.SGD.  g1 = g . s.  g2 = g1 + (wd . p), a multiply, then an add.  With momentum:
+ *                   b = g2 when first_step, else b = (mu . b) + (omd . g2), two multiplies, then an add; d = g2 + (mu . b) with
+ *                   nesterov (the new b), else d = b.  Without momentum d = g2.  p = p - (lr . d), a multiply, then a subtract.
+ *                   first_step does not read the buffer.
+ *   np_adam_step    torch.optim.Adam, and AdamW when decoupled.  g1 = g . s.  decoupled: p1 = p - (lrwd . p), g2 = g1; otherwise
+ *                   g2 = g1 + (wd . p), p1 = p.  m = (b1 . m) + (omb1 . g2).  v = (b2 . v) + ((omb2 . g2) . g2).
+ *                   den = (sqrt(v) / bc2s) + eps.  p = p1 - (ss . (m / den)).  step >= 1 is the number of this update; exp_avg and
+ *                   exp_avg_sq are required.
+ *   Special values  a NaN or +-Inf gradient element reaches its own element of p and the states, and no other.  weight_decay == 0
+ *                   with p = +-Inf leaves g untouched.  eps = 0 with v = 0 gives m / 0: NaN for m = 0.
+ *   Aliasing        no written range (the parameters and states of ALL tensors) may overlap another written range, a gradient or
+ *                   grad_scale; found on the host by sorting the ranges.  Two gradients may share memory: grads[t] == grads[u].
+ *   Sizes           all size_t; counts[t] beyond 2^31 works.
+ *   Alignment       any 4-byte-aligned pointer is accepted.  A tensor whose pointers are all congruent mod 16 is updated with
+ *                   16-byte accesses over its aligned middle and scalar accesses at its head and tail, any other with scalar
+ *                   accesses; the choice is per tensor and both forms give the same bits.
+ *   Determinism     no atomics, no scratch.  Results are bit-identical from run to run.
+ * Convention as above: pointers are checked first, then the extents, the parameters, the aliasing, then work begins.
+ * NP_ERR_INVALID before any device work: a null list or a null required pointer; T = 0 or a counts[t] = 0; an lr, weight_decay or eps
+ * that is negative or not finite; a momentum or dampening outside [0, 1]; nesterov with momentum == 0 or dampening != 0; a beta
+ * outside [0, 1); step < 1; overlapping ranges. */
+int np_sgd_step(float *const *params, const float *const *grads, float *const *bufs /* may be NULL when momentum == 0 */,
+                const size_t *counts, size_t T, double lr, double momentum, double dampening, double weight_decay, int nesterov,
+                int first_step, const float *grad_scale /* device, may be NULL */);
+int np_adam_step(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                 const size_t *counts, size_t T, long long step, double lr, double beta1, double beta2, double eps,
+                 double weight_decay, int decoupled, const float *grad_scale /* device, may be NULL */);
+/* The gradient norm of a list and torch's clip_grad_norm_ coefficient, written to two DEVICE floats; no host read, so dev_out2 + 1
+ * is what the step calls take as grad_scale and clipping costs no synchronisation.
+ *   S               sum over t and i of g^2, each square formed in double from the float (exact), accumulated in fp64 from +0.0.
+ *                   One partial per 8192 elements of a tensor goes to pool scratch that is released on every path; one workgroup
+ *                   adds the partials in a fixed order.  The order depends on (counts, T) alone: no atomics, bit-identical from
+ *                   run to run, the same at every alignment.
+ *   dev_out2[0]     f32(sqrt(S)): ONE rounding of an fp64 value.
+ *   dev_out2[1]     f32(min(1, max_norm / ((double) dev_out2[0] + 1e-6))); 1 when max_norm is +Inf and the norm is finite.
+ *   Classes         squares are never negative, so S is NaN exactly when an element is NaN, else +Inf when an element is +-Inf
+ *                   (or f32(sqrt(S)) overflows), else finite.  norm NaN: the coefficient is NaN.
+ *                   norm +Inf: the coefficient is 0, or NaN when max_norm is +Inf too.
+ * NP_ERR_INVALID before any device work: a null pointer, T = 0, a counts[t] = 0, a max_norm that is negative or NaN, a result that
+ * overlaps a gradient. */
+int np_grad_norm(const float *const *grads, const size_t *counts, size_t T, double max_norm, float *dev_out2);
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

@@ -219,6 +219,20 @@ int np_debug_attention_last_path(int *d_class, int *q_tile, int *k_tile, int *la
  * rule), bounds[2 .. 4] = the largest D of the three instantiations, bounds[5] = the rows of a wave, bounds[6] = the keys of a
  * workgroup of the dk / dv kernel */
 int np_debug_attention_bounds(size_t bounds[], int n);
+/* tests / tools: what the last np_sgd_step, np_adam_step or np_grad_norm of the process launched.  launches: the kernels it took
+ * (a step: ceil(T / bounds[1]); the norm: that many and the fold).  chunks: the chunks of all its launches (a step: per tensor
+ * ceil((o + n) / bounds[0]) with o = (the pointers' common residue mod 16) / 4 for a tensor served with 16-byte accesses and
+ * o = 0 for a scalar one; the norm: per tensor ceil(n / bounds[2]), one partial each).  vec_tensors, scalar_tensors: the tensors of
+ * a step by access form (both 0 for the norm).  Zeros before any launch; NP_ERR_INVALID on a null pointer.  Plain process globals. */
+int np_debug_optim_last_path(int *launches, size_t *chunks, int *vec_tensors, int *scalar_tensors);
+/* the constants, n >= 5: bounds[0] = the elements of a step chunk, bounds[1] = kOptimMaxTensors, the tensors of one launch,
+ * bounds[2] = the elements behind one partial of np_grad_norm (its slice rule: tensor t gives ceil(n_t / bounds[2]) partials, in
+ * list order), bounds[3] = the workgroups per CU that cap a grid (min(chunks, CUs . bounds[3] | 1)), bounds[4] = the bytes of
+ * the list as a kernel argument */
+int np_debug_optim_bounds(size_t bounds[], int n);
+/* testing / A-B: on != 0 serves every tensor of a step with scalar accesses, 0 (the default) chooses per tensor by the pointers'
+ * residues.  Both forms give the same bits.  Process-global. */
+int np_debug_optim_force_scalar(int on);
 /* tests / tools: which kernel families the last np_reduce_axis or np_reduce_all(_dev) call of the process launched, the calls it
  * makes on its own partials included: the OR of the NP_REDUCE_PATH_ bits below (0 = none yet).  A plain process global, cleared
  * at the top of those entry points; calls the library makes itself (split-K GEMM folds, chain partials) overwrite it too. */

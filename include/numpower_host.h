@@ -460,6 +460,20 @@ NDArray **NDArrayDNN_GroupNorm_Backward(NDArray *x, NDArray *dy, int num_groups,
 NDArray **NDArrayDNN_Attention_Forward(NDArray *q, NDArray *k, NDArray *v, int causal, float scale);
 NDArray **NDArrayDNN_Attention_Backward(NDArray *q, NDArray *k, NDArray *v, NDArray *o, NDArray *dout, NDArray *save_max, NDArray *save_sum,
                                         int causal, float scale);
+/* Optimizer steps (host/numpower_dnn.cpp; the reference has none): GPU operands in lists, entry t of each list belonging to
+ * tensor t.  _SGD_Step is torch.optim.SGD's update (bufs may be NULL with n_bufs = 0 when momentum == 0; first_step != 0 sets the
+ * buffers to the gradients), _Adam_Step torch.optim.Adam's, and AdamW's when decoupled != 0 (step >= 1 counts the updates).
+ * Parameters and states are updated in place and must be contiguous arrays; gradients may be views, which are made contiguous.
+ * grad_scale (or NULL) is a GPU array whose element grad_scale_index multiplies every gradient, read on the device.  Both return 1,
+ * or 0 after an error.  _GradNorm returns a new (2) array: the norm of all the gradients and the coefficient
+ * min(1, max_norm / (norm + 1e-6)) that, passed as (grad_scale, 1), clips by the norm.  NPH_SGD_Step, NPH_Adam_Step and NPH_GradNorm
+ * over np_sgd_step, np_adam_step and np_grad_norm do the work.  Errors: ext/hip_dnn.h, NPH_OPTIM_MSG_*. */
+int NDArrayDNN_SGD_Step(NDArray **params, int n_params, NDArray **grads, int n_grads, NDArray **bufs, int n_bufs, double lr, double momentum,
+                        double dampening, double weight_decay, int nesterov, int first_step, NDArray *grad_scale, int grad_scale_index);
+int NDArrayDNN_Adam_Step(NDArray **params, int n_params, NDArray **grads, int n_grads, NDArray **exp_avg, int n_exp_avg, NDArray **exp_avg_sq,
+                         int n_exp_avg_sq, long step, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                         NDArray *grad_scale, int grad_scale_index);
+NDArray *NDArrayDNN_GradNorm(NDArray **grads, int n_grads, double max_norm);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,9 @@
 // the reference does not have; the same glue file does their work.
 // A translation unit of its own: the sanitizer build of numpower_host.cpp (tests/test_host_sanitizers_cpu.py) links
 // against a null device that has no convolution.
+#include <deque>
 #include <optional>
+#include <vector>
 
 #include "hip_dnn.h"
 #include "np_ext_hooks.h"
@@ -36,6 +38,36 @@ auto on_contiguous(Glue glue, NDArray *a, NDArray *b, NDArray *c = nullptr, NDAr
     }
     return glue(arr[0], arr[1], arr[2], arr[3]);
 }
+
+// The lists of an optimizer call, each entry made contiguous for the call (take, in argument order).  A list that is NULL or
+// holds a NULL or a CPU array is handed on as it is: it only ever meets the glue's checks.  in_place: a list that the call
+// updates, so an entry that had to be copied is refused.
+struct OptimLists {
+    std::deque<Operand> held;
+    std::deque<std::vector<NDArray *>> lists;
+    std::vector<NDArray **> given;
+
+    bool take(NDArray **list, int n, bool in_place) {
+        lists.emplace_back();
+        given.push_back(list);
+        if (!list || n < 1) return true;
+        for (int i = 0; i < n; ++i)
+            if (!list[i] || NDArray_DEVICE(list[i]) != NDARRAY_DEVICE_GPU) return true;
+        std::vector<NDArray *> &out = lists.back();
+        for (int i = 0; i < n; ++i) {
+            NDArray *c = held.emplace_back(list[i]).arr;
+            if (!c) return false;
+            if (in_place && c != list[i]) {
+                np_ext_throw(NPH_OPTIM_MSG_VIEW);
+                return false;
+            }
+            out.push_back(c);
+        }
+        return true;
+    }
+    // list k as the glue takes it
+    NDArray **at(size_t k) { return lists[k].empty() ? given[k] : lists[k].data(); }
+};
 
 }  // namespace
 
@@ -220,6 +252,36 @@ NDArray **NDArrayDNN_Attention_Backward(NDArray *q, NDArray *k, NDArray *v, NDAr
                 dout, save_max, save_sum);
         },
         q, k, v, o);
+}
+
+// Optimizer steps (np_sgd_step / np_adam_step / np_grad_norm), which the reference does not have either.  The
+// lists are handed to the glue as they are when they are malformed or hold a CPU array, so that its messages speak.  Otherwise
+// gradients are made contiguous for the call; a parameter or state that would have to be copied (a view) is refused.
+int NDArrayDNN_SGD_Step(NDArray **params, int n_params, NDArray **grads, int n_grads, NDArray **bufs, int n_bufs, double lr, double momentum,
+                        double dampening, double weight_decay, int nesterov, int first_step, NDArray *grad_scale, int grad_scale_index) {
+    OptimLists l;
+    if (!l.take(params, n_params, true) || !l.take(grads, n_grads, false) || !l.take(bufs, n_bufs, true) || !l.take(&grad_scale, grad_scale ? 1 : 0, false))
+        return 0;
+    return NPH_SGD_Step(l.at(0), n_params, l.at(1), n_grads, l.at(2), n_bufs, lr, momentum, dampening, weight_decay, nesterov, first_step,
+                        grad_scale ? l.at(3)[0] : nullptr, grad_scale_index);
+}
+
+int NDArrayDNN_Adam_Step(NDArray **params, int n_params, NDArray **grads, int n_grads, NDArray **exp_avg, int n_exp_avg, NDArray **exp_avg_sq,
+                         int n_exp_avg_sq, long step, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                         NDArray *grad_scale, int grad_scale_index) {
+    OptimLists l;
+    if (!l.take(params, n_params, true) || !l.take(grads, n_grads, false) || !l.take(exp_avg, n_exp_avg, true) ||
+        !l.take(exp_avg_sq, n_exp_avg_sq, true) || !l.take(&grad_scale, grad_scale ? 1 : 0, false))
+        return 0;
+    return NPH_Adam_Step(l.at(0), n_params, l.at(1), n_grads, l.at(2), n_exp_avg, l.at(3), n_exp_avg_sq, step, lr, beta1, beta2, eps, weight_decay,
+                         decoupled, grad_scale ? l.at(4)[0] : nullptr, grad_scale_index);
+}
+
+// a new (2) array: the norm of the list and the clip coefficient for max_norm
+NDArray *NDArrayDNN_GradNorm(NDArray **grads, int n_grads, double max_norm) {
+    OptimLists l;
+    if (!l.take(grads, n_grads, false)) return nullptr;
+    return NPH_GradNorm(l.at(0), n_grads, max_norm);
 }
 
 }  // extern "C"

@@ -172,6 +172,10 @@ def _load_host():
     sig["NDArrayDNN_GroupNorm_Backward"] = (C.POINTER(_P), [_P, _P, C.c_int, _P, _P, _P])
     sig["NDArrayDNN_Attention_Forward"] = (C.POINTER(_P), [_P, _P, _P, C.c_int, C.c_float])
     sig["NDArrayDNN_Attention_Backward"] = (C.POINTER(_P), [_P] * 7 + [C.c_int, C.c_float])
+    pp = C.POINTER(_P)
+    sig["NDArrayDNN_SGD_Step"] = (C.c_int, [pp, C.c_int] * 3 + [C.c_double] * 4 + [C.c_int, C.c_int, _P, C.c_int])
+    sig["NDArrayDNN_Adam_Step"] = (C.c_int, [pp, C.c_int] * 4 + [C.c_long] + [C.c_double] * 5 + [C.c_int, _P, C.c_int])
+    sig["NDArrayDNN_GradNorm"] = (_P, [pp, C.c_int, C.c_double])
     sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
     sig["NDArray_Eig"] = (C.POINTER(_P), [_P])
     sig["NDArray_Qr"] = (C.POINTER(_P), [_P])
@@ -1194,6 +1198,81 @@ class NDArray:
         if any(a is None for a in ops):
             raise Error("dnn_attention_backward: q, k, v, o, dout, save_max and save_sum must be arrays")
         return NDArray._norm_results(h, h.NDArrayDNN_Attention_Backward(*[a._p for a in ops], 1 if causal else 0, sc))
+
+    @staticmethod
+    def _optim_list(who, name, values, optional=False):
+        """-> (the arrays, which keeps them alive; the C vector of their pointers; its length) for a list or tuple of arrays.  Every
+        pointer goes through the marshalling point, so a pending chain on a parameter, a state or a gradient is computed first."""
+        if values is None and optional:
+            return [], None, 0
+        if not isinstance(values, (list, tuple)) or any(not isinstance(v, NDArray) for v in values):
+            raise Error("%s: %s must be a list of arrays" % (who, name))
+        return list(values), (_P * max(1, len(values)))(*[v._p for v in values]), len(values)
+
+    @staticmethod
+    def _optim_number(who, name, value):
+        if isinstance(value, bool) or not isinstance(value, (int, float, np.floating, np.integer)):
+            raise Error("%s: %s must be a number" % (who, name))
+        return float(value)
+
+    @staticmethod
+    def _optim_scale(who, grad_scale):
+        """None, an array (its element 0) or (array, index) -> (array or None, pointer or None, index)"""
+        if grad_scale is None:
+            return None, None, 0
+        arr, index = grad_scale if isinstance(grad_scale, tuple) and len(grad_scale) == 2 else (grad_scale, 0)
+        if not isinstance(arr, NDArray) or isinstance(index, bool) or not isinstance(index, (int, np.integer)):
+            raise Error(who + ": grad_scale must be an array, (array, index) or None")
+        return arr, arr._p, int(index)
+
+    @staticmethod
+    def dnn_sgd_step(params, grads, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, buffers=None, first_step=False,
+                     grad_scale=None):
+        """One torch.optim.SGD update of a list of GPU arrays, in place, in one launch per 64 tensors:
+        g = grad . s + weight_decay . p; with a momentum b = g on the first step, else momentum . b + (1 - dampening) . g, and the
+        direction is b, or g + momentum . b with nesterov; p = p - lr . direction.  buffers is the list of momentum buffers (needed
+        when momentum != 0); first_step=True sets them instead of reading them.  grad_scale: None, a GPU array whose element 0
+        multiplies every gradient on the device, or (array, index): (dnn_grad_norm's result, 1) clips by the norm with no host read.
+        Parameters and buffers must be contiguous arrays; gradients may be views.  Returns None."""
+        who = "dnn_sgd_step"
+        h = _load_host()
+        nums = [NDArray._optim_number(who, n, v) for n, v in (("lr", lr), ("momentum", momentum), ("dampening", dampening), ("weight_decay", weight_decay))]
+        keep = [NDArray._optim_list(who, "params", params), NDArray._optim_list(who, "grads", grads), NDArray._optim_list(who, "buffers", buffers, True)]
+        scale, scale_p, index = NDArray._optim_scale(who, grad_scale)
+        args = [x for k in keep for x in k[1:]]
+        if not h.NDArrayDNN_SGD_Step(*args, *nums, 1 if nesterov else 0, 1 if first_step else 0, scale_p, index):
+            _raise_pending(h)
+
+    @staticmethod
+    def dnn_adam_step(params, grads, exp_avg, exp_avg_sq, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False,
+                      grad_scale=None):
+        """One torch.optim.Adam update of a list of GPU arrays, in place; decoupled=True is AdamW's, whose weight
+        decay multiplies p by (1 - lr . weight_decay) instead of joining the gradient.  exp_avg and exp_avg_sq are the lists of the
+        two moments, zeros before the first update; step >= 1 is the number of this update, for the bias corrections.  grad_scale
+        as in dnn_sgd_step.  Returns None."""
+        who = "dnn_adam_step"
+        h = _load_host()
+        if isinstance(step, bool) or not isinstance(step, (int, np.integer)):
+            raise Error(who + ": step must be an int")
+        if not isinstance(betas, (tuple, list)) or len(betas) != 2:
+            raise Error(who + ": betas must be a pair of numbers")
+        nums = [NDArray._optim_number(who, n, v) for n, v in (("lr", lr), ("betas", betas[0]), ("betas", betas[1]), ("eps", eps), ("weight_decay", weight_decay))]
+        keep = [NDArray._optim_list(who, n, v) for n, v in (("params", params), ("grads", grads), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq))]
+        scale, scale_p, index = NDArray._optim_scale(who, grad_scale)
+        args = [x for k in keep for x in k[1:]]
+        if not h.NDArrayDNN_Adam_Step(*args, max(-1, min(int(step), 2 ** 62)), *nums, 1 if decoupled else 0, scale_p, index):
+            _raise_pending(h)
+
+    @staticmethod
+    def dnn_grad_norm(grads, max_norm=float("inf")):
+        """-> a (2) GPU array: the 2-norm of all the elements of a list of GPU arrays (an fp64 sum of squares, one rounding) and
+        torch's clip_grad_norm_ coefficient min(1, max_norm / (norm + 1e-6)), 1 for max_norm = inf.  Nothing is read back: pass
+        (result, 1) as grad_scale of dnn_sgd_step / dnn_adam_step to clip."""
+        who = "dnn_grad_norm"
+        h = _load_host()
+        limit = NDArray._optim_number(who, "max_norm", max_norm)
+        keep = NDArray._optim_list(who, "grads", grads)
+        return NDArray(h.NDArrayDNN_GradNorm(keep[1], keep[2], limit))
 
     def copy(self):          # PHP_METHOD copy: NDArray_Copy on the array's own device
         return NDArray._wrap(_load_host().NDArray_Copy(self._p, C.cast(self._p, _P).contents.device))

@@ -35,6 +35,14 @@ copy of the SAME bytes (8 per element forward, 12 backward, 8 plus the labels an
 shapes, with the four-pass composition examples/softmax_regression.py uses (max, two fused chains, the loss chain), which is how the
 library computed a softmax loss before.  Reported: ms, TB/s, copy / op (1.00 = the copy's rate, the ceiling of a form that reads a row
 once and writes it once) and composition / op.  The log is stamped with the sources it ran on.  Writes profiles/dnn/softmax_sweep.log.
+--optim is the leg of the optimizer steps (np_optim.hip), four cases (OPTIM_CASES).  0 and 1: plain SGD, momentum SGD and AdamW (12, 20
+and 28 bytes per element) on one tensor of 10^8 elements and on a ResNet-like list of 301 tensors with the same total, each alternating
+round by round with np_memcpy_d2d (the float4 copy) of the same bytes and with np_binary add over the same bytes; reported: ms, TB/s,
+copy / step, copy / add, and the spread of both over the rounds.  2: the wall time of one step for 300 tensors of 1000 elements,
+np_sgd_step and np_adam_step through the C ABI and through NDArray, against the per-tensor `p - g * lr` loop and against the Adam
+composition from NDArray calls.  3: np_grad_norm on the two lists against np_reduce_all (sum) over the same bytes.  Writes
+profiles/dnn/optim_sweep.log.
+
 --batchnorm is the leg of batch normalization (np_batchnorm.hip): training forward, inference forward and backward on BATCHNORM_SHAPES,
 which reach every kernel form.  Each operation alternates, round by round in one session, with the float4 copy of the bytes its form
 moves (8 per element for inference and the one-launch training form, 12 for the split and rows training forward, 12 for the
@@ -61,6 +69,7 @@ Usage: python tools/dnn_sweep.py [--layers 0,1,...] [--rounds N] [--limit S] [--
        python tools/dnn_sweep.py --batchnorm [--layers ...]   the batch-normalization leg
        python tools/dnn_sweep.py --groupnorm [--layers ...]   the layer / group normalization leg
        python tools/dnn_sweep.py --attention [--layers ...]   the attention leg
+       python tools/dnn_sweep.py --optim [--layers ...]       the optimizer leg
        python tools/dnn_sweep.py --profile LAYER     three calls of each operation and nothing else, for a run under the kernel profiler"""
 import argparse
 import statistics
@@ -111,8 +120,22 @@ GROUPNORM_SHAPES = [("layer (65536, 1024)", (65536, 1, 1024, 1), True), ("layer 
 ATTENTION_SHAPES = [(64, 512, 64), (64, 2048, 64), (16, 8192, 64), (64, 2048, 128), (512, 197, 64), (64, 2048, 32)]
 MATRIX_PEAK_TFLOPS = 157.3
 
+OPTIM_CASES = ["one tensor of 10^8", "ResNet-like list of 301 tensors, 10^8 in all", "300 tensors of 1000: wall time of a step", "np_grad_norm"]
+OPTIM_TOTAL = 10 ** 8
+
+
+def optim_resnet_like():
+    """100 3x3 convolutions over 64 .. 512 channels, each with a gamma and a beta, and one dense layer that brings the total to 10^8"""
+    counts = []
+    for j in range(100):
+        c = (64, 128, 256, 512)[j % 4]
+        counts += [c * c * 9, c, c]
+    return counts + [OPTIM_TOTAL - sum(counts)]
+
+
 ap = argparse.ArgumentParser()
 ap.add_argument("--batchnorm", action="store_true")
+ap.add_argument("--optim", action="store_true")
 ap.add_argument("--groupnorm", action="store_true")
 ap.add_argument("--attention", action="store_true")
 ap.add_argument("--pool", action="store_true")
@@ -129,9 +152,9 @@ ap.add_argument("--profile", type=int, default=None)
 ap.add_argument("--child", default=None, help="internal: 'layer:<i>' or 'torch'")
 args = ap.parse_args()
 if args.layers is None:
-    args.layers = ",".join(str(i) for i in range(len(ATTENTION_SHAPES if args.attention else GROUPNORM_SHAPES if args.groupnorm else BATCHNORM_SHAPES if args.batchnorm else SOFTMAX_SHAPES if args.softmax else POOL_LAYERS if args.pool else LAYERS)))
+    args.layers = ",".join(str(i) for i in range(len(OPTIM_CASES if args.optim else ATTENTION_SHAPES if args.attention else GROUPNORM_SHAPES if args.groupnorm else BATCHNORM_SHAPES if args.batchnorm else SOFTMAX_SHAPES if args.softmax else POOL_LAYERS if args.pool else LAYERS)))
 if args.out is None:
-    args.out = str(ROOT / "profiles" / "dnn" / ("attention_sweep.log" if args.attention else "groupnorm_sweep.log" if args.groupnorm else "batchnorm_sweep.log" if args.batchnorm else "softmax_sweep.log" if args.softmax else "pool2d_sweep.log" if args.pool else "conv2d_act_sweep.log" if args.act else
+    args.out = str(ROOT / "profiles" / "dnn" / ("optim_sweep.log" if args.optim else "attention_sweep.log" if args.attention else "groupnorm_sweep.log" if args.groupnorm else "batchnorm_sweep.log" if args.batchnorm else "softmax_sweep.log" if args.softmax else "pool2d_sweep.log" if args.pool else "conv2d_act_sweep.log" if args.act else
                                                "conv2d_forward_only.log" if args.forward_only else "conv2d_sweep.log"))
 LARGE = (256, 128, 3136)                        # (N, F, P) of the large case of --act: 1.03e8 elements
 HBM_TBS = 8.0
@@ -512,6 +535,155 @@ def run_batchnorm(i, rounds, sets):
                  min(c / p for c, p in zip(copy_ms, op_ms)), max(c / p for c, p in zip(copy_ms, op_ms)), tail), flush=True)
 
 
+def run_optim(i, rounds):
+    """one case of OPTIM_CASES"""
+    import ctypes as C_
+    import numpy as np
+    D, lib, check, ramp, _ = _setup()
+    from numpower_amd._lib import BINARY_OPS, REDUCE_OPS, Timer
+    t = Timer()
+    rng = np.random.default_rng(i)
+    block = rng.standard_normal(1 << 20).astype(np.float32)
+    vec = lambda values: (C_.c_void_p * len(values))(*values)
+
+    def timed(fn, reps):
+        t.start()
+        for _ in range(reps):
+            fn()
+        t.stop()
+        return t.elapsed_ms() / reps
+
+    def reps_for(fn):
+        for _ in range(3):
+            fn()
+        D.sync()
+        t0 = time.time()
+        fn()
+        D.sync()
+        return max(5, min(200, int(0.05 / max(time.time() - t0, 1e-5))))
+
+    def probe():
+        launches, chunks, wide, scalar = C_.c_int(), C_.c_size_t(), C_.c_int(), C_.c_int()
+        check(lib.np_debug_optim_last_path(C_.byref(launches), C_.byref(chunks), C_.byref(wide), C_.byref(scalar)))
+        return launches.value, chunks.value, wide.value, scalar.value
+
+    def carve(counts, value=None):
+        """one allocation cut into the tensors of a list, each on a 16-byte boundary -> (the allocation, the pointers)"""
+        starts, at = [], 0
+        for n in counts:
+            starts.append(at)
+            at += -(-n // 4) * 4
+        whole = D.DeviceArray.from_host(np.resize(block, at) if value is None else np.full(at, value, np.float32))
+        return whole, vec([whole.ptr + 4 * s for s in starts])
+
+    if i in (0, 1, 3):
+        counts = [OPTIM_TOTAL] if i == 0 else optim_resnet_like()
+        lists = [("one tensor of 10^8", [OPTIM_TOTAL]), ("list of 301, 10^8 in all", optim_resnet_like())] if i == 3 else [(OPTIM_CASES[i], counts)]
+    if i in (0, 1):
+        T, n = len(counts), sum(counts)
+        sizes = (C_.c_size_t * T)(*counts)
+        (hp, p), (hg, g), (hm, m), (hv, v) = carve(counts), carve(counts), carve(counts, 0.0), carve(counts, 0.0)
+        words = 28 * n // 8 + 16
+        cs, cd, third = D.DeviceArray((words,)), D.DeviceArray((words,)), D.DeviceArray((28 * n // 12 + 16,))
+        check(lib.np_memset0(cs.ptr, 4 * words))
+        check(lib.np_memset0(cd.ptr, 4 * words))
+        ramp()
+        steps = [("plain SGD", 12, lambda: check(lib.np_sgd_step(p, g, None, sizes, T, 1e-3, 0.0, 0.0, 0.0, 0, 0, None))),
+                 ("momentum SGD", 20, lambda: check(lib.np_sgd_step(p, g, m, sizes, T, 1e-3, 0.9, 0.0, 0.0, 0, 0, None))),
+                 ("AdamW", 28, lambda: check(lib.np_adam_step(p, g, m, v, sizes, T, 10, 1e-3, 0.9, 0.999, 1e-8, 1e-2, 1, None)))]
+        for label, per, fn in steps:
+            nbytes = per * n
+            half, n_add = nbytes // 2 // 16 * 16, nbytes // 12
+            copy = lambda: check(lib.np_memcpy_d2d(cd.ptr, cs.ptr, half))
+            add = lambda: check(lib.np_binary(BINARY_OPS["add"], cs.ptr, 0, cd.ptr, 0, third.ptr, 1, n_add, 0, 0))
+            reps = reps_for(fn)
+            for f in (copy, add):
+                for _ in range(3):
+                    f()
+            step_ms, copy_ms, add_ms = [], [], []
+            for _ in range(rounds):                   # alternating in one session
+                step_ms.append(timed(fn, reps))
+                copy_ms.append(timed(copy, reps))
+                add_ms.append(timed(add, reps))
+            fn()
+            launches, chunks, wide, scalar = probe()
+            sm, cm, am = statistics.median(step_ms), statistics.median(copy_ms), statistics.median(add_ms)
+            ratios, add_ratios = [c / x for c, x in zip(copy_ms, step_ms)], [c / a for c, a in zip(copy_ms, add_ms)]
+            print("%-44s %-13s launches %d chunks %6d vec %3d scalar %d %7.1f MB %8.4f ms %5.2f TB/s   copy %8.4f ms %5.2f TB/s   copy / step %5.3f (min %5.3f max %5.3f)"
+                  "   add %8.4f ms   copy / add %5.3f (min %5.3f max %5.3f)"
+                  % (OPTIM_CASES[i], label, launches, chunks, wide, scalar, nbytes * 1e-6, sm, nbytes / sm * 1e-9, cm, nbytes / cm * 1e-9, cm / sm, min(ratios),
+                     max(ratios), am, cm / am, min(add_ratios), max(add_ratios)), flush=True)
+    elif i == 2:
+        from numpower_amd.ndarray import NDArray as nd
+        T, each = 300, 1000
+        counts = [each] * T
+        sizes = (C_.c_size_t * T)(*counts)
+        (hp, p), (hg, g), (hm, m), (hv, v) = carve(counts), carve(counts), carve(counts, 0.0), carve(counts, 0.0)
+        host = lambda value=None: [nd.array(block[:each] if value is None else np.full(each, value, np.float32)).gpu() for _ in range(T)]
+        P, G, M, V = host(), host(), host(0.0), host(0.0)
+        state = {"P": P, "M": M, "V": V}
+        lr, b1, b2, eps = 1e-3, 0.9, 0.999, 1e-8
+        bc2s, ss = float(np.sqrt(1.0 - b2 ** 10)), lr / (1.0 - b1 ** 10)
+
+        def sgd_loop():
+            state["P"] = [a - b * lr for a, b in zip(state["P"], G)]
+
+        def adam_composition():
+            state["M"] = [a * b1 + b * (1.0 - b1) for a, b in zip(state["M"], G)]
+            state["V"] = [a * b2 + b * b * (1.0 - b2) for a, b in zip(state["V"], G)]
+            state["P"] = [a - (b / (nd.sqrt(c) / bc2s + eps)) * ss for a, b, c in zip(state["P"], state["M"], state["V"])]
+
+        ramp()
+        cases = [("np_sgd_step, the C ABI", lambda: check(lib.np_sgd_step(p, g, None, sizes, T, lr, 0.0, 0.0, 0.0, 0, 0, None))),
+                 ("NDArray.dnn_sgd_step", lambda: nd.dnn_sgd_step(P, G, lr)),
+                 ("the loop p - g * lr", sgd_loop),
+                 ("np_adam_step, the C ABI", lambda: check(lib.np_adam_step(p, g, m, v, sizes, T, 10, lr, b1, b2, eps, 0.0, 0, None))),
+                 ("NDArray.dnn_adam_step", lambda: nd.dnn_adam_step(P, G, M, V, 10, lr, (b1, b2), eps)),
+                 ("Adam from NDArray calls", adam_composition)]
+        walls = {label: [] for label, _ in cases}
+        for label, fn in cases:
+            for _ in range(3):
+                fn()
+        D.sync()
+        for _ in range(rounds):                       # alternating in one session; a host clock around work that ends in a synchronise
+            for label, fn in cases:
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    fn()
+                D.sync()
+                walls[label].append((time.perf_counter() - t0) / 10 * 1e6)
+        base = {"sgd": statistics.median(walls["NDArray.dnn_sgd_step"]), "adam": statistics.median(walls["NDArray.dnn_adam_step"])}
+        for label, _ in cases:
+            med = statistics.median(walls[label])
+            print("%-44s %-26s %9.1f us per step (min %9.1f max %9.1f)   over the NDArray method %6.1fx"
+                  % (OPTIM_CASES[i], label, med, min(walls[label]), max(walls[label]), med / base["adam" if "dam" in label else "sgd"]), flush=True)
+    else:
+        ramp()
+        for name, counts in lists:
+            T, n = len(counts), sum(counts)
+            sizes = (C_.c_size_t * T)(*counts)
+            hg, g = carve(counts)
+            flat = D.DeviceArray.from_host(np.resize(block, n))
+            out = D.DeviceArray((2,))
+            value = C_.c_float()
+            norm = lambda: check(lib.np_grad_norm(g, sizes, T, 1.0, out.ptr))
+            total = lambda: check(lib.np_reduce_all(REDUCE_OPS["sum"], flat.ptr, n, C_.byref(value)))
+            reps = reps_for(norm)
+            for _ in range(3):
+                total()
+            norm_ms, sum_ms = [], []
+            for _ in range(rounds):
+                norm_ms.append(timed(norm, reps))
+                sum_ms.append(timed(total, reps))
+            launches, chunks, _, _ = probe()
+            nm, sm = statistics.median(norm_ms), statistics.median(sum_ms)
+            ratios = [a / b for a, b in zip(sum_ms, norm_ms)]
+            print("%-44s %-26s launches %d partials %6d %7.1f MB %8.4f ms %5.2f TB/s   np_reduce_all sum %8.4f ms %5.2f TB/s   sum / norm %5.3f (min %5.3f max %5.3f)"
+                  % (OPTIM_CASES[i], name, launches, chunks, 4e-6 * n, nm, 4e-9 * n / nm * 1e3 * 1e-3, sm, 4e-9 * n / sm * 1e3 * 1e-3, sm / nm, min(ratios), max(ratios)), flush=True)
+            hg.free()
+            flat.free()
+
+
 def run_groupnorm(i, rounds, sets):
     """one shape: forward, backward with the parameter gradients, backward without them, each alternating with a float4 copy of the
     bytes its forms move; for the 2-D shapes the forward pass also with the NDArray composition and batch norm's rows form"""
@@ -836,6 +1008,8 @@ if args.child:
         run_pool(int(args.child.split(":")[1]), args.rounds, args.sets)
     elif args.child.startswith("batchnorm:"):
         run_batchnorm(int(args.child.split(":")[1]), args.rounds, args.sets)
+    elif args.child.startswith("optim:"):
+        run_optim(int(args.child.split(":")[1]), args.rounds)
     elif args.child.startswith("attention:"):
         run_attention(int(args.child.split(":")[1]), args.rounds)
     elif args.child.startswith("groupnorm:"):
@@ -871,8 +1045,15 @@ def child(what):
     return proc.returncode == 0
 
 
-kind = "attention" if args.attention else "groupnorm" if args.groupnorm else "batchnorm" if args.batchnorm else "softmax" if args.softmax else "pool" if args.pool else "act" if args.act else "fwd" if args.forward_only else "layer"
-if args.attention:
+kind = "optim" if args.optim else "attention" if args.attention else "groupnorm" if args.groupnorm else "batchnorm" if args.batchnorm else "softmax" if args.softmax else "pool" if args.pool else "act" if args.act else "fwd" if args.forward_only else "layer"
+if args.optim:
+    import hashlib
+    say("np_sgd_step / np_adam_step / np_grad_norm: the step against np_memcpy_d2d (the float4 copy) of the same bytes and against np_binary add over the same "
+        "bytes, alternating round by round in one process; the wall time of a step over 300 small tensors against the NDArray compositions; the norm against "
+        "np_reduce_all; fp32, medians of %d rounds" % args.rounds)
+    say("sources: " + ", ".join("%s sha256 %s" % (f, hashlib.sha256((ROOT / "numpower_amd" / "csrc" / f).read_bytes()).hexdigest()[:16])
+                                for f in ("np_optim.hip", "np_internal.h")))
+elif args.attention:
     import hashlib
     say("np_attention_forward / np_attention_backward with all three gradients and with dq alone, Sq = Sk = S, causal and not; useful TFLOP/s from 4.BH.S.S.D "
         "forward and 10.BH.S.S.D backward (6 for dq alone: its three products), halved under causal, against the %.1f TFLOP/s fp32 matrix peak; the forward pass without causal "
