@@ -1087,3 +1087,107 @@ NDArray *NPH_GradNorm(NDArray **grads, int n_grads, double max_norm) {
     optim_release(&o);
     return out;
 }
+
+
+/* ---- dense layers (hip_dnn.h): np_linear_forward / np_linear_backward ---- */
+
+typedef struct { size_t M, K, N; } nph_linear;
+
+/* the checks of both directions, in the order of hip_dnn.h.  bias, out and dy may be NULL; out is compared only with an
+ * activation.  0 after a raised error */
+static int linear_of(NDArray *x, NDArray *weight, NDArray *bias, NDArray *out, NDArray *dy, int act, nph_linear *l) {
+    if (act < 0) {
+        np_ext_throw(NPH_LINEAR_MSG_ACTIVATION);
+        return 0;
+    }
+    const int ndim = NDArray_NDIM(x);
+    if (ndim < 1 || NDArray_NDIM(weight) != 2) {
+        np_ext_throw(NPH_LINEAR_MSG_NDIM);
+        return 0;
+    }
+    const int *xs = NDArray_SHAPE(x), *ws = NDArray_SHAPE(weight);
+    if (xs[ndim - 1] != ws[1]) {
+        np_ext_throw(NPH_LINEAR_MSG_FEATURES);
+        return 0;
+    }
+    if (bias != NULL && (NDArray_NDIM(bias) != 1 || NDArray_SHAPE(bias)[0] != ws[0])) {
+        np_ext_throw(NPH_LINEAR_MSG_BIAS);
+        return 0;
+    }
+    l->M = 1;
+    for (int d = 0; d < ndim - 1; ++d) l->M *= (size_t) (xs[d] > 0 ? xs[d] : 0);
+    if (l->M < 1 || ws[0] < 1 || ws[1] < 1) {
+        np_ext_throw(NPH_LINEAR_MSG_EMPTY);
+        return 0;
+    }
+    l->K = (size_t) ws[1], l->N = (size_t) ws[0];
+    if (dy != NULL) {
+        int same = NDArray_NDIM(dy) == ndim && NDArray_SHAPE(dy)[ndim - 1] == ws[0];
+        for (int d = 0; same && d < ndim - 1; ++d) same = NDArray_SHAPE(dy)[d] == xs[d];
+        if (!same) {
+            np_ext_throw(NPH_LINEAR_MSG_GRADIENT);
+            return 0;
+        }
+        if (act != NP_ACT_NONE && (out == NULL || !has_shape(out, NDArray_SHAPE(dy), ndim))) {
+            np_ext_throw(NPH_LINEAR_MSG_OUT);
+            return 0;
+        }
+    }
+    NDArray *others[4] = {weight, bias, act != NP_ACT_NONE ? out : NULL, dy};
+    for (int i = 0; i < 4; ++i)
+        if (others[i] != NULL && NDArray_DEVICE(others[i]) != NDArray_DEVICE(x)) {
+            np_ext_throw(NPH_LINEAR_MSG_DEVICE);
+            return 0;
+        }
+    if (NDArray_DEVICE(x) != NDARRAY_DEVICE_GPU) {
+        np_ext_throw(NPH_LINEAR_MSG_CPU);
+        return 0;
+    }
+    return 1;
+}
+
+NDArray *NPH_Linear_Forward(NDArray *x, NDArray *weight, NDArray *bias, char activation) {
+    nph_linear l;
+    const int act = activation_of(activation);
+    if (x == NULL || weight == NULL || !linear_of(x, weight, bias, NULL, NULL, act, &l)) return NULL;
+    const int ndim = NDArray_NDIM(x);
+    int *dims = (int *) NPH_ALLOC(sizeof(int) * (size_t) ndim);
+    if (dims == NULL) return NULL;
+    for (int d = 0; d < ndim - 1; ++d) dims[d] = NDArray_SHAPE(x)[d];
+    dims[ndim - 1] = (int) l.N;
+    NDArray *y = empty_of_ints_on_gpu(dims, ndim);
+    NPH_RELEASE(dims);
+    if (y == NULL) return NULL;
+    if (np_linear_forward(NDArray_FDATA(x), NDArray_FDATA(weight), bias != NULL ? NDArray_FDATA(bias) : NULL, l.M, l.K, l.N, act, NDArray_FDATA(y)) !=
+        NP_OK) {
+        np_ext_throw_last();
+        NDArray_FREE(y);
+        return NULL;
+    }
+    return y;
+}
+
+NDArray **NPH_Linear_Backward(NDArray *x, NDArray *out, NDArray *dy, NDArray *weight, char activation, int use_bias, int need_dx) {
+    nph_linear l;
+    const int act = activation_of(activation);
+    if (x == NULL || dy == NULL || weight == NULL || !linear_of(x, weight, NULL, out, dy, act, &l)) return NULL;
+    NDArray **rtns = (NDArray **) NPH_ALLOC(sizeof(NDArray *) * 3);
+    NDArray *dw = empty_like_on_gpu(weight), *dx = need_dx ? empty_like_on_gpu(x) : NULL, *db = use_bias ? empty_on_gpu(1, &l.N) : NULL;
+    void *dz = NULL;   /* pool scratch, only with an activation: dz = dy otherwise */
+    int ok = rtns != NULL && dw != NULL && (dx != NULL || !need_dx) && (db != NULL || !use_bias);
+    if (ok && act != NP_ACT_NONE && np_malloc(&dz, l.M * l.N * sizeof(float)) != NP_OK) {
+        np_ext_throw_last();
+        dz = NULL;
+        ok = 0;
+    }
+    if (ok && np_linear_backward(NDArray_FDATA(x), NDArray_FDATA(weight), act != NP_ACT_NONE ? NDArray_FDATA(out) : NULL, NDArray_FDATA(dy), l.M, l.K,
+                                 l.N, act, (float *) dz, dx != NULL ? NDArray_FDATA(dx) : NULL, NDArray_FDATA(dw),
+                                 db != NULL ? NDArray_FDATA(db) : NULL) != NP_OK) {
+        np_ext_throw_last();
+        ok = 0;
+    }
+    if (dz != NULL) np_free(dz);   /* released on every path; the pool is stream-ordered: safe right behind the launches that read it */
+    if (!ok) return batchnorm_drop(rtns, dw, dx, db);
+    rtns[0] = dw, rtns[1] = dx, rtns[2] = db;
+    return rtns;
+}

@@ -286,6 +286,31 @@ int NPH_Adam_Step(struct NDArray **params, int n_params, struct NDArray **grads,
 /* a new (2) GPU array: the norm of the list and the clip coefficient for max_norm (+Inf: 1) */
 struct NDArray *NPH_GradNorm(struct NDArray **grads, int n_grads, double max_norm);
 
+/* ---- dense layers (np_linear_forward / _backward of include/np_hip.h) ----
+ * The reference has no dense layer, so tools/apply_with_hip.py inserts nothing; they are what a binding with these methods calls.
+ * torch's layout: x is (..., K) with ndim >= 1, its leading axes flattened to M rows (1 without one); weight is (N, K); bias is a
+ * 1-D (N,) array or NULL; y and dy are x's shape with N in place of K.  activation: 'r' relu, 't' tanh, 's' sigmoid, 'n' or 0
+ * none.  y = act(x . weight^T + bias[n]): the bias is ONE fp32 add after the reduction, the activation runs in the same kernel.
+ * The backward pass takes `out`, the forward RESULT (gradients are expressed through the output), and dy, the gradient of that
+ * result: dz = dy . act'(out) goes to pool scratch that is released on every path.
+ * The messages, checked in this order (out's and the gradient's by NPH_Linear_Backward alone): */
+#define NPH_LINEAR_MSG_ACTIVATION "dnn_linear: unknown activation: 'r' (relu), 't' (tanh), 's' (sigmoid), 'n' or 0 (none)"
+#define NPH_LINEAR_MSG_NDIM "dnn_linear: x must have at least 1 dimension (..., K) and the weight exactly 2 (N, K)"
+#define NPH_LINEAR_MSG_FEATURES "dnn_linear: the last axis of x must equal the weight's second axis K (in_features)"
+#define NPH_LINEAR_MSG_BIAS "dnn_linear: the bias must be 1-dimensional with one element per output feature (N,)"
+#define NPH_LINEAR_MSG_EMPTY "dnn_linear: an operand has no elements"
+#define NPH_LINEAR_MSG_GRADIENT "dnn_linear_backward: the gradient must have the shape of the forward result (..., N)"
+#define NPH_LINEAR_MSG_OUT "dnn_linear_backward: an activation needs out, the forward result, in the shape of the gradient"
+#define NPH_LINEAR_MSG_DEVICE "dnn_linear: the operands must be on the same device"
+#define NPH_LINEAR_MSG_CPU "dnn_linear: operands are on the CPU; numpower_amd only computes on the GPU (call ->gpu() first)"
+
+/* y (..., N), a new GPU array */
+struct NDArray *NPH_Linear_Forward(struct NDArray *x, struct NDArray *weight, struct NDArray *bias, char activation);
+/* A vector of THREE, the conv layer's order: rtn[0] = dW (N, K), rtn[1] = dX in x's shape, NULL without need_dx (and then no
+ * launch is spent on it), rtn[2] = db (N,), NULL without use_bias.  `out` may be NULL when the activation is none. */
+struct NDArray **NPH_Linear_Backward(struct NDArray *x, struct NDArray *out, struct NDArray *dy, struct NDArray *weight, char activation,
+                                     int use_bias, int need_dx);
+
 #ifdef __cplusplus
 }
 #endif

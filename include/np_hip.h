@@ -933,6 +933,62 @@ int np_adam_step(float *const *params, const float *const *grads, float *const *
  * overlaps a gradient. */
 int np_grad_norm(const float *const *grads, const size_t *counts, size_t T, double max_norm, float *dev_out2);
 
+/* ---- dense layers (np_linear.hip; DESIGN.md "dnn_linear") ------------
+ * torch's layout: x (M, K), w (N, K) = (out_features, in_features), bias (N) or NULL, y (M, N), all contiguous row-major fp32.
+ *   y[m,n]  = act(sum_k x[m,k] . w[n,k] + bias[n])
+ *   dz[m,n] = dy[m,n] . act'(y[m,n])
+ *   dx[m,k] = sum_n dz[m,n] . w[n,k]
+ *   dw[n,k] = sum_m dz[m,n] . x[m,k]
+ *   db[n]   = sum_m dz[m,n]
+ * act is an np_conv_act with exactly the rules written above np_conv2d_forward_act / np_conv2d_backward_act: v = acc + bias[n] is
+ * ONE fp32 add after the reduction, then the activation; the derivative goes through the OUTPUT y, relu a select, tanh
+ * dy * (1 - y*y), sigmoid dy * ((1 - y) * y), each operation rounded on its own.
+ * One MFMA tile kernel (v_mfma_f32_32x32x2_f32) serves the three products, reading every operand along its own contiguous axis;
+ * no transposed copy of x, w or dz is written.
+ *   Order     every element of y, dx and dw is ONE fp32 fmaf chain from +0.0f over its reduction index in ascending order.  For y
+ *             the order depends on K alone, for dx on N alone, not on M, the row's position, the tile or any device state: a row
+ *             of x alone gives bit for bit the row it gives inside any batch.
+ *             dw reduces over M: the ceil(M / 32) steps of 32 rows are cut into S slices of whole steps, S from (M, K, N) alone:
+ *             tiles = ceil(N / TM) . ceil(K / 128) with TM the smallest of 32, 64, 128 that covers N (128 beyond),
+ *             want = min(steps / 8, ceil(512 / tiles), 256), at least 1, steps_per_slice = ceil(steps / want),
+ *             S = ceil(steps / steps_per_slice).  Inside a slice the chain runs over m ascending from +0.0f; the slices' tiles go
+ *             to pool scratch and a second kernel adds them in slice order (S == 1 writes dw directly).
+ *             dz and db come from one streaming kernel over y and dy whose lanes run along n.  The M rows are cut into S' slices
+ *             of R rows, from (M, N) alone: want = min(M / 256, ceil(1024 / ceil(N / 64)), 256), at least 1, R = ceil(M / want)
+ *             rounded up to a multiple of 4, S' = ceil(M / R).  Inside a slice that begins at row m0, four row groups g = 0 .. 3
+ *             add rows m0 + g, m0 + g + 4, ... in ascending order from +0.0f, the four sums are added as ((s0 + s1) + s2) + s3,
+ *             the slices go to pool scratch and a second kernel adds them in slice order (S' == 1 writes db directly).
+ *             No float atomics anywhere; every result is bit-identical from run to run.  dw and db of a batch are not the sums of
+ *             the dws and dbs of its rows.
+ *   NaN       the reduction's tail and the tile edges are stored zeros on both operands: a NaN in row m of x reaches exactly row
+ *             m of y, a NaN in row n of w exactly column n, a NaN in bias[n] exactly column n.  A NaN in dy[m,n] reaches dz[m,n],
+ *             row m of dx, row n of dw and db[n]; an Inf or NaN dy over a relu-dead output (y <= 0) reaches nothing.
+ *   Backward  with NP_ACT_NONE dz = dy: dz is NOT written and neither y nor dz is read; both may be NULL.  With an activation dz is
+ *             a caller buffer of M.N floats that receives dz; it may be NULL only when dx and dw are both NULL (db alone).
+ *             Each of dx, dw and db may be NULL and then costs no launch; at least one must not be.  x is read for dw only and w
+ *             for dx only: either may be NULL when its product is not asked for.
+ *   Overlaps  forward: y may not overlap x, w or bias.  Backward: dz may be dy itself (dz == dy: an element is read and then
+ *             written by the same lane) and may not overlap dy in any other way; apart from that no written range (dz, dx, dw,
+ *             db) may overlap another written range or a range the call reads (x, w, y, dy).
+ *   Alignment any 4-byte-aligned pointer is accepted.  An operand whose pointer is 16-byte aligned and whose row length is a
+ *             multiple of 4 is staged with 16-byte loads, any other with dword loads; the choice is per operand and both give
+ *             the same bits.
+ * Convention as above: pointers are checked first, then the extents, the activation, the pointers an activation needs, the
+ * overlaps, then work begins.  NP_ERR_INVALID before any device work: a null required pointer; dx, dw and db all NULL; an extent
+ * of zero; M.N, M.K or N.K at 2^31 or more; an unknown act; a refused overlap.
+ *   Two forms each product (y, dx, dw) takes one of two forms, chosen per product from (M, K, N) alone: the tile form described above
+ *             below a constant number of multiply-adds M.K.N, the library form from it up.  The library form sends the product through
+ *             np_sgemm; the operand np_sgemm needs the other way round is first written to pool scratch by np_transpose2d (w for y,
+ *             dz for dw; dx needs none) and released on every path; bias and activation are ONE in-place pass over y (the same
+ *             one add, the same activation text).  Its results have the bits of the composition of the public calls np_transpose2d,
+ *             np_sgemm, an fp32 add and the activation, on equally aligned operands.  np_sgemm's plan depends on M: batch
+ *             invariance holds for the tile form only, and so do the summation orders stated above; the NaN rules, the
+ *             refusals and dz / db (always the streaming kernel above) are the same in both forms.  The constants are measured
+ *             (np_debug_linear_bounds reports them; DESIGN.md says which table fixed them). */
+int np_linear_forward(const float *x, const float *w, const float *bias /* may be NULL */, size_t M, size_t K, size_t N, int act, float *y);
+int np_linear_backward(const float *x, const float *w, const float *y, const float *dy, size_t M, size_t K, size_t N, int act,
+                       float *dz, float *dx, float *dw, float *db);
+
 /* ---- device-side initializers (the reference's own phpbench suite, benchmarks/initializers/) ------
  * The reference builds every array on the CPU (initializers.c) and a GPU user pays the PCIe copy on
  * ->gpu(); zeros / ones / full are np_memset0 / np_fill above.

@@ -233,6 +233,21 @@ int np_debug_optim_bounds(size_t bounds[], int n);
 /* testing / A-B: on != 0 serves every tensor of a step with scalar accesses, 0 (the default) chooses per tensor by the pointers'
  * residues.  Both forms give the same bits.  Process-global. */
 int np_debug_optim_force_scalar(int on);
+/* tests / tools: what the last np_linear_forward (product 0) or np_linear_backward (products 1 .. 3) of the process launched for
+ * one product: 0 = y, 1 = dx, 2 = dw, 3 = the dz / db kernel.  form: 1 = the tile form, 2 = the library form over np_sgemm (0: the last
+ * call did not launch this product; product 3 always reports 1).  tm: the tile's row count (32, 64 or 128; 0 for product 3 and for
+ * the library form).  slices: S of dw, S' of dz / db, 1 for y and dx; 0 for the library form.  launches: the kernels the product took
+ * (tile form: 1, or 2 with a fold; library form: the transpose, np_sgemm's own launches and the bias / activation pass).  A backward call clears products 1 .. 3 first, so a product that
+ * was not asked for reads (0, 0, 0, 0).  NP_ERR_INVALID on a null pointer or an unknown product.  Plain process globals. */
+int np_debug_linear_last_path(int product, int *form, int *tm, int *slices, int *launches);
+/* testing / A-B: form = 1 sends every product through the tile form, 2 through the library form, 0 (the default) chooses per
+ * product by (M, K, N).  NP_ERR_INVALID for any other value.  Process-global. */
+int np_debug_linear_force_form(int form);
+/* the constants, n >= 16: bounds[0 .. 2] = the three TM, bounds[3] = the tile's columns, bounds[4] = the reduction step,
+ * bounds[5 .. 7] = dw's slice rule (the fewest steps of a slice, the workgroups the slices aim for, the most slices),
+ * bounds[8 .. 12] = the dz / db kernel (the columns of a workgroup, its row groups, the fewest rows of a slice, the workgroups the
+ * slices aim for, the most slices), bounds[13 .. 15] = the multiply-adds M.K.N from which y, dx and dw take the library form */
+int np_debug_linear_bounds(size_t bounds[], int n);
 /* tests / tools: which kernel families the last np_reduce_axis or np_reduce_all(_dev) call of the process launched, the calls it
  * makes on its own partials included: the OR of the NP_REDUCE_PATH_ bits below (0 = none yet).  A plain process global, cleared
  * at the top of those entry points; calls the library makes itself (split-K GEMM folds, chain partials) overwrite it too. */

@@ -474,6 +474,15 @@ int NDArrayDNN_Adam_Step(NDArray **params, int n_params, NDArray **grads, int n_
                          int n_exp_avg_sq, long step, double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled,
                          NDArray *grad_scale, int grad_scale_index);
 NDArray *NDArrayDNN_GradNorm(NDArray **grads, int n_grads, double max_norm);
+/* Dense layers (host/numpower_dnn.cpp; the reference has none): GPU operands in torch's layout, x (..., K) with its leading axes
+ * flattened to rows, weight (N, K), bias a 1-D (N,) array or NULL; y = act(x . weight^T + bias), the bias ONE fp32 add after the
+ * reduction, activation 'r' relu, 't' tanh, 's' sigmoid, 'n' or 0 none, all in one kernel.  _Backward takes `out`, the forward
+ * result (NULL is allowed without an activation), and dy, its gradient, and returns a malloc'd vector of THREE in the conv
+ * layer's order: dW (N, K), dX in x's shape (NULL without need_dx: a first layer does not pay for it) and db (N,) (NULL without
+ * use_bias).  The caller frees the vector.  Views are made contiguous; NPH_Linear_Forward / _Backward over np_linear_forward /
+ * _backward do the work.  Errors: ext/hip_dnn.h, NPH_LINEAR_MSG_*. */
+NDArray *NDArrayDNN_Linear_Forward(NDArray *x, NDArray *weight, NDArray *bias, char activation);
+NDArray **NDArrayDNN_Linear_Backward(NDArray *x, NDArray *out, NDArray *dy, NDArray *weight, char activation, int use_bias, int need_dx);
 
 #ifdef __cplusplus
 }

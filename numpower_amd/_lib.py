@@ -172,6 +172,8 @@ PROTOTYPES = {
     "np_sgd_step": (C.c_int, [C.POINTER(C.c_void_p)] * 3 + [C.POINTER(C.c_size_t), C.c_size_t] + [C.c_double] * 4 + [C.c_int, C.c_int, _f32p]),
     "np_adam_step": (C.c_int, [C.POINTER(C.c_void_p)] * 4 + [C.POINTER(C.c_size_t), C.c_size_t, C.c_longlong] + [C.c_double] * 5 + [C.c_int, _f32p]),
     "np_grad_norm": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.c_double, _f32p]),
+    "np_linear_forward": (C.c_int, [_f32p] * 3 + [C.c_size_t] * 3 + [C.c_int, _f32p]),
+    "np_linear_backward": (C.c_int, [_f32p] * 4 + [C.c_size_t] * 3 + [C.c_int] + [_f32p] * 4),
     "np_permute": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "np_strided_copy": (C.c_int, [_f32p, _f32p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_longlong)]),
     "np_identity": (C.c_int, [_f32p, C.c_size_t]),
@@ -222,6 +224,9 @@ PROTOTYPES = {
     "np_debug_optim_last_path": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "np_debug_optim_bounds": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
     "np_debug_optim_force_scalar": (C.c_int, [C.c_int]),
+    "np_debug_linear_last_path": (C.c_int, [C.c_int] + [C.POINTER(C.c_int)] * 4),
+    "np_debug_linear_bounds": (C.c_int, [C.POINTER(C.c_size_t), C.c_int]),
+    "np_debug_linear_force_form": (C.c_int, [C.c_int]),
     "np_debug_reduce_last_path": (C.c_int, [C.POINTER(C.c_uint)]),
     "np_debug_chain_reduce_last_path": (C.c_int, [C.POINTER(C.c_uint)]),
     "np_clear_device_error": (C.c_int, [C.POINTER(C.c_uint)]),

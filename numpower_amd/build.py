@@ -32,7 +32,7 @@ OBJDIR = ROOT / "build" / "obj"
 HIP_SOURCES = ["np_runtime.hip", "np_elementwise.hip", "np_fused_chain.hip", "np_fused_static.hip", "np_reduce.hip", "np_argreduce.hip", "np_stats.hip",
                "np_sgemm.hip", "np_layout.hip", "np_select.hip", "np_comm.hip", "np_lu.hip", "np_cholesky.hip", "np_jacobi.hip",
                "np_signal.hip", "np_qr.hip", "np_dnn.hip", "np_pool.hip", "np_softmax.hip", "np_batchnorm.hip", "np_groupnorm.hip",
-               "np_attention.hip", "np_optim.hip"]
+               "np_attention.hip", "np_optim.hip", "np_linear.hip"]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{INCLUDE}", f"-I{CSRC}"]
 
 

@@ -50,25 +50,16 @@
 
 #include <type_traits>
 
-#include "np_elementwise_ops.h"   // the bodies of NP_TANH and NP_EXP; fp contraction is off in a unit that includes it
-#include "np_internal.h"
+#include "np_dnn_tile.h"   // act_apply / act_grad, the tile constants and mma_step: the text np_linear.hip compiles too
 
 namespace {
 
-// ---- tile constants (tests/test_gpu_dnn.py mirrors them) ----
-constexpr int kTN = 128;                  // columns of a tile: pixels jg (forward), reduction columns k (dW)
-constexpr int kTK = 32;                   // reduction step staged through LDS
-constexpr int kTMSmall = 32, kTMMid = 64, kTMLarge = 128;   // the TM instantiations
-constexpr int kAStr = kTK + 1, kBStr = kTN + 1;             // LDS row strides (odd: a column walk touches every bank)
-// dW: a slice is at least kWgradMinSteps steps long, slices stop once tiles x S reaches kWgradTargetGroups workgroups
-constexpr int kWgradMinSteps = 8, kWgradTargetGroups = 512, kWgradMaxSlices = 256;
+// ---- tile constants: np_dnn_tile.h; a tile's columns are pixels jg (forward) or reduction columns k (dW) ----
 
 // db (tests/test_gpu_dnn_act.py mirrors the rule): the M = N.P elements of a filter are cut into S slices,
 //   want = min(M / kActMinSlice, ceil(kActTargetGroups / F), kActMaxSlices), at least 1
 //   L = ceil(M / want) rounded up to a multiple of kActBlock,  S = ceil(M / L)
 constexpr int kActBlock = 256, kActMinSlice = 4096, kActTargetGroups = 2048, kActMaxSlices = 256;
-
-typedef float dnn_v16f __attribute__((ext_vector_type(16)));
 
 int g_dnn_last_tm = 0, g_dnn_last_slices = 0, g_dnn_last_form = 0;
 int g_dnn_last_act = 0, g_dnn_last_has_bias = 0, g_dnn_last_bias_slices = 0;
@@ -100,54 +91,7 @@ struct EpiArgs : KernelArgs<FORM> {
 template <int FORM, bool EPI>
 using FpropArgs = std::conditional_t<EPI, EpiArgs<FORM>, KernelArgs<FORM>>;
 
-// y = act(v).  relu: a NaN stays NaN, -0.0 becomes +0.0; sigmoid: 0 and 1 at -+Inf, NaN at NaN
-template <int ACT>
-__device__ __forceinline__ float act_apply(float v) {
-    if constexpr (ACT == NP_ACT_RELU) return (v <= 0.0f) ? 0.0f : v;
-    if constexpr (ACT == NP_ACT_TANH) return unary_apply<NP_TANH>(v, 0.0f, 0.0f);
-    if constexpr (ACT == NP_ACT_SIGMOID) return 1.0f / (1.0f + unary_apply<NP_EXP>(-v, 0.0f, 0.0f));
-    return v;
-}
-
-// dz = dy . act'(y) through the output y.  relu is a select: a NaN y passes dy, a dy over y <= 0 reaches nothing
-template <int ACT>
-__device__ __forceinline__ float act_grad(float y, float dy) {
-    if constexpr (ACT == NP_ACT_RELU) return (y <= 0.0f) ? 0.0f : dy;
-    if constexpr (ACT == NP_ACT_TANH) return dy * (1.0f - y * y);
-    if constexpr (ACT == NP_ACT_SIGMOID) return dy * ((1.0f - y) * y);
-    return dy;
-}
-
 int form_of(const ConvArgs &a) { return (a.lh != 1 || a.lw != 1) ? 2 : (a.sh != 1 || a.sw != 1 || a.dh != 1 || a.dw != 1) ? 1 : 0; }
-
-// how the 4 waves share a TM x kTN tile: 32 x 32 MFMA blocks, MI x NJ of them per wave
-template <int TM>
-struct Tile {
-    static constexpr int WM = TM >= 128 ? 2 : 1, WN = 4 / WM, MI = TM / (WM * 32), NJ = kTN / (WN * 32);
-};
-
-// the accumulator's row inside a 32 x 32 block: register r of a lane in half kq
-__device__ __forceinline__ int acc_row(int r, int kq) { return (r & 3) + 8 * (r >> 2) + 4 * kq; }
-
-// one staged step: acc += As (TM x kTK) . Bs (kTK x kTN), k ascending
-template <int TM>
-__device__ __forceinline__ void mma_step(const float *As, const float *Bs, dnn_v16f (&acc)[Tile<TM>::MI][Tile<TM>::NJ], int wm, int wn,
-                                         int lane) {
-    using T = Tile<TM>;
-    const int i = lane & 31, kq = lane >> 5;
-#pragma unroll
-    for (int kk = 0; kk < kTK; kk += 2) {
-        float a[T::MI], b[T::NJ];
-#pragma unroll
-        for (int mi = 0; mi < T::MI; ++mi) a[mi] = As[((wm * T::MI + mi) * 32 + i) * kAStr + kk + kq];
-#pragma unroll
-        for (int nj = 0; nj < T::NJ; ++nj) b[nj] = Bs[(kk + kq) * kBStr + (wn * T::NJ + nj) * 32 + i];
-#pragma unroll
-        for (int mi = 0; mi < T::MI; ++mi)
-#pragma unroll
-            for (int nj = 0; nj < T::NJ; ++nj) acc[mi][nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mi], b[nj], acc[mi][nj], 0, 0, 0);
-    }
-}
 
 // k = (c.kh + p).kw + q -> the tap's offset inside one image of x and its (p.dh, q.dw); koff = -1 marks the reduction's tail.
 // Form 2: (kp, kq) are the quotients of p.dh, q.dw by the input dilation and (rp, rq) the residues, koff is built from the quotients.
@@ -469,12 +413,6 @@ __global__ __launch_bounds__(256) void dnn_bias_fold_kernel(const float *__restr
     for (int s = 1; s < slices; ++s) acc += part[(size_t)s * F + f];
     db[f] = acc;
 }
-
-int pick_tm(size_t F) { return F <= (size_t)kTMSmall ? kTMSmall : F <= (size_t)kTMMid ? kTMMid : kTMLarge; }
-
-constexpr size_t kLim = (size_t)1 << 31;
-// a * b, saturating at kLim (both factors at most kLim)
-size_t mul_lim(size_t a, size_t b) { return (a >= kLim || b >= kLim || a * b >= kLim) ? kLim : a * b; }
 
 // a layer as the C ABI names it; the plain entry points have stride and dilation 1, np_conv2d_shape* N = C = F = 1
 struct LayerShape {

@@ -284,4 +284,19 @@ NDArray *NDArrayDNN_GradNorm(NDArray **grads, int n_grads, double max_norm) {
     return NPH_GradNorm(l.at(0), n_grads, max_norm);
 }
 
+// Dense layers (np_linear_forward / _backward), which the reference does not have either.  bias may be nullptr;
+// out may be nullptr without an activation.
+NDArray *NDArrayDNN_Linear_Forward(NDArray *x, NDArray *weight, NDArray *bias, char activation) {
+    if (!x || !weight) return nullptr;
+    return on_contiguous([=](NDArray *cx, NDArray *cw, NDArray *cb, NDArray *) { return NPH_Linear_Forward(cx, cw, cb, activation); }, x, weight, bias);
+}
+
+// a malloc'd vector of three: dW, dX (nullptr without need_dx) and db (nullptr without use_bias)
+NDArray **NDArrayDNN_Linear_Backward(NDArray *x, NDArray *out, NDArray *dy, NDArray *weight, char activation, int use_bias, int need_dx) {
+    if (!x || !dy || !weight) return nullptr;
+    return on_contiguous([=](NDArray *cx, NDArray *cy, NDArray *cw, NDArray *co) {
+        return NPH_Linear_Backward(cx, co, cy, cw, activation, use_bias, need_dx);
+    }, x, dy, weight, out);
+}
+
 }  // extern "C"

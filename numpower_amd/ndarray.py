@@ -176,6 +176,8 @@ def _load_host():
     sig["NDArrayDNN_SGD_Step"] = (C.c_int, [pp, C.c_int] * 3 + [C.c_double] * 4 + [C.c_int, C.c_int, _P, C.c_int])
     sig["NDArrayDNN_Adam_Step"] = (C.c_int, [pp, C.c_int] * 4 + [C.c_long] + [C.c_double] * 5 + [C.c_int, _P, C.c_int])
     sig["NDArrayDNN_GradNorm"] = (_P, [pp, C.c_int, C.c_double])
+    sig["NDArrayDNN_Linear_Forward"] = (_P, [_P, _P, _P, C.c_char])
+    sig["NDArrayDNN_Linear_Backward"] = (C.POINTER(_P), [_P, _P, _P, _P, C.c_char, C.c_int, C.c_int])
     sig["NDArray_SVD"] = (C.POINTER(_P), [_P])
     sig["NDArray_Eig"] = (C.POINTER(_P), [_P])
     sig["NDArray_Qr"] = (C.POINTER(_P), [_P])
@@ -904,9 +906,9 @@ class NDArray:
     _DNN_ACTIVATIONS = {None: b"n", "relu": b"r", "tanh": b"t", "sigmoid": b"s"}
 
     @staticmethod
-    def _dnn_activation(activation):
+    def _dnn_activation(activation, who="dnn_conv2d"):
         if not (activation is None or isinstance(activation, str)) or activation not in NDArray._DNN_ACTIVATIONS:
-            raise Error("dnn_conv2d: activation must be None, 'relu', 'tanh' or 'sigmoid', not %r" % (activation,))
+            raise Error("%s: activation must be None, 'relu', 'tanh' or 'sigmoid', not %r" % (who, activation))
         return NDArray._DNN_ACTIVATIONS[activation]
 
     @staticmethod
@@ -1273,6 +1275,40 @@ class NDArray:
         limit = NDArray._optim_number(who, "max_norm", max_norm)
         keep = NDArray._optim_list(who, "grads", grads)
         return NDArray(h.NDArrayDNN_GradNorm(keep[1], keep[2], limit))
+
+    @staticmethod
+    def dnn_linear_forward(x, weight, bias=None, activation=None):      # the reference has no dense layer
+        """y (..., N) = act(x . weight^T + bias) of GPU arrays in torch's layout: x (..., K), its leading axes
+        flattened to rows; weight (N, K); bias a 1-D array (N,) or None, ONE fp32 add after the reduction; activation None,
+        'relu', 'tanh' or 'sigmoid', applied in the same kernel.  Every output is one fp32 fmaf chain over k ascending: a row
+        alone gives the bits it gives inside any batch."""
+        h = _load_host()
+        act = NDArray._dnn_activation(activation, "dnn_linear")
+        a, _ = NDArray._coerce(x)
+        w, _ = NDArray._coerce(weight)
+        b = None if bias is None else NDArray._coerce(bias)[0]
+        return NDArray._wrap(h.NDArrayDNN_Linear_Forward(a._p, w._p, None if b is None else b._p, act))
+
+    @staticmethod
+    def dnn_linear_backward(x, dy, weight, out=None, activation=None, bias=False, need_dx=True):
+        """(dW (N, K), dX in x's shape) for dy = the gradient of dnn_linear_forward(x, weight, ...), the conv layer's order; with
+        bias=True (dW, dX, db) with db (N,).  need_dx=False: dX is None and costs no launch (a first layer).  For a layer with
+        an activation pass it and `out`, the forward RESULT: the gradient goes through act'(out) first (relu: a select on
+        out <= 0; tanh: 1 - out^2; sigmoid: (1 - out) out).  No transposed copy of x, weight or dy is made."""
+        h = _load_host()
+        act = NDArray._dnn_activation(activation, "dnn_linear")
+        if activation is not None and out is None:
+            raise Error("dnn_linear_backward: an activation needs out, the forward result (gradients are expressed through the output)")
+        a, _ = NDArray._coerce(x)
+        g, _ = NDArray._coerce(dy)
+        w, _ = NDArray._coerce(weight)
+        o = None if out is None or activation is None else NDArray._coerce(out)[0]
+        rtns = h.NDArrayDNN_Linear_Backward(a._p, None if o is None else o._p, g._p, w._p, act, 1 if bias else 0, 1 if need_dx else 0)
+        if not rtns:
+            _raise_pending(h)
+        results = tuple(NDArray(C.cast(rtns[i], _P)) if rtns[i] else None for i in range(3 if bias else 2))
+        _libc_free(C.cast(rtns, C.c_void_p))
+        return results
 
     def copy(self):          # PHP_METHOD copy: NDArray_Copy on the array's own device
         return NDArray._wrap(_load_host().NDArray_Copy(self._p, C.cast(self._p, _P).contents.device))

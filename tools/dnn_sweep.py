@@ -60,6 +60,17 @@ ATTENTION_SHAPES, causal and not.  Reported: ms, the useful TFLOP/s (4.BH.Sq.Sk.
 and its fraction of the 157.3 TFLOP/s fp32 matrix peak; for the forward pass without causal also the ratio to the composition from
 NDArray calls (batched_matmul on a transposed k, a multiply, softmax, batched_matmul) and to np_sgemm_strided_batched on the two
 products alone, alternating round by round in one session.  Writes profiles/dnn/attention_sweep.log.
+--linear is the leg of the dense layer (np_linear.hip) on LINEAR_SHAPES (M, K, N), from below the examples' sizes to 4096^3.  Per shape,
+in one child: each of the three products (y = x . w^T, dx = dz . w, dw = dz^T . x) with the tile form forced and with the library form
+forced (np_debug_linear_force_form), alternating round by round, and bare np_sgemm on dense, already transposed operands of the same
+extents as information, with ms, TFLOP/s, the fraction of the 157.3 TFLOP/s fp32 matrix peak, TM and S, which form is faster and which
+form the unforced call takes: the dispatcher's constants (the work M.K.N from which a product takes the library form) are set where
+the faster form changes in this table; then the whole layer, unforced, with a bias and tanh, forward and backward
+(y, dz, dx, dw, db), against the composition from NDArray calls the examples used (transposes, bare products, a broadcast add, the
+activation, its gradient, a column sum) and against the 1 x 1 convolution route (np_conv2d_forward_act, np_conv2d_backward_act,
+np_conv2d_backward_filter, np_conv2d_backward_data); then the dz / db kernel alone against the float4 copy of its 12 bytes per element.
+A shape where the layer is slower than the composition by more than the composition's own spread is marked FINDING.  Writes
+profiles/dnn/linear_sweep.log.
 
 Usage: python tools/dnn_sweep.py [--layers 0,1,...] [--rounds N] [--limit S] [--torch] [--out FILE]
        python tools/dnn_sweep.py --act [--layers ...]         the bias / activation leg
@@ -70,6 +81,7 @@ Usage: python tools/dnn_sweep.py [--layers 0,1,...] [--rounds N] [--limit S] [--
        python tools/dnn_sweep.py --groupnorm [--layers ...]   the layer / group normalization leg
        python tools/dnn_sweep.py --attention [--layers ...]   the attention leg
        python tools/dnn_sweep.py --optim [--layers ...]       the optimizer leg
+       python tools/dnn_sweep.py --linear [--layers ...]      the dense-layer leg
        python tools/dnn_sweep.py --profile LAYER     three calls of each operation and nothing else, for a run under the kernel profiler"""
 import argparse
 import statistics
@@ -120,6 +132,8 @@ GROUPNORM_SHAPES = [("layer (65536, 1024)", (65536, 1, 1024, 1), True), ("layer 
 ATTENTION_SHAPES = [(64, 512, 64), (64, 2048, 64), (16, 8192, 64), (64, 2048, 128), (512, 197, 64), (64, 2048, 32)]
 MATRIX_PEAK_TFLOPS = 157.3
 
+LINEAR_SHAPES = [(32, 32, 32), (64, 64, 32), (128, 64, 64), (128, 128, 64), (128, 256, 128), (256, 128, 128), (256, 256, 256), (4096, 64, 10), (16, 1024, 1024),
+                 (512, 784, 256), (1024, 1024, 1024), (4096, 1024, 1024), (8192, 4096, 1024), (128, 4096, 4096), (4096, 4096, 4096)]      # (M, K, N)
 OPTIM_CASES = ["one tensor of 10^8", "ResNet-like list of 301 tensors, 10^8 in all", "300 tensors of 1000: wall time of a step", "np_grad_norm"]
 OPTIM_TOTAL = 10 ** 8
 
@@ -136,6 +150,7 @@ def optim_resnet_like():
 ap = argparse.ArgumentParser()
 ap.add_argument("--batchnorm", action="store_true")
 ap.add_argument("--optim", action="store_true")
+ap.add_argument("--linear", action="store_true")
 ap.add_argument("--groupnorm", action="store_true")
 ap.add_argument("--attention", action="store_true")
 ap.add_argument("--pool", action="store_true")
@@ -152,9 +167,9 @@ ap.add_argument("--profile", type=int, default=None)
 ap.add_argument("--child", default=None, help="internal: 'layer:<i>' or 'torch'")
 args = ap.parse_args()
 if args.layers is None:
-    args.layers = ",".join(str(i) for i in range(len(OPTIM_CASES if args.optim else ATTENTION_SHAPES if args.attention else GROUPNORM_SHAPES if args.groupnorm else BATCHNORM_SHAPES if args.batchnorm else SOFTMAX_SHAPES if args.softmax else POOL_LAYERS if args.pool else LAYERS)))
+    args.layers = ",".join(str(i) for i in range(len(LINEAR_SHAPES if args.linear else OPTIM_CASES if args.optim else ATTENTION_SHAPES if args.attention else GROUPNORM_SHAPES if args.groupnorm else BATCHNORM_SHAPES if args.batchnorm else SOFTMAX_SHAPES if args.softmax else POOL_LAYERS if args.pool else LAYERS)))
 if args.out is None:
-    args.out = str(ROOT / "profiles" / "dnn" / ("optim_sweep.log" if args.optim else "attention_sweep.log" if args.attention else "groupnorm_sweep.log" if args.groupnorm else "batchnorm_sweep.log" if args.batchnorm else "softmax_sweep.log" if args.softmax else "pool2d_sweep.log" if args.pool else "conv2d_act_sweep.log" if args.act else
+    args.out = str(ROOT / "profiles" / "dnn" / ("linear_sweep.log" if args.linear else "optim_sweep.log" if args.optim else "attention_sweep.log" if args.attention else "groupnorm_sweep.log" if args.groupnorm else "batchnorm_sweep.log" if args.batchnorm else "softmax_sweep.log" if args.softmax else "pool2d_sweep.log" if args.pool else "conv2d_act_sweep.log" if args.act else
                                                "conv2d_forward_only.log" if args.forward_only else "conv2d_sweep.log"))
 LARGE = (256, 128, 3136)                        # (N, F, P) of the large case of --act: 1.03e8 elements
 HBM_TBS = 8.0
@@ -684,6 +699,128 @@ def run_optim(i, rounds):
             flat.free()
 
 
+def run_linear(i, rounds):
+    """one shape: the three products against bare np_sgemm, the whole layer against the NDArray composition and the 1 x 1 convolution
+    route, the dz / db kernel against the float4 copy, alternating round by round in one session"""
+    import ctypes as C
+    import numpy as np
+    D, lib, check, ramp, _ = _setup()
+    from numpower_amd._lib import Timer
+    from numpower_amd.ndarray import NDArray as nd
+    t = Timer()
+    M, K, N = LINEAR_SHAPES[i]
+    rng = np.random.default_rng(i)
+    draw = lambda *shape: np.resize(rng.standard_normal(1 << 20).astype(np.float32), int(np.prod(shape))).reshape(shape)
+    hx, hw, hb, hdy = draw(M, K), draw(N, K) * np.float32(1.0 / np.sqrt(K)), draw(N), draw(M, N)
+    x, w, b, dy = (D.DeviceArray.from_host(h) for h in (hx, hw, hb, hdy))
+    y, dz, dx, dw, db = D.DeviceArray((M, N)), D.DeviceArray((M, N)), D.DeviceArray((M, K)), D.DeviceArray((N, K)), D.DeviceArray((N,))
+    wt = D.DeviceArray.from_host(np.ascontiguousarray(hw.T))       # dense operands of the bare products, made outside the timing
+    dyt = D.DeviceArray.from_host(np.ascontiguousarray(hdy.T))
+    c1, c2 = D.DeviceArray((3 * M * N // 2 + 4,)), D.DeviceArray((3 * M * N // 2 + 4,))
+    gx, gw, gb, gdy = (nd.array(h).gpu() for h in (hx, hw, hb, hdy))
+    TANH = 2
+    chosen = C.c_int(0)
+
+    def timed(fn, reps):
+        t.start()
+        for _ in range(reps):
+            fn()
+        t.stop()
+        return t.elapsed_ms() / reps
+
+    def probe(product):
+        v = [C.c_int(0) for _ in range(4)]
+        check(lib.np_debug_linear_last_path(product, *(C.byref(c) for c in v)))
+        return v[1].value, v[2].value
+
+    def against(fn, others, divide=4):
+        """-> the rounds of fn and of every other, alternating"""
+        for f in [fn] + others:
+            for _ in range(2):
+                f()
+        D.sync()
+        t0 = time.time()
+        fn()
+        D.sync()
+        reps = max(3, min(100, int(0.05 / max(time.time() - t0, 1e-5))))
+        op_ms, other_ms = [], [[] for _ in others]
+        for _ in range(rounds):
+            op_ms.append(timed(fn, reps))
+            for f, ms in zip(others, other_ms):
+                ms.append(timed(f, max(2, reps // divide)))
+        return op_ms, other_ms
+
+    fwd_plain = lambda: check(lib.np_linear_forward(x.ptr, w.ptr, None, M, K, N, 0, y.ptr))
+    only_dx = lambda: check(lib.np_linear_backward(None, w.ptr, None, dy.ptr, M, K, N, 0, None, dx.ptr, None, None))
+    only_dw = lambda: check(lib.np_linear_backward(x.ptr, None, None, dy.ptr, M, K, N, 0, None, None, dw.ptr, None))
+    gemm_y = lambda: check(lib.np_sgemm(M, N, K, x.ptr, wt.ptr, y.ptr))
+    gemm_dx = lambda: check(lib.np_sgemm(M, K, N, dy.ptr, w.ptr, dx.ptr))
+    gemm_dw = lambda: check(lib.np_sgemm(N, K, M, dyt.ptr, x.ptr, dw.ptr))
+    ramp()
+    flop = 2.0 * M * N * K
+    def forced(form, fn):
+        def run():
+            check(lib.np_debug_linear_force_form(form))
+            fn()
+            check(lib.np_debug_linear_force_form(0))
+        return run
+
+    for label, fn, gemm, product in (("y  = x . w^T", fwd_plain, gemm_y, 0), ("dx = dz . w", only_dx, gemm_dx, 1), ("dw = dz^T . x", only_dw, gemm_dw, 2)):
+        t_ms, (l_ms, g_ms) = against(forced(1, fn), [forced(2, fn), gemm], 1)
+        forced(1, fn)()
+        tm, S = probe(product)
+        fn()
+        check(lib.np_debug_linear_last_path(product, *(C.byref(c) for c in (chosen, C.c_int(), C.c_int(), C.c_int()))))
+        tm_, lm, gm = statistics.median(t_ms), statistics.median(l_ms), statistics.median(g_ms)
+        print("(%d, %d, %d) work %.3g %-14s tile form TM %3d S %3d %9.4f ms %7.2f TFLOP/s %5.3f of the matrix peak (min %.4f max %.4f)   library form %9.4f ms %7.2f TFLOP/s "
+              "%5.3f of the peak (min %.4f max %.4f)   tile / library %5.2f: the %s form is faster; unforced takes form %d   np_sgemm alone %9.4f ms (min %.4f max %.4f)"
+              % (M, K, N, float(M) * K * N, label, tm, S, tm_, flop / tm_ * 1e-9, flop / tm_ * 1e-9 / MATRIX_PEAK_TFLOPS, min(t_ms), max(t_ms), lm, flop / lm * 1e-9,
+                 flop / lm * 1e-9 / MATRIX_PEAK_TFLOPS, min(l_ms), max(l_ms), tm_ / lm, "library" if lm < tm_ else "tile", chosen.value, gm, min(g_ms), max(g_ms)), flush=True)
+
+    def layer():
+        check(lib.np_linear_forward(x.ptr, w.ptr, b.ptr, M, K, N, TANH, y.ptr))
+        check(lib.np_linear_backward(x.ptr, w.ptr, y.ptr, dy.ptr, M, K, N, TANH, dz.ptr, dx.ptr, dw.ptr, db.ptr))
+
+    def composition():
+        gy = nd.tanh(nd.matmul(gx, nd.transpose(gw)) + gb)
+        gz = gdy * (1.0 - gy * gy)
+        return nd.sum(gz, 0), nd.matmul(nd.transpose(gz), gx), nd.matmul(gz, gw)
+
+    dims = (M, K, 1, 1, N, 1, 1, 0, 0)
+
+    def conv_route():
+        check(lib.np_conv2d_forward_act(x.ptr, w.ptr, b.ptr, *dims, 1, 1, 1, 1, TANH, y.ptr))
+        check(lib.np_conv2d_backward_act(y.ptr, dy.ptr, M, N, 1, TANH, dz.ptr, db.ptr))
+        check(lib.np_conv2d_backward_filter(x.ptr, dz.ptr, *dims, dw.ptr))
+        check(lib.np_conv2d_backward_data(dz.ptr, w.ptr, *dims, dx.ptr))
+
+    others, names = [conv_route], ["1 x 1 convolution route"]
+    try:
+        composition()
+        others, names = [composition] + others, ["NDArray composition"] + names
+    except Exception as e:      # a composition this build cannot express is named, not hidden
+        print("(%d, %d, %d) the NDArray composition is not expressed: %s" % (M, K, N, str(e)[:100]), flush=True)
+    op_ms, other_ms = against(layer, others)
+    om = statistics.median(op_ms)
+    tail = ""
+    for name, ms in zip(names, other_ms):
+        med = statistics.median(ms)
+        tail += "   %s %9.4f ms (min %.4f max %.4f) / layer %6.2f" % (name, med, min(ms), max(ms), med / om)
+        if name == "NDArray composition" and om > med + (max(ms) - min(ms)):
+            tail += "  FINDING: the layer is slower than the composition by more than its spread"
+    print("(%d, %d, %d) layer, bias and tanh, forward + backward (y, dz, dx, dw, db) %9.4f ms %7.2f TFLOP/s (min %.4f max %.4f)%s"
+          % (M, K, N, om, 3 * flop / om * 1e-9, min(op_ms), max(op_ms), tail), flush=True)
+
+    act_only = lambda: check(lib.np_linear_backward(None, None, y.ptr, dy.ptr, M, K, N, TANH, dz.ptr, None, None, db.ptr))
+    nbytes = 12 * M * N
+    copy = lambda: check(lib.np_memcpy_d2d(c1.ptr, c2.ptr, nbytes // 2))
+    op_ms, (c_ms,) = against(act_only, [copy], 1)
+    act_only()
+    om, cm = statistics.median(op_ms), statistics.median(c_ms)
+    print("(%d, %d, %d) dz and db (tanh), S %3d %9.4f ms %5.2f TB/s (min %.4f max %.4f)   float4 copy of the same bytes %9.4f ms %5.2f TB/s (min %.4f max %.4f)   "
+          "copy / kernel %5.2f" % (M, K, N, probe(3)[1], om, nbytes / om * 1e-9, min(op_ms), max(op_ms), cm, nbytes / cm * 1e-9, min(c_ms), max(c_ms), cm / om), flush=True)
+
+
 def run_groupnorm(i, rounds, sets):
     """one shape: forward, backward with the parameter gradients, backward without them, each alternating with a float4 copy of the
     bytes its forms move; for the 2-D shapes the forward pass also with the NDArray composition and batch norm's rows form"""
@@ -1008,6 +1145,8 @@ if args.child:
         run_pool(int(args.child.split(":")[1]), args.rounds, args.sets)
     elif args.child.startswith("batchnorm:"):
         run_batchnorm(int(args.child.split(":")[1]), args.rounds, args.sets)
+    elif args.child.startswith("linear:"):
+        run_linear(int(args.child.split(":")[1]), args.rounds)
     elif args.child.startswith("optim:"):
         run_optim(int(args.child.split(":")[1]), args.rounds)
     elif args.child.startswith("attention:"):
@@ -1045,8 +1184,17 @@ def child(what):
     return proc.returncode == 0
 
 
-kind = "optim" if args.optim else "attention" if args.attention else "groupnorm" if args.groupnorm else "batchnorm" if args.batchnorm else "softmax" if args.softmax else "pool" if args.pool else "act" if args.act else "fwd" if args.forward_only else "layer"
-if args.optim:
+kind = "linear" if args.linear else "optim" if args.optim else "attention" if args.attention else "groupnorm" if args.groupnorm else "batchnorm" if args.batchnorm else "softmax" if args.softmax else "pool" if args.pool else "act" if args.act else "fwd" if args.forward_only else "layer"
+if args.linear:
+    import hashlib
+    say("np_linear_forward / np_linear_backward, (M, K, N): each product against bare np_sgemm on dense operands of the same extents; the whole layer (a bias, "
+        "tanh; y, dz, dx, dw, db) against the composition from NDArray calls and against the 1 x 1 convolution route; the dz / db kernel against np_memcpy_d2d "
+        "(the float4 copy) of the same bytes; alternating round by round in one process; TFLOP/s from 2 M N K per product against the %.1f TFLOP/s fp32 matrix "
+        "peak; fp32, ms per call, medians of %d rounds.  Every product is timed with the tile form forced and with the library form forced; work = M.K.N is what "
+        "the dispatcher compares with its constant per product; the layer and the dz / db kernel run unforced." % (MATRIX_PEAK_TFLOPS, args.rounds))
+    say("sources: " + ", ".join("%s sha256 %s" % (f, hashlib.sha256((ROOT / "numpower_amd" / "csrc" / f).read_bytes()).hexdigest()[:16])
+                                for f in ("np_linear.hip", "np_dnn_tile.h", "np_internal.h")))
+elif args.optim:
     import hashlib
     say("np_sgd_step / np_adam_step / np_grad_norm: the step against np_memcpy_d2d (the float4 copy) of the same bytes and against np_binary add over the same "
         "bytes, alternating round by round in one process; the wall time of a step over 300 small tensors against the NDArray compositions; the norm against "
